@@ -9,10 +9,15 @@ the fixed-size per-pair result records (match counts) of every step (= a rank's 
 asynchronous RCCL all_gather that overlaps the next step's kernels.
 
 Rank 0 prints, LAST, one JSON line shorter than 4 KB with `roofline` (dominant kernel, measured live with HIP events inside the library,
-see mlpl_profile_*) and `cpu_baseline` (the oracle's single-thread LUT port timed on this host).  Before it: one `bench_detail {...}` line
-(everything: extras, per-step arrays, notes; also written to bench_detail.json) and one `bench_secondary {...}` line (C3 RANSAC hyp/s and
-config 5, each with its own roofline and cpu_baseline) -- see bench_record.py.  The C5 measurement itself lives in bench_c5.py, the other
-secondary measurements in bench_extras.py.
+see mlpl_profile_*) and, with --full, `cpu_baseline` (the oracle's single-thread LUT port timed on this host).  Before it: one
+`bench_detail {...}` line (everything: extras, per-step arrays, notes; also written to bench_detail.json) and one `bench_secondary {...}`
+line (with --full: C3 RANSAC hyp/s and config 5, each with its own roofline and cpu_baseline) -- see bench_record.py.  The C5 measurement
+itself lives in bench_c5.py, the other secondary measurements in bench_extras.py.
+
+A plain run (no --full) only sets up, settles and warms up, times exactly --steps steps and prints the lines; everything beside the
+headline (steady state, single-pair / 8-pair shapes, CPU baselines and the CPU check of the timed step, after-idle launches, C3 / C4 / C5
+extras) runs with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs are seeded: two builds
+can be compared output for output).
 
 `python bench.py --gpus N` works by itself: when N > 1 and no torch.distributed environment is present, this process starts the N
 rank processes (python -m torch.distributed.run on 127.0.0.1) BEFORE it touches the GPU and relays their output; under an external
@@ -84,13 +89,50 @@ def run_c5(args, rank, local_rank, world, dev, ctx):
 
 
 RCCL_RANKS_SEEN = {}
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: what a caller of match_hamming_device receives from the last timed step, as float32 .npy files (every value is an
+    integer below 2^24 or an fp32 distance, so the conversion is exact): idx / dist [B, nq, 2], matches [B, nq, 4] (queryIdx, trainIdx,
+    imgIdx, distance; rows at and beyond a pair's count are -1, the library leaves them unwritten), count [B].  Past DUMP_MAX_BYTES a fixed
+    sample of pairs (and, if one pair alone is too large, of queries) is written, its indices as pair_index.npy / query_index.npy."""
+    import numpy as np
+
+    idx, dist = out["idx"].cpu().numpy(), out["dist"].cpu().numpy()
+    count = out["count"].cpu().numpy()
+    m = out["matches"].cpu().numpy()
+    B, nq = idx.shape[:2]
+    matches = np.concatenate([m[..., :3].astype(np.float32), m[..., 3:].view(np.float32)], axis=-1)
+    matches[np.arange(nq)[None, :] >= count[:, None]] = -1.0
+    arrays = {"idx": idx.astype(np.float32), "dist": dist.astype(np.float32), "matches": matches, "count": count.astype(np.float32)}
+    per_query = 4 * (idx.shape[2] + dist.shape[2] + matches.shape[2])
+    rng = np.random.default_rng(20260102)
+    if B * nq * per_query > DUMP_MAX_BYTES:
+        keep_q = max(1, min(nq, DUMP_MAX_BYTES // per_query))
+        keep_b = max(1, min(B, DUMP_MAX_BYTES // (keep_q * per_query)))
+        pb = np.sort(rng.choice(B, keep_b, replace=False))
+        pq = np.sort(rng.choice(nq, keep_q, replace=False)) if keep_q < nq else np.arange(nq)
+        arrays = {k: (v[pb] if k == "count" else v[pb][:, pq]) for k, v in arrays.items()}
+        arrays["pair_index"] = pb.astype(np.float32)
+        if keep_q < nq:
+            arrays["query_index"] = pq.astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; --workload c5: 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps before the timed ones (default 20; --workload c5: 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: steady state, single-pair / 8-pair shapes, CPU baselines and the CPU check of "
+                         "the timed step, the after-idle launches, C3 / C4 / C5 extras.  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (idx, dist, matches, count of rank 0's pairs) as DIR/<name>.npy, float32")
     ap.add_argument("--pairs-per-gpu", type=int, default=64, help="image pairs per rank per step (one batched launch per kernel)")
     ap.add_argument("--n", type=int, default=8192, help="descriptors per image")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -127,6 +169,13 @@ def main():
     ap.add_argument("--estimator", default="ransac", choices=["ransac", "usac", "usac_prosac", "usac_default_refine", "arrsac"],
                     help="robust estimator of the C5 pipeline (--workload c5 and the c5 object of the default line)")
     args = ap.parse_args()
+    # the defaults are sized for the C2 step; a C5 step is a whole batch.  An explicit --steps / --warmup is always taken as given.
+    if args.steps is None:
+        args.steps = 5 if args.workload == "c5" else 200
+    if args.warmup is None:
+        args.warmup = 2 if args.workload == "c5" else 20
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs writes the C2 step's outputs (--workload c5 has --dump-records)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))          # before any GPU call: this process only launches and relays
@@ -173,8 +222,6 @@ def main():
     # (the timed region and the steady-state pass run the PRODUCTION kernel: no clock stamps; a separate stamped pass behind them records
     #  the shader clock -- hamming_stamps = 2 adds two clock reads and one 32-byte store to the kernel's first workgroup)
     if args.workload == "c5":
-        if args.steps == 200 and args.warmup == 20:   # the defaults are sized for the C2 step; a C5 step is a whole batch
-            args.steps, args.warmup = 5, 2
         run_c5(args, rank, local_rank, world, dev, ctx)
         if dist_on(world):
             dist.barrier()
@@ -278,10 +325,12 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed, kern_ms, n_bracketed, ms_steps_gpu, clk_timed = timed_region(args.steps, bool(args.step_events))
+    if args.dump_outputs and rank == 0:   # before anything else reuses the result buffers: exactly what the last timed step returned
+        dump_outputs(args.dump_outputs, out)
     # steady state (VERDICT r4 #1b): the driver's protocol (20 steps after 5 warm-ups) times the first ~11 ms of GPU work after the input
     # upload; the same step in a long run is measured right behind it, same buffers, same verification below.  `value` stays the former.
     steady = None
-    if args.steady_steps > args.steps and args.steady_steps > 0:
+    if args.full and args.steady_steps > args.steps and args.steady_steps > 0:
         st_el, st_kern, st_n, _, _ = timed_region(args.steady_steps, False)
         steady = {"steps": args.steady_steps, "ms_per_step": st_el / args.steady_steps * 1e3, "kernel_ms_avg": st_kern, "launches_timed": st_n,
                   "value": world * P * n * n * args.steady_steps / st_el, "clock_GHz_median": None}
@@ -306,7 +355,7 @@ def main():
     assert all(abs(c - n // 2) <= max(8, n // 100) for c in counts), f"match counts {counts} are not ~{n // 2}"
     # the literal config 2 (ONE image pair per launch, latency shape) beside the batched headline
     single_ms = eight_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         o1 = match_hamming_device(d_q[:1], d_t[:1], ratio_test=True, ratio=0.75, ctx=ctx, stream=stream)
         for _ in range(50):   # (the first calls of a new launch shape size its workspaces and split tables)
             o1 = match_hamming_device(d_q[:1], d_t[:1], ratio_test=True, ratio=0.75, ctx=ctx, out=o1, stream=stream)
@@ -454,7 +503,7 @@ def main():
             "steady_state": steady,
         }
         rec["config"]["hamming_train_operand"] = "{0,+1}" if ctx.get_option("hamming_train01") == 1 else "+-1"
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib
             ora = oracle_lib.load()
@@ -488,7 +537,7 @@ def main():
         # while the inputs are generated and uploaded.  The clock and duration of the first launches from that state, launch by launch,
         # tell a clock / power ramp (clock rises or falls over the launches) from first-touch effects (only launch 0 is slow) and from a
         # slow box (every figure low, steady state included).  Same buffers as the timed steps; not part of any reported rate.
-        if args.after_idle_launches > 0 and mfma_path:
+        if args.full and args.after_idle_launches > 0 and mfma_path:
             if args.no_cpu_baseline:
                 time.sleep(2.0)
             k = min(args.after_idle_launches, 200)
@@ -509,7 +558,7 @@ def main():
                                          "shader clock inside each launch"}
             rec["timed_region"] = {"ms_steps_gpu": [round(x, 4) for x in ms_steps_gpu] if ms_steps_gpu else None}
             rec["config"]["clock_GHz_stamped_median"] = float(np.median(ai_ghz)) if len(ai_ghz) else None   # of the after-idle launches
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             try:
                 import bench_extras
                 rec["extras"] = bench_extras.run(ctx, dev, cpu_baseline=not args.no_cpu_baseline)
@@ -518,7 +567,7 @@ def main():
     # north_star's config 5 (the whole per-pair pipeline, sharded over the ranks, records + match lists gathered) beside the headline at
     # EVERY N, so that a scaling run measures the RANSAC / cheirality half too -- not part of `value`, its own barrier-bracketed regions
     c5 = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         c5 = measure_c5(args, rank, local_rank, world, dev, ctx, max(args.c5_steps, 5), 2, cpu_baseline=not args.no_cpu_baseline)
     if rank == 0:
         # BASELINE's metric is "descriptor-pairs/s + RANSAC hyp/s; 1/2/4/8 GPU": the second half (C3) and the batch of config 5 are

@@ -1,6 +1,7 @@
 """CPU tests of the ARRSAC oracle (oracle/arrsac_oracle.cpp): its building blocks against independent statements and against the
 fixtures under tests/golden/ (Eigen's JacobiSVD from the reference's vendored Eigen; the oracle's own trace)."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +10,8 @@ import oracle_lib
 from matchinglib_poselib_amd import synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
+sys.path.insert(0, GOLD)
+import make_golden  # noqa: E402  (inputs of the live check)
 
 
 def test_cv_rng_is_the_multiply_with_carry_generator(oracle):
@@ -34,16 +37,13 @@ def test_eigen_jacobi_svd_equals_the_vendored_eigen(oracle):
         assert np.array_equal(oracle.eigen_svd3(M)[2], oracle.eigen_svd3(-M)[2])
 
 
-def test_eigen_jacobi_svd_live_against_the_reference_build(oracle, tmp_path):
-    tool = oracle_lib.ref_tool("eigen_svd3")
-    if tool is None:
-        pytest.skip("oracle/_ref/eigen_svd3 is built only where /root/reference exists")
-    import struct
-    import subprocess
-    Ms = np.random.default_rng(5).standard_normal((300, 3, 3))
-    (tmp_path / "i.bin").write_bytes(struct.pack("i", len(Ms)) + Ms.tobytes())
-    subprocess.run([tool, str(tmp_path / "i.bin"), str(tmp_path / "o.bin")], check=True)
-    ref = np.fromfile(tmp_path / "o.bin").reshape(-1, 21)
+def test_eigen_jacobi_svd_live_against_the_reference_build(oracle):
+    """Eigen::JacobiSVD<Matrix3d> of the vendored Eigen on 300 random matrices: its output is recorded in tests/golden/ref_live.npz
+    (make_golden.py ref_live); where oracle/_ref/eigen_svd3 exists it runs again and must reproduce the recording."""
+    Ms = make_golden.live_svd_inputs()
+    ref = np.load(os.path.join(GOLD, "ref_live.npz"))["svd"]
+    if oracle_lib.ref_tool("eigen_svd3") is not None:
+        assert np.array_equal(make_golden.run_eigen_svd3(Ms), ref)
     for M, r in zip(Ms, ref):
         sv, U, V = oracle.eigen_svd3(M)
         assert np.abs(sv - r[:3]).max() < 1e-12 and np.abs(V - r[12:].reshape(3, 3)).max() < 1e-9

@@ -134,15 +134,17 @@ def test_stewenius_runs_that_part_do_so_at_a_named_place_and_end_alike(oracle):
 
 
 def test_live_against_the_reference_build(oracle):
+    """oracle/_ref/usac_ref on six random scenes (PROSAC on every other one): its traces are recorded in tests/golden/ref_live.npz
+    (make_golden.py ref_live); where the tool exists it runs again and must reproduce the recording."""
     import usac_ref_tool as u
-    if not u.available():
-        pytest.skip("oracle/_ref/usac_ref is built only where /root/reference exists")
-    rng = np.random.default_rng(77)
-    for trial in range(6):
-        n, frac, seed = int(rng.integers(60, 1500)), float(rng.uniform(0.35, 0.9)), int(rng.integers(1, 10 ** 6))
+    g = np.load(os.path.join(GOLD, "ref_live.npz"))
+    for trial, n, frac, seed in make_golden.live_usac_trials():
+        r = {k: g[f"usac{trial}_{k}"] for k in ("events", "final", "flags", "pool")}
+        if u.available():
+            live = make_golden.live_usac_run(trial, n, frac, seed)
+            assert all(np.array_equal(live[k], r[k]) for k in r), trial
         p1, p2, th, truth, order = make_golden.usac_scene(n, frac, seed)
         si = order if trial % 2 else None
-        r = u.run(p1, p2, th, 1000 + trial, sorted_idx=si, solver_oracle=True)
         o = oracle.usac_essential(p1, p2, th, 1000 + trial, sorted_idx=si, event_cap=200000)
         first, d = usac_compare.compare(r["events"], o["events"])
         if first is not None:   # only ever at a refit where ccmath stopped early

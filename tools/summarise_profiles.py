@@ -80,7 +80,7 @@ if os.path.exists(bp):
     PAIRS = int(json.load(open(bp)).get("config", {}).get("pairs_per_gpu", PAIRS))
 HEADLINE_GRID = str(4096 * PAIRS)  # 8 workgroups of 512 threads per image pair: one per 256 queries, ONE train split (round 5; with two splits 8192 * PAIRS)
 traffic = {"round": R, "pairs_per_launch": PAIRS,
-           "how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `bench.py --steps 20 --warmup 2 "
+           "how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `bench.py --full --steps 20 --warmup 2 "
                   f"--no-cpu-baseline` (dispatches of {PAIRS} image pairs per launch, grid {HEADLINE_GRID}); (2*FETCH_SIZE + WRITE_SIZE)*1024 B, FETCH_SIZE doubled per "
                   "MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B for 16-B/lane streams)"}
 for k, e in summary.items():

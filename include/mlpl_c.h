@@ -64,7 +64,8 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *   Hamming: "hamming_variant" 3 = fp4 matrix-core kernels (default; descriptors above 64 bytes fall back to 0), 0 = LDS-tiled VALU
  *     kernel, 1 = scalar-operand VALU kernel, 2 = one-wave-per-block VALU kernel; "hamming_mfma_lds" 1 (default) = LDS-ring kernel for
  *     32-byte descriptors, 0 = register-prefetch kernel, 2 = dynamic train splits; "hamming_mfma_weighted" (default 1) = age-aware split
- *     sizes; "hamming_mfma_prio" 0|1|2 (diagnostics) | 3 (wave-uniform skip of the running top-2 update: measured slower, round 6); "hamming_mfma_blocks_per_cu" and "hamming_mfma_qt" (query tiles per wave,
+ *     sizes; "hamming_mfma_prio" 0 | 1 (rotating wave priorities, diagnostics) | 3 (wave-uniform skip of the running top-2 update, 8-wave
+ *     workgroups only: measured slower, round 6); "hamming_mfma_blocks_per_cu" and "hamming_mfma_qt" (query tiles per wave,
  *     0 = automatic) size the matrix-core grid; "hamming_qpl" queries per lane 1|2 and "hamming_blocks_per_cu" size the VALU grids;
  *     "hamming_stamps" 1 = per-wave / per-workgroup clock stamps (mlpl_debug_hamming_stamps), 2 = one clock record per launch
  *       (mlpl_debug_hamming_clock).  "hamming_train01" 1 = {0, +1} instead of +-1 train fragments in the matrix-core Hamming kernel
@@ -73,7 +74,9 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *       assumes that the whole merge grid is resident, which other streams on the same device can break).
  *       "hamming_split_rows" 0 (default) | 8192 | 4096 = cap on the train rows one workgroup scans (4096 = rounds 1-4: every 8192-row train
  *       set was cut in two even with the chip full); "hamming_mfma_waves" 0 (automatic) | 4 | 8 | 16 waves per workgroup and
- *       "hamming_mfma_prefetch" 0 | 2 | 4 | 6 tiles of prefetch distance in the LDS-ring kernel.
+ *       "hamming_mfma_prefetch" 0 | 2 | 4 | 6 tiles of prefetch distance in the LDS-ring kernel.  They do not combine: waves 16 beats a
+ *       prefetch of 4 or 6, which beats "hamming_mfma_prio"; prefetch and prio 3 exist with 8-wave workgroups only and are ignored elsewhere.
+ *       "hamming_expand_fine" (default 1) = small launches expand the train set with one thread per (tile, K-step, lane).
  *   L2: "l2_mfma_waves" 0|4|8 and "l2_mfma_blocks_per_cu" shape the int8 matrix-core kernel of the forced mode (see mlpl_set_l2_path);
  *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0).
  *   RANSAC: "ransac_device_draw" (default 1) = large passes draw their samples on the device (mlpl_debug_ransac_draw); "ransac_chunk" hypotheses per device pass (0 = 32768 = the maximum; the sequential best/niters rule is replayed across
@@ -96,7 +99,9 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *     Hamming: "hamming_fused_merge" (default 1) = the LDS-ring kernel folds its train splits, evaluates the ratio predicate and counts
  *     itself, 0 = separate merge launch; RANSAC: "ransac_count_mpl" 1|2 models per lane of the counting kernel (A/B, default 2);
  *     "ransac_count_threads" 256 (default since round 6: 4-wave workgroups at 96 VGPRs, five per CU) | 512; "ransac_count_tiles" 2 (default) | 1
- *     tiles of 512 correspondences per counting workgroup.
+ *     tiles of 512 correspondences per counting workgroup; "ransac_count_wpe" 5 (default) | 6 waves per SIMD the 256-thread counting
+ *     kernel's registers are cut for; "ransac_count_defer" (default 1) = the counting kernel decides its undecided evaluations in a
+ *     workgroup-wide queue after its loop, 0 = on the spot (same counts).
  *   "solver_polish" (default 1) = every 5-point solution is finished by <= 4 Gauss-Newton steps on the ten cubic constraints (a step is
  *     kept only while the residual falls).  It is the accuracy safeguard of THIS solver, not a departure from the reference: the device's
  *     elimination (like the CPU code's, five-point.cpp:366-471, but on other samples) is ill conditioned on ~0.4 % of minimal samples and its
@@ -106,8 +111,7 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *     oracle fail (USAC decisions part).  RANSAC runs: identical to the CPU path on 126 of 126 seeds either way.  0 = the plain elimination +
  *     root path, kept for A/B (mlpl_set_option(ctx, "solver_polish", 0) or MLPL_OPTIONS=solver_polish=0). */
 int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value);
-/* The current value of a tuning knob (the names mlpl_set_option takes; a subset: the Hamming knobs, "solver_polish", "ransac_count_mpl",
- * "hub_workers", "hub_lanes").  Returns 0, MLPL_E_BAD_INPUT for a name it does not know. */
+/* The current value of a tuning knob: every name mlpl_set_option takes.  Returns 0, MLPL_E_BAD_INPUT for a name it does not know. */
 int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value);
 
 /* ---- in-library kernel timing (for roofline accounting) ------------------------------------------------------

@@ -73,6 +73,33 @@ int mlpl_debug_hamming_clock(mlpl_ctx *ctx, unsigned long long *out, int max_ite
  * of entries written (<= max_items). */
 int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, long long *ws_grows);
 
+/* Diagnostics: the kernel instances the last launches chose (tests check that an option reached the instance it names).  Writes 12 ints
+ * and returns 12:
+ *   out[0]  instance of the last inlier-count pass (RANSAC pass, pair batch, mlpl_count_models, mlpl_debug_count_pass; 0 = none yet):
+ *           1 score_models_block_kernel<count> (one workgroup per model), 2 score_models_kernel<fp64, 512 threads>,
+ *           3 score_models_kernel<fp64, 128 threads, 256-point tiles> (passes of <= 24576 models), 4 count_models_f32_kernel<128, 256>
+ *           (the same passes, packed-fp32 filter), 5 count_models_f32_kernel<512, 512> (one model per lane), 6 <512, 512, 2 models per
+ *           lane>, 7 <512, 512, 2, deferred queue>, 8 <256, 512, 2, deferred, 96 VGPRs> (default), 9 <256, 512, 2, deferred, 80 VGPRs>
+ *           (ransac_count_wpe 6), 10 / 11 the block / 4-lane kernels with error sums;
+ *   out[1]  its workgroups per model group (point splits; 0 for the block kernel);
+ *   out[2]  Hamming kernel of the last knn_hamming call: 0 / 1 / 2 VALU kernel of hamming_variant 0 / 1 / 2, 3 register-prefetch
+ *           matrix-core kernel, 4 static LDS-ring kernel, 5 dynamic-split LDS-ring kernel;
+ *   out[3]  query tiles per wave (matrix-core) or queries per lane (VALU);  out[4] PRIO of the static ring kernel (0, 1, 3);
+ *   out[5]  waves per workgroup of the static ring kernel (4, 8, 16; 4 for the other matrix-core kernels, 0 VALU);
+ *   out[6]  its prefetch distance in tiles (2, 4, 6; 0 otherwise);  out[7] 1 = the kernel merged its splits itself (no merge launch);
+ *   out[8]  1 = the age-aware split table was used;  out[9] 1 = the train set was expanded one thread per (tile, K-step, lane);
+ *   out[10] train splits;  out[11] 64-bit K-steps of the matrix-core kernels (0 VALU). */
+int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[12]);
+
+/* Tests: one count-only scoring pass exactly as a RANSAC pass runs it.  The correspondences are packed as for RANSAC; E holds n_live
+ * models (9 doubles each), padded on the device to n_bound rows with NaN models; the live count n_live is read on the device; the count
+ * of live model m goes to table_inout[ids ? ids[m] : m] (table_len ints, uploaded as given and read back: slots no id names keep their
+ * contents).  point_splits: -1 = what a RANSAC pass of n_bound models would take, 0 = one workgroup per model (stores), 1 = one workgroup
+ * per model group (stores), > 1 = that many workgroups per model group, which ADD to the table.  The instance follows the context's
+ * ransac_count_* / ransac_f32_filter options (mlpl_debug_last_kernels reports it). */
+int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_live, int n_bound,
+                          const int32_t *ids, int table_len, double thresh2, int point_splits, int32_t *table_inout);
+
 #ifdef __cplusplus
 }
 #endif

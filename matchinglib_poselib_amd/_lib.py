@@ -121,6 +121,9 @@ _SIGNATURES = {
     "mlpl_debug_hamming_stamps": (c_int, [c_void_p, c_void_p, c_int]),
     "mlpl_debug_hamming_clock": (c_int, [c_void_p, c_void_p, c_int]),
     "mlpl_debug_hop_trace": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "mlpl_debug_last_kernels": (c_int, [c_void_p, c_void_p]),
+    "mlpl_debug_count_pass": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_int,
+                                      c_void_p]),
     "mlpl_pair_pose_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                    c_int, c_double, c_int, c_u32, c_double, c_void_p, c_void_p]),
     "mlpl_pair_pose_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
@@ -236,6 +239,14 @@ class Context:
         v = C.c_int(0)
         check(self._lib.mlpl_get_option(self._h, name.encode(), C.byref(v)), "mlpl_get_option")
         return v.value
+
+    def last_kernels(self) -> list:
+        """mlpl_debug_last_kernels (include/mlpl_debug.h): the counting and Hamming kernel instances the last launches chose."""
+        out = (C.c_int * 12)()
+        n = self._lib.mlpl_debug_last_kernels(self._h, out)
+        if n < 0:
+            raise MlplError(n, "mlpl_debug_last_kernels", last_error())
+        return list(out[:n])
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

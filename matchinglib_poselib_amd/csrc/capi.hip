@@ -218,7 +218,7 @@ int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
     else if (!std::strcmp(name, "hamming_mfma_blocks_per_cu") && value >= 1 && value <= 64) ctx->opt_hamming_mfma_blocks_per_cu = value;
     else if (!std::strcmp(name, "hamming_mfma_lds") && (value >= 0 && value <= 2)) ctx->opt_hamming_mfma_lds = value;
     else if (!std::strcmp(name, "hamming_expand_fine") && (value == 0 || value == 1)) ctx->opt_hamming_expand_fine = value;
-    else if (!std::strcmp(name, "hamming_mfma_prio") && (value >= 0 && value <= 3)) ctx->opt_hamming_mfma_prio = value;
+    else if (!std::strcmp(name, "hamming_mfma_prio") && (value == 0 || value == 1 || value == 3)) ctx->opt_hamming_mfma_prio = value;
     else if (!std::strcmp(name, "hamming_mfma_prefetch") && (value == 0 || value == 2 || value == 4 || value == 6)) ctx->opt_hamming_mfma_prefetch = value;
     else if (!std::strcmp(name, "hamming_split_rows") && (value == 0 || value == 4096 || value == 8192)) ctx->opt_hamming_split_rows = value;
     else if (!std::strcmp(name, "hamming_mfma_waves") && (value == 0 || value == 4 || value == 8 || value == 16)) ctx->opt_hamming_mfma_waves = value;
@@ -273,27 +273,70 @@ int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
 
 int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value) {
     if (!ctx || !name || !value) return MLPL_E_BAD_INPUT;
+    // every name mlpl_set_option accepts, in its order
     if (!std::strcmp(name, "hamming_variant")) *value = ctx->opt_hamming_variant;
     else if (!std::strcmp(name, "hamming_mfma_qt")) *value = ctx->opt_hamming_mfma_qt;
+    else if (!std::strcmp(name, "hamming_mfma_blocks_per_cu")) *value = ctx->opt_hamming_mfma_blocks_per_cu;
     else if (!std::strcmp(name, "hamming_mfma_lds")) *value = ctx->opt_hamming_mfma_lds;
-    else if (!std::strcmp(name, "hamming_fused_merge")) *value = ctx->opt_hamming_fused_merge;
-    else if (!std::strcmp(name, "hamming_train01")) *value = ctx->opt_hamming_train01;
-    else if (!std::strcmp(name, "hamming_merge_emit")) *value = ctx->opt_hamming_merge_emit;
-    else if (!std::strcmp(name, "hamming_stamps")) *value = ctx->opt_hamming_stamps;
+    else if (!std::strcmp(name, "hamming_expand_fine")) *value = ctx->opt_hamming_expand_fine;
+    else if (!std::strcmp(name, "hamming_mfma_prio")) *value = ctx->opt_hamming_mfma_prio;
+    else if (!std::strcmp(name, "hamming_mfma_prefetch")) *value = ctx->opt_hamming_mfma_prefetch;
     else if (!std::strcmp(name, "hamming_split_rows")) *value = ctx->opt_hamming_split_rows;
     else if (!std::strcmp(name, "hamming_mfma_waves")) *value = ctx->opt_hamming_mfma_waves;
-    else if (!std::strcmp(name, "solver_polish")) *value = ctx->opt_solver_polish;
+    else if (!std::strcmp(name, "hamming_mfma_weighted")) *value = ctx->opt_hamming_mfma_weighted;
+    else if (!std::strcmp(name, "hamming_fused_merge")) *value = ctx->opt_hamming_fused_merge;
+    else if (!std::strcmp(name, "hamming_stamps")) *value = ctx->opt_hamming_stamps;
+    else if (!std::strcmp(name, "hamming_train01")) *value = ctx->opt_hamming_train01;
+    else if (!std::strcmp(name, "hamming_merge_emit")) *value = ctx->opt_hamming_merge_emit;
+    else if (!std::strcmp(name, "l2_mfma_waves")) *value = ctx->opt_l2_mfma_waves;
+    else if (!std::strcmp(name, "l2_mfma_blocks_per_cu")) *value = ctx->opt_l2_mfma_blocks_per_cu;
+    else if (!std::strcmp(name, "hamming_qpl")) *value = ctx->opt_hamming_qpl;
+    else if (!std::strcmp(name, "hamming_blocks_per_cu")) *value = ctx->opt_hamming_blocks_per_cu;
+    else if (!std::strcmp(name, "ransac_lazy_sums")) *value = ctx->opt_ransac_lazy_sums;
+    else if (!std::strcmp(name, "ransac_overlap")) *value = ctx->opt_ransac_overlap;
+    else if (!std::strcmp(name, "ransac_dev_split")) *value = ctx->opt_ransac_dev_split;
+    else if (!std::strcmp(name, "rand_cache_max")) *value = ctx->opt_rand_cache_max;
+    else if (!std::strcmp(name, "ransac_f32_filter")) *value = ctx->opt_ransac_f32_filter;
+    else if (!std::strcmp(name, "arrsac_refine_warm_start")) *value = ctx->opt_arrsac_refine_warm_start;
     else if (!std::strcmp(name, "ransac_count_mpl")) *value = ctx->opt_ransac_count_mpl;
-    else if (!std::strcmp(name, "ransac_count_threads")) *value = ctx->opt_ransac_count_threads;
     else if (!std::strcmp(name, "ransac_count_tiles")) *value = ctx->opt_ransac_count_tiles;
+    else if (!std::strcmp(name, "ransac_count_threads")) *value = ctx->opt_ransac_count_threads;
+    else if (!std::strcmp(name, "ransac_count_wpe")) *value = ctx->opt_ransac_count_wpe;
     else if (!std::strcmp(name, "ransac_count_defer")) *value = ctx->opt_ransac_count_defer;
-    else if (!std::strcmp(name, "hub_workers")) *value = ctx->opt_hub_workers;
+    else if (!std::strcmp(name, "ransac_event_cap")) *value = ctx->opt_ransac_event_cap;
+    else if (!std::strcmp(name, "solver_polish")) *value = ctx->opt_solver_polish;
+    else if (!std::strcmp(name, "solver_wave3")) *value = ctx->opt_solver_wave3;
+    else if (!std::strcmp(name, "ransac_device_draw")) *value = ctx->opt_ransac_device_draw;
+    else if (!std::strcmp(name, "l2_float_mfma")) *value = ctx->opt_l2_float_mfma;
+    else if (!std::strcmp(name, "arrsac_flag_points")) *value = ctx->opt_arrsac_flag_points;
+    else if (!std::strcmp(name, "pair_batch")) *value = ctx->opt_pair_batch;
     else if (!std::strcmp(name, "hub_lanes")) *value = ctx->opt_hub_lanes;
+    else if (!std::strcmp(name, "eig_inverse_iteration")) *value = ctx->opt_eig_inverse_iteration;
+    else if (!std::strcmp(name, "hub_blocking_sync")) *value = ctx->opt_hub_blocking_sync;
+    else if (!std::strcmp(name, "hub_workers")) *value = ctx->opt_hub_workers;
+    else if (!std::strcmp(name, "hub_cohort")) *value = ctx->opt_hub_cohort;
+    else if (!std::strcmp(name, "pair_batch_seq")) *value = ctx->opt_pair_batch_seq;
+    else if (!std::strcmp(name, "pair_batch_feed")) *value = ctx->opt_pair_batch_feed;
+    else if (!std::strcmp(name, "pair_batch_raw_cap")) *value = ctx->opt_pair_batch_raw_cap;
+    else if (!std::strcmp(name, "usac_lo_stepwise")) *value = ctx->opt_usac_lo_stepwise;
+    else if (!std::strcmp(name, "usac_lo_warm_start")) *value = ctx->opt_usac_lo_warm_start;
+    else if (!std::strcmp(name, "usac_first_batch")) *value = ctx->opt_usac_first_batch;
+    else if (!std::strcmp(name, "usac_lo5_fused_fit")) *value = ctx->opt_usac_lo5_fused_fit;
+    else if (!std::strcmp(name, "usac_sprt_fast")) *value = ctx->opt_usac_sprt_fast;
+    else if (!std::strcmp(name, "ransac_host_table")) *value = ctx->opt_ransac_host_table;
+    else if (!std::strcmp(name, "ransac_chunk")) *value = ctx->opt_ransac_chunk;
     else {
         set_error("mlpl_get_option: unknown option: %s", name);
         return MLPL_E_BAD_INPUT;
     }
     return MLPL_OK;
+}
+
+int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[12]) {
+    if (!ctx || !out) return MLPL_E_BAD_INPUT;
+    out[0] = ctx->dbg_count_kernel[0], out[1] = ctx->dbg_count_kernel[1];
+    for (int i = 0; i < 10; ++i) out[2 + i] = ctx->dbg_hamming_kernel[i];
+    return 12;
 }
 
 int mlpl_debug_hamming_stamps(mlpl_ctx *ctx, unsigned long long *out, int max_items) {

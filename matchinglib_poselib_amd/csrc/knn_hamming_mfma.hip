@@ -399,7 +399,6 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
 
     // my piece (K-step w) of the split's first tile; a tile is KS * 64 uint4 = 4 KiB, contiguous
     const uint4 *tbase = tfrag + (size_t)b * t_batch_u4 + (size_t)tile0 * KS * 64 + (size_t)w * 64;  // wave-uniform
-    if (PRIO == 2) tbase = tfrag + (size_t)w * 64;  // diagnostics: every workgroup streams the SAME tiles (wrong results, L1/L2-hot source)
     auto copy_tile = [&](int t_rel) {
         if (NW > KS && w >= KS) return;  // (wave-uniform: the K-steps are copied by the first KS waves)
         __builtin_amdgcn_global_load_lds((const void *)(tbase + (size_t)t_rel * KS * 64 + l),
@@ -981,7 +980,8 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     const ExpandArgs qa = expand_q ? ExpandArgs{qw, q_batch_words, nq, q_tiles_padded, (uint4 *)qf} : ta;  // blockIdx.z == 0
     const dim3 egrid((unsigned)(((expand_q ? std::max(q_tiles_padded, t_tiles) : t_tiles) * 64 + 255) / 256), batch, expand_q ? 2 : 1);
     // (one thread per K-step when the launch is small: the single-pair latency shape)
-    if (!expand_q && ks == 4 && nw == 8 && !counters && (long long)t_tiles * batch <= 4LL * ctx->num_cus && ctx->opt_hamming_expand_fine) {
+    const bool expand_fine = !expand_q && ks == 4 && nw == 8 && !counters && (long long)t_tiles * batch <= 4LL * ctx->num_cus && ctx->opt_hamming_expand_fine;
+    if (expand_fine) {
         hipLaunchKernelGGL(hamming_expand_fine_kernel, dim3((unsigned)t_tiles, batch), dim3(256), 0, s, ta, train01);
     } else
     switch (ks) {
@@ -1086,6 +1086,17 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
         }
         *fused_out = 1;
     }
+    // Instance of the static LDS-ring kernel.  Precedence (the options do not combine): waves 16 (qt 4 only; the plain <4, 0, 16>) beats a
+    // prefetch distance of 4 or 6, which beats prio; prefetch and prio 3 exist at qt 4 with 8 waves only, prio 1 at every shape.  An option
+    // the shape has no instance for is ignored: prefetch with 4 waves, prio 3 below 8 waves (prio 0 is run).
+    const int pd = (nwv == 8 && (ctx->opt_hamming_mfma_prefetch == 4 || ctx->opt_hamming_mfma_prefetch == 6)) ? ctx->opt_hamming_mfma_prefetch : 2;
+    const int prio = (nwv == 16 || pd != 2) ? 0 : ctx->opt_hamming_mfma_prio == 1 ? 1 : (ctx->opt_hamming_mfma_prio == 3 && nwv == 8) ? 3 : 0;
+    {
+        int *rec = ctx->dbg_hamming_kernel;
+        rec[0] = dyn ? 5 : lds_ring ? 4 : 3, rec[1] = (dyn || !lds_ring) ? (ks <= 4 && qt == 4 ? 4 : qt >= 2 ? 2 : 1) : qt;
+        rec[2] = (lds_ring && !dyn) ? prio : 0, rec[3] = lds_ring && !dyn ? nwv : 4, rec[4] = lds_ring && !dyn ? pd : 0;
+        rec[5] = *fused_out, rec[6] = split_tab != nullptr, rec[7] = expand_fine, rec[8] = nsplit, rec[9] = ks;
+    }
     prof_mark(ctx, MLPL_PROF_KNN_HAMMING, 0, s);
     if (dyn) {
 #define MLPL_DYN_LAUNCH(QT_)                                                                                                          \
@@ -1098,32 +1109,29 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     } else if (lds_ring) {
 #define MLPL_RING_LAUNCH(QT_)                                                                                                          \
     do {                                                                                                                               \
-        if (ctx->opt_hamming_mfma_prio == 2)                                                                                           \
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 2>), grid, dim3(256), 0, s, qw, q_batch_words, (const uint4 *)tf, \
-                               t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
-        else if (ctx->opt_hamming_mfma_prio)                                                                                           \
+        if (prio == 1)                                                                                                                 \
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 1>), grid, dim3(256), 0, s, qw, q_batch_words, (const uint4 *)tf, \
                                t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
         else                                                                                                                           \
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 0>), grid, dim3(256), 0, s, qw, q_batch_words, (const uint4 *)tf, \
                                t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
     } while (0)
-        if (qt == 4 && nwv == 16)
+        if (nwv == 16)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 16>), grid, dim3(1024), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (qt == 4 && nwv == 8 && ctx->opt_hamming_mfma_prefetch == 4)
+        else if (nwv == 8 && pd == 4)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 4>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (qt == 4 && nwv == 8 && ctx->opt_hamming_mfma_prefetch == 6)
+        else if (nwv == 8 && pd == 6)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 6>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (qt == 4 && nwv == 8 && ctx->opt_hamming_mfma_prio == 3)
+        else if (nwv == 8 && prio == 3)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 3, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (qt == 4 && nwv == 8 && ctx->opt_hamming_mfma_prio == 1)
+        else if (nwv == 8 && prio == 1)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 1, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (qt == 4 && nwv == 8)
+        else if (nwv == 8)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (qt == 4) MLPL_RING_LAUNCH(4);

@@ -111,7 +111,7 @@ struct mlpl_ctx {
     int opt_hamming_mfma_waves;     // waves per workgroup of the static LDS-ring kernel: 0 (default) = automatic (8 with four query tiles per wave, else 4), 4, 8
     int opt_hamming_split_rows;     // cap on the train rows of one split: 0 (default) = 8192, the exactness bound of the row fraction; 4096 = the cap up to round 4
     int opt_hamming_mfma_prefetch;  // prefetch distance of the ring in tiles with 8-wave workgroups: 0 / 2 (default), 4, 6
-    int opt_hamming_mfma_prio;      // 1 = the LDS-ring kernel rotates wave priorities on a clock slice (equal finish times per SIMD; measured: no faster). Default 0
+    int opt_hamming_mfma_prio;      // 1 = the LDS-ring kernel rotates wave priorities on a clock slice (equal finish times per SIMD; measured: no faster); 3 = the wave-uniform top-2 skip (<4, 3, 8> only; measured: no faster). Default 0
     int opt_hamming_mfma_weighted;  // 1 (default) = age-aware split sizes in the static LDS-ring kernel (4 workgroups per CU)
     long long split_tab_key;        // shape key of the split table currently in WS_COUNTERS
     void *split_tab_ptr;
@@ -127,6 +127,10 @@ struct mlpl_ctx {
     uint32_t hamming_scan_gen;
     int opt_hamming_train01;        // 1 = {0, +1} train fragments in the static LDS-ring kernel (accumulator = pop(query) - distance), 0 = +-1
     int dbg_stamp_items;
+    // diagnostics (mlpl_debug_last_kernels): what the last launches chose -- {count instance code, its point splits} of the last
+    // inlier-count pass, and the Hamming instance of the last knn_hamming call (layout: include/mlpl_debug.h)
+    int dbg_count_kernel[2];
+    int dbg_hamming_kernel[10];
     int opt_ransac_chunk;           // hypotheses per device pass (0 = 32768)
     int opt_ransac_event_cap;       // tests: capacity of the record-event list of candidate / replay kernels (0 = 1024); forces their serial fallback
     int opt_ransac_count_mpl;       // models per lane of the packed-fp32 counting kernel: 2 (default) or 1

@@ -3154,54 +3154,116 @@ double inlier_bound(double thresh2) {
 
 // Launchers used by the C ABI ------------------------------------------------------------------------------------
 
+// ---- instances of the count-only scoring pass -------------------------------------------------------------------------------------------
+// ONE selection for every caller (launch_score's passes, mlpl_count_models(shape = 1), the pair batch): the options pick among the compiled
+// instances here and nowhere else.  The codes are what mlpl_debug_last_kernels reports (include/mlpl_debug.h lists them).
+enum CountKernel {
+    kCountNone = 0,
+    kCountBlock = 1,          // score_models_block_kernel<true, false>: one workgroup per model, stores (launch_score(point_splits = 0))
+    kCountF64 = 2,            // score_models_kernel<false, 512>: fp64 predicate, 128 models per workgroup
+    kCountF64Small = 3,       // score_models_kernel<false, 128, 256>: passes of <= kScoreBlockMaxModels models, 32 per workgroup
+    kCountF32Small = 4,       // count_models_f32_kernel<128, 256>
+    kCountF32 = 5,            // count_models_f32_kernel<512, 512>: one model per lane
+    kCountF32Mpl2 = 6,        // count_models_f32_kernel<512, 512, 2>
+    kCountF32Mpl2Defer = 7,   // count_models_f32_kernel<512, 512, 2, true>
+    kCountF32W256 = 8,        // count_models_f32_kernel<256, 512, 2, true>: 96 VGPRs, five workgroups per CU (default)
+    kCountF32W256Wpe6 = 9,    // count_models_f32_kernel<256, 512, 2, true, 6>: 80 VGPRs, six per CU
+    kCountSumsBlock = 10,     // score_models_block_kernel<true, true> (counts and error sums)
+    kCountSums = 11,          // score_models_kernel<true> (counts and error sums)
+};
+
+// small = a pass of <= kScoreBlockMaxModels models (one 256-point tile per workgroup); n = the largest point count of the pass (the
+// deferred queue entry holds 23 bits of correspondence index, so the DEFER instances need n < 2^23).  `wpe` only matters at 256 threads.
+static int count_kernel_choice(bool small, bool f32_filter, int mpl, bool defer, int n, int threads, int wpe) {
+    if (small) return f32_filter ? kCountF32Small : kCountF64Small;
+    if (!f32_filter) return kCountF64;
+    if (mpl == 2 && defer && n < (1 << 23)) {
+        if (threads == 256) return wpe == 6 ? kCountF32W256Wpe6 : kCountF32W256;
+        return kCountF32Mpl2Defer;
+    }
+    return mpl == 2 ? kCountF32Mpl2 : kCountF32;
+}
+
+// models one workgroup of the instance covers
+static int count_kernel_models_per_wg(int code) {
+    switch (code) {
+        case kCountF64Small: case kCountF32Small: return kScoreThreadsSmall / 4;
+        case kCountF32Mpl2: case kCountF32Mpl2Defer: return 2 * kScoreModels;
+        case kCountF32W256: case kCountF32W256Wpe6: return 128;
+        default: return kScoreModels;
+    }
+}
+
+// Launches instance `code` (kCountF64 ... kCountF32W256Wpe6) over max_models models x point_splits workgroups per model group x nslots pair
+// slots (ps != nullptr: the batched pass, packed fp32 instances only).  point_splits > 1 ADDS to the table, 1 stores.
+static void launch_count_kernel(int code, hipStream_t s, int max_models, int point_splits, int nslots, const double4 *pts, int n,
+                                const double *E_list, const int32_t *ids, const int32_t *total_ptr, int total_host, double thresh2,
+                                double qmax, int32_t *good, const PairSlot *ps = nullptr, int slot_stride = 0) {
+    const int per_wg = count_kernel_models_per_wg(code);
+    const dim3 grid((max_models + per_wg - 1) / per_wg, point_splits, nslots);
+    switch (code) {
+        case kCountF64Small:
+            hipLaunchKernelGGL((score_models_kernel<false, kScoreThreadsSmall, kScoreTileSmall>), grid, dim3(kScoreThreadsSmall), 0, s, pts, n,
+                               E_list, ids, total_ptr, total_host, thresh2, qmax, good, (double *)nullptr);
+            break;
+        case kCountF32Small:
+            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreadsSmall, kScoreTileSmall>), grid, dim3(kScoreThreadsSmall), 0, s, pts, n,
+                               E_list, ids, total_ptr, total_host, thresh2, qmax, good, ps, slot_stride);
+            break;
+        case kCountF32:
+            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile>), grid, dim3(kScoreThreads), 0, s, pts, n, E_list, ids,
+                               total_ptr, total_host, thresh2, qmax, good, ps, slot_stride);
+            break;
+        case kCountF32Mpl2:
+            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile, 2>), grid, dim3(kScoreThreads), 0, s, pts, n, E_list, ids,
+                               total_ptr, total_host, thresh2, qmax, good, ps, slot_stride);
+            break;
+        case kCountF32Mpl2Defer:
+            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile, 2, true>), grid, dim3(kScoreThreads), 0, s, pts, n, E_list,
+                               ids, total_ptr, total_host, thresh2, qmax, good, ps, slot_stride);
+            break;
+        case kCountF32W256:   // round 6: 4-wave workgroups at 96 VGPRs, five per CU
+            hipLaunchKernelGGL((count_models_f32_kernel<256, kScoreTile, 2, true>), grid, dim3(256), 0, s, pts, n, E_list, ids, total_ptr,
+                               total_host, thresh2, qmax, good, ps, slot_stride);
+            break;
+        case kCountF32W256Wpe6:   // A/B: 80 VGPRs, six 4-wave workgroups per CU
+            hipLaunchKernelGGL((count_models_f32_kernel<256, kScoreTile, 2, true, 6>), grid, dim3(256), 0, s, pts, n, E_list, ids, total_ptr,
+                               total_host, thresh2, qmax, good, ps, slot_stride);
+            break;
+        default:   // kCountF64 (no batched form: the pair batch never selects it)
+            hipLaunchKernelGGL((score_models_kernel<false, kScoreThreads>), grid, dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr,
+                               total_host, thresh2, qmax, good, (double *)nullptr);
+            break;
+    }
+}
+
 // Sampson scoring of up to `max_models` models (dense list, live count on the device or the host): few models -> one block per
-// model, many -> 4 lanes per model (see the two kernels).  Identical results either way.
+// model, many -> 4 lanes per model (see the two kernels).  Identical results either way.  Returns the CountKernel code launched.
 constexpr int kScoreBlockMaxModels = 24576;
-static void launch_score(hipStream_t s, const double4 *pts, int n, const double *E_list, const int32_t *ids, const int32_t *total_ptr,
-                         int total_host, int max_models, double thresh2, int32_t *good, double *esum, bool sums = true,
-                         double qmax = -1.0, int point_splits = 1, bool f32_filter = false, int mpl = 1, bool defer = false, int count_threads = 512, int count_wpe = 5) {
-    if (max_models <= 0) return;
+static int launch_score(hipStream_t s, const double4 *pts, int n, const double *E_list, const int32_t *ids, const int32_t *total_ptr,
+                        int total_host, int max_models, double thresh2, int32_t *good, double *esum, bool sums = true,
+                        double qmax = -1.0, int point_splits = 1, bool f32_filter = false, int mpl = 1, bool defer = false, int count_threads = 512, int count_wpe = 5) {
+    if (max_models <= 0) return kCountNone;
     const size_t lds = (size_t)((n + 3) / 4 * 4) * sizeof(float);
     const bool block = n <= kScoreBlockMaxN && max_models <= kScoreBlockMaxModels;
     if (sums) {
-        if (block)
+        if (block) {
             hipLaunchKernelGGL((score_models_block_kernel<true, true>), dim3(max_models), dim3(256), lds, s, pts, n, E_list, ids, total_ptr,
                                total_host, thresh2, qmax, good, esum, (const int32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(score_models_kernel<true>, dim3((max_models + kScoreModels - 1) / kScoreModels), dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr,
-                               total_host, thresh2, qmax, good, esum);
-    } else if (point_splits == 0) {  // one workgroup per model, no accumulation: callers that do not zero the table
+            return kCountSumsBlock;
+        }
+        hipLaunchKernelGGL(score_models_kernel<true>, dim3((max_models + kScoreModels - 1) / kScoreModels), dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr,
+                           total_host, thresh2, qmax, good, esum);
+        return kCountSums;
+    }
+    if (point_splits == 0) {  // one workgroup per model, no accumulation: callers that do not zero the table
         hipLaunchKernelGGL((score_models_block_kernel<true, false>), dim3(max_models), dim3(256), 0, s, pts, n, E_list, ids, total_ptr,
                            total_host, thresh2, qmax, good, esum, (const int32_t *)nullptr);
-    } else if (max_models <= kScoreBlockMaxModels) {
-        const dim3 grid((max_models + kScoreThreadsSmall / 4 - 1) / (kScoreThreadsSmall / 4), point_splits);
-        if (f32_filter)
-            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreadsSmall, kScoreTileSmall>), grid, dim3(kScoreThreadsSmall), 0, s, pts, n, E_list, ids,
-                               total_ptr, total_host, thresh2, qmax, good);
-        else
-            hipLaunchKernelGGL((score_models_kernel<false, kScoreThreadsSmall, kScoreTileSmall>), grid, dim3(kScoreThreadsSmall), 0, s, pts, n, E_list,
-                               ids, total_ptr, total_host, thresh2, qmax, good, esum);
-    } else {
-        const dim3 grid((max_models + kScoreModels - 1) / kScoreModels, point_splits);
-        if (f32_filter && mpl == 2 && defer && n < (1 << 23) && count_threads == 256 && count_wpe == 6)   // A/B: 80 VGPRs, six 4-wave workgroups per CU
-            hipLaunchKernelGGL((count_models_f32_kernel<256, kScoreTile, 2, true, 6>), dim3((max_models + 127) / 128, point_splits),
-                               dim3(256), 0, s, pts, n, E_list, ids, total_ptr, total_host, thresh2, qmax, good);
-        else if (f32_filter && mpl == 2 && defer && n < (1 << 23) && count_threads == 256)   // round 6: 4-wave workgroups at 96 VGPRs, five per CU
-            hipLaunchKernelGGL((count_models_f32_kernel<256, kScoreTile, 2, true>), dim3((max_models + 127) / 128, point_splits),
-                               dim3(256), 0, s, pts, n, E_list, ids, total_ptr, total_host, thresh2, qmax, good);
-        else if (f32_filter && mpl == 2 && defer && n < (1 << 23))
-            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile, 2, true>), dim3((max_models + 2 * kScoreModels - 1) / (2 * kScoreModels), point_splits),
-                               dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr, total_host, thresh2, qmax, good);
-        else if (f32_filter && mpl == 2)
-            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile, 2>), dim3((max_models + 2 * kScoreModels - 1) / (2 * kScoreModels), point_splits),
-                               dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr, total_host, thresh2, qmax, good);
-        else if (f32_filter)
-            hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile>), grid, dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr,
-                               total_host, thresh2, qmax, good);
-        else
-            hipLaunchKernelGGL((score_models_kernel<false, kScoreThreads>), grid, dim3(kScoreThreads), 0, s, pts, n, E_list, ids, total_ptr,
-                               total_host, thresh2, qmax, good, esum);
+        return kCountBlock;
     }
+    const int code = count_kernel_choice(max_models <= kScoreBlockMaxModels, f32_filter, mpl, defer, n, count_threads, count_wpe);
+    launch_count_kernel(code, s, max_models, point_splits, 1, pts, n, E_list, ids, total_ptr, total_host, thresh2, qmax, good);
+    return code;
 }
 
 // Workgroups per model group of the count-only scoring pass (see score_models_kernel); with more than one the counts are ACCUMULATED
@@ -3452,34 +3514,22 @@ static int score_models_impl(mlpl_ctx *ctx, const double *p1, const double *p2, 
     if ((rc = pack_points(ctx, (const double *)dp1, (const double *)dp2, n, &pts, s))) return rc;
     prof_mark(ctx, MLPL_PROF_SCORE, 0, s);
     const double qmax = inlier_bound(thresh2);
-    if (shape == 1 && !err_sum && ctx->opt_ransac_f32_filter && ctx->opt_ransac_count_mpl == 2 && ctx->opt_ransac_count_defer && n < (1 << 23) &&
-        ctx->opt_ransac_count_threads == 256)
-        hipLaunchKernelGGL((count_models_f32_kernel<256, kScoreTile, 2, true>), dim3((n_models + 127) / 128), dim3(256), 0, s,
-                           (const double4 *)pts, n, (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, thresh2, qmax,
-                           (int32_t *)dgood);
-    else if (shape == 1 && !err_sum && ctx->opt_ransac_f32_filter && ctx->opt_ransac_count_mpl == 2 && ctx->opt_ransac_count_defer && n < (1 << 23))
-        hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile, 2, true>), dim3((n_models + 2 * kScoreModels - 1) / (2 * kScoreModels)), dim3(kScoreThreads), 0, s,
-                           (const double4 *)pts, n, (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, thresh2, qmax,
-                           (int32_t *)dgood);
-    else if (shape == 1 && !err_sum && ctx->opt_ransac_f32_filter && ctx->opt_ransac_count_mpl == 2)
-        hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile, 2>), dim3((n_models + 2 * kScoreModels - 1) / (2 * kScoreModels)), dim3(kScoreThreads), 0, s,
-                           (const double4 *)pts, n, (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, thresh2, qmax,
-                           (int32_t *)dgood);
-    else if (shape == 1 && !err_sum && ctx->opt_ransac_f32_filter)
-        hipLaunchKernelGGL((count_models_f32_kernel<kScoreThreads, kScoreTile>), dim3((n_models + kScoreModels - 1) / kScoreModels), dim3(kScoreThreads), 0, s,
-                           (const double4 *)pts, n, (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, thresh2, qmax,
-                           (int32_t *)dgood);
-    else if (shape == 1 && !err_sum)
-        hipLaunchKernelGGL(score_models_kernel<false>, dim3((n_models + kScoreModels - 1) / kScoreModels), dim3(kScoreThreads), 0, s, (const double4 *)pts, n,
-                           (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, thresh2, qmax,
-                           (int32_t *)dgood, (double *)dsum);
-    else if (shape == 2 && !err_sum)
+    if (shape == 1 && !err_sum) {   // the large-pass instance the options select, one workgroup per model group (stores)
+        const int code = count_kernel_choice(false, ctx->opt_ransac_f32_filter != 0, ctx->opt_ransac_count_mpl, ctx->opt_ransac_count_defer != 0, n,
+                                             ctx->opt_ransac_count_threads, ctx->opt_ransac_count_wpe);
+        launch_count_kernel(code, s, n_models, 1, 1, (const double4 *)pts, n, (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                            n_models, thresh2, qmax, (int32_t *)dgood);
+        ctx->dbg_count_kernel[0] = code, ctx->dbg_count_kernel[1] = 1;
+    } else if (shape == 2 && !err_sum) {
         hipLaunchKernelGGL((score_models_block_kernel<true, false>), dim3(std::min(n_models, 4096)), dim3(256), 0, s, (const double4 *)pts,
                            n, (const double *)dE, (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, thresh2, qmax,
                            (int32_t *)dgood, (double *)dsum, (const int32_t *)nullptr);
-    else
-        launch_score(s, (const double4 *)pts, n, (const double *)dE, nullptr, nullptr, n_models, n_models, thresh2, (int32_t *)dgood,
-                     (double *)dsum, err_sum != nullptr, qmax);
+        ctx->dbg_count_kernel[0] = kCountBlock, ctx->dbg_count_kernel[1] = 0;
+    } else {
+        ctx->dbg_count_kernel[0] = launch_score(s, (const double4 *)pts, n, (const double *)dE, nullptr, nullptr, n_models, n_models, thresh2,
+                                                (int32_t *)dgood, (double *)dsum, err_sum != nullptr, qmax);
+        ctx->dbg_count_kernel[1] = 1;
+    }
     prof_mark(ctx, MLPL_PROF_SCORE, 1, s);
     MLPL_HIP_TRY(hipGetLastError());
     MLPL_HIP_TRY(hipMemcpyAsync(count, dgood, (size_t)n_models * 4, hipMemcpyDeviceToHost, s));
@@ -3504,6 +3554,55 @@ int mlpl_count_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, 
         return MLPL_E_BAD_INPUT;
     }
     return score_models_impl(ctx, p1, p2, n, E, n_models, thresh2, count, nullptr, shape);
+}
+
+// The count-only pass exactly as a RANSAC pass runs it (tests): packed points, a dense model list of n_bound rows of which the first n_live
+// are live (the rest NaN), the live count read on the device, counts scattered through ids into the caller's table.
+int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_live, int n_bound,
+                          const int32_t *ids, int table_len, double thresh2, int point_splits, int32_t *table_inout) {
+    if (!ctx || !p1 || !p2 || !E || !table_inout || n < 1 || n_live < 0 || n_bound < 1 || n_live > n_bound || table_len < 1 ||
+        point_splits < -1 || point_splits > 1024 || (!ids && n_live > table_len)) {
+        set_error("mlpl_debug_count_pass: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    if (ids)
+        for (int i = 0; i < n_live; ++i)
+            if (ids[i] < 0 || ids[i] >= table_len) {
+                set_error("mlpl_debug_count_pass: ids[%d] = %d outside the table", i, ids[i]);
+                return MLPL_E_BAD_INPUT;
+            }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    void *dp1, *dp2, *dE, *dids, *dtab;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX5, (size_t)n_bound * 72, &dE))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX6, (size_t)(n_bound + 1) * 4, &dids))) return rc;   // [0] = live count, then the ids
+    if ((rc = ws_get(ctx, WS_AUX7, (size_t)table_len * 4, &dtab))) return rc;
+    std::vector<double> Epad((size_t)n_bound * 9, std::nan(""));
+    std::memcpy(Epad.data(), E, (size_t)n_live * 72);
+    std::vector<int32_t> hids((size_t)n_bound + 1, 0);
+    hids[0] = n_live;
+    for (int i = 0; i < n_live; ++i) hids[1 + i] = ids ? ids[i] : i;
+    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(dE, Epad.data(), (size_t)n_bound * 72, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(dids, hids.data(), (size_t)(n_bound + 1) * 4, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(dtab, table_inout, (size_t)table_len * 4, hipMemcpyHostToDevice, s));
+    double4 *pts;
+    if ((rc = pack_points(ctx, (const double *)dp1, (const double *)dp2, n, &pts, s))) return rc;
+    const int splits = point_splits < 0 ? score_point_splits(n, n_bound, false, ctx->opt_ransac_count_tiles) : point_splits;
+    const int32_t *d_total = (const int32_t *)dids;
+    ctx->dbg_count_kernel[0] = launch_score(s, (const double4 *)pts, n, (const double *)dE, d_total + 1, d_total, 0, n_bound, thresh2,
+                                            (int32_t *)dtab, (double *)nullptr, false, inlier_bound(thresh2), splits,
+                                            ctx->opt_ransac_f32_filter != 0, ctx->opt_ransac_count_mpl, ctx->opt_ransac_count_defer != 0,
+                                            ctx->opt_ransac_count_threads, ctx->opt_ransac_count_wpe);
+    ctx->dbg_count_kernel[1] = splits;
+    MLPL_HIP_TRY(hipGetLastError());
+    MLPL_HIP_TRY(hipMemcpyAsync(table_inout, dtab, (size_t)table_len * 4, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipStreamSynchronize(s));
+    return MLPL_OK;
 }
 
 int mlpl_ransac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double thresh, double confidence,
@@ -3689,9 +3788,10 @@ int mlpl_ransac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d
         }
         prof_mark(ctx, MLPL_PROF_SCORE, 0, s);
         prof_mark(ctx, MLPL_PROF_COUNT, 0, s);
-        launch_score(s, (const double4 *)pts, n, (const double *)B.dense_E, (const int32_t *)B.dense_id, (const int32_t *)B.total, 0,
+        ctx->dbg_count_kernel[0] = launch_score(s, (const double4 *)pts, n, (const double *)B.dense_E, (const int32_t *)B.dense_id, (const int32_t *)B.total, 0,
                      cnt * 10, thresh2, B.good, B.esum, !lazy, qmax, point_splits, ctx->opt_ransac_f32_filter != 0, ctx->opt_ransac_count_mpl,
                      ctx->opt_ransac_count_defer != 0, ctx->opt_ransac_count_threads, ctx->opt_ransac_count_wpe);
+        ctx->dbg_count_kernel[1] = point_splits;
         prof_mark(ctx, MLPL_PROF_COUNT, 1, s);
         if (lazy) {
             // error sums only for the models that can still win (ties on the inlier count are decided by them)

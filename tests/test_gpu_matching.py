@@ -7,6 +7,8 @@ import pytest
 import matchinglib_poselib_amd as mpa
 import oracle_lib
 from matchinglib_poselib_amd import synth
+from hamming_cases import check_hamming_cases
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -399,54 +401,48 @@ def test_hamming_every_kernel_variant_bit_exact(ctx, oracle, variant):
     (32-row MFMA tiles, 128-row LDS tiles), descriptor widths around the K-step (8 bytes), ties, ragged last tiles, k = 1."""
     _set_hamming(ctx, HAMMING_VARIANTS[variant])
     try:
-        for nq, nt, nbytes, k in [(1, 2, 32, 2), (15, 15, 32, 2), (64, 1000, 32, 1), (300, 129, 32, 2), (1000, 5000, 32, 2),
-                                  (77, 333, 64, 2), (50, 200, 16, 2), (40, 90, 61, 2), (33, 70, 24, 2), (20, 40, 1, 2),
-                                  (10, 600, 128, 2), (31, 33, 8, 2), (129, 4097, 32, 2), (513, 31, 32, 2), (2048, 2048, 32, 2),
-                                  (100, 9000, 64, 2), (640, 96, 9, 2)]:
-            q, t = synth.orb_pair(nq, nt, nbytes=nbytes, seed=2000 + nq + nt + nbytes)
-            idx, dist = mpa.knn_hamming(q, t, k=k, ctx=ctx)
-            oi, od = oracle.knn_hamming(q, t, k=k)
-            assert np.array_equal(dist, od), (variant, nq, nt, nbytes, k)
-            assert np.array_equal(idx, oi), (variant, nq, nt, nbytes, k)
-        # ties everywhere: 5 distinct descriptors, the smaller train index must win in every merge level
-        rng = np.random.default_rng(9)
-        base = rng.integers(0, 256, (5, 32), dtype=np.uint8)
-        t = base[rng.integers(0, 5, 3000)]
-        q = base[rng.integers(0, 5, 500)]
-        idx, dist = mpa.knn_hamming(q, t, ctx=ctx)
-        oi, od = oracle.knn_hamming(q, t)
-        assert np.array_equal(idx, oi) and np.array_equal(dist, od)
-        # extremes of the distance range: all-equal and all-different bits
-        z = np.zeros((70, 32), np.uint8)
-        o = np.full((90, 32), 255, np.uint8)
-        for a, b in ((z, o), (z, z[:40]), (o, np.concatenate([z[:45], o[:3]]))):
-            idx, dist = mpa.knn_hamming(a, b, ctx=ctx)
-            oi, od = oracle.knn_hamming(a, b)
-            assert np.array_equal(idx, oi) and np.array_equal(dist, od)
-        # the fused getMatches path on this variant
-        q, t = synth.orb_pair(700, 900, seed=31)
-        err, m = mpa.getMatches([None] * 700, [None] * 900, q, t, matcher_name="LINEAR", ctx=ctx)
-        rc, om = oracle.get_matches_linear(700, 900, q, t)
-        assert err == rc == 0 and m.tobytes() == om.tobytes()
+        check_hamming_cases(ctx, oracle, variant)
     finally:
         _set_hamming(ctx, HAMMING_DEFAULT)
 
 
-@pytest.mark.parametrize("variant", ["mfma_fp4", "mfma_fp4_qt2", "mfma_fp4_train01", "mfma_fp4_train_pm1"])
+_C2 = {}
+
+
+def _c2_oracle(oracle):
+    """BASELINE C2 inputs and the oracle's pairs for all 8192 rows (computed once per module)."""
+    if not _C2:
+        q, t = synth.orb_pair(8192, 8192, seed=20260102)
+        _C2["q"], _C2["t"] = q, t
+        _C2["oracle"] = oracle.knn_hamming_fast(q, t)[:2]
+    return _C2["q"], _C2["t"], _C2["oracle"]
+
+
+# the matrix-core instances of the C2 shape beyond HAMMING_VARIANTS: (options, (kernel, PRIO, waves, prefetch) of mlpl_debug_last_kernels)
+C2_INSTANCES = {
+    "ring_4_3_8_skip": (dict(hamming_mfma_qt=4, hamming_mfma_prio=3), (4, 3, 8, 2)),
+    "ring_4_0_16": (dict(hamming_mfma_qt=4, hamming_mfma_waves=16), (4, 0, 16, 2)),
+    "ring_4_0_8_prefetch4": (dict(hamming_mfma_qt=4, hamming_mfma_prefetch=4), (4, 0, 8, 4)),
+    "ring_4_0_8_prefetch6": (dict(hamming_mfma_qt=4, hamming_mfma_prefetch=6), (4, 0, 8, 6)),
+}
+
+
+@pytest.mark.parametrize("variant", ["mfma_fp4", "mfma_fp4_qt2", "mfma_fp4_train01", "mfma_fp4_train_pm1"] + sorted(C2_INSTANCES))
 def test_c2_full_size_matrix_core_equals_valu(ctx, oracle, variant):
-    """BASELINE C2 (8192 x 8192 x 256 bit): the matrix-core kernel against the VALU kernel (itself oracle-checked on samples)."""
-    q, t = synth.orb_pair(8192, 8192, seed=20260102)
-    _set_hamming(ctx, HAMMING_VARIANTS["valu_lds_tiled"])
-    idx0, dist0 = mpa.knn_hamming(q, t, ctx=ctx)
-    _set_hamming(ctx, HAMMING_VARIANTS[variant])
-    try:
+    """BASELINE C2 (8192 x 8192 x 256 bit): the matrix-core kernel against the VALU kernel and against the oracle on EVERY row."""
+    q, t, (oi, od) = _c2_oracle(oracle)
+    with options(ctx):
+        _set_hamming(ctx, HAMMING_VARIANTS["valu_lds_tiled"])
+        idx0, dist0 = mpa.knn_hamming(q, t, ctx=ctx)
+    with options(ctx, **(C2_INSTANCES[variant][0] if variant in C2_INSTANCES else {})):
+        if variant not in C2_INSTANCES:
+            _set_hamming(ctx, HAMMING_VARIANTS[variant])
         idx3, dist3 = mpa.knn_hamming(q, t, ctx=ctx)
-    finally:
-        _set_hamming(ctx, HAMMING_DEFAULT)
+        if variant in C2_INSTANCES:
+            rec = ctx.last_kernels()
+            assert (rec[2], rec[4], rec[5], rec[6]) == C2_INSTANCES[variant][1], (variant, rec)
     assert np.array_equal(idx0, idx3) and np.array_equal(dist0, dist3)
-    rows = np.random.default_rng(1).choice(8192, 64, replace=False)
-    oi, od = oracle.knn_hamming(q[rows], t)
-    assert np.array_equal(idx3[rows], oi) and np.array_equal(dist3[rows], od)
+    assert np.array_equal(idx3, oi) and np.array_equal(dist3, od)
 
 
 @pytest.mark.parametrize("variant", ["mfma_fp4", "valu_lds_tiled"])

@@ -100,7 +100,7 @@ class Mat {
 };
 
 // Proxy argument types with the member API of OpenCV's cv::_InputArray / _OutputArray / _InputOutputArray (core/mat.hpp) that the
-// facade uses -- getMat(), empty(), needed(), create(), type(), rows(), cols(), total() -- so that facade.cpp is written once against
+// facade uses -- getMat(), empty(), needed(), create(), clear(), type(), rows(), cols(), total() -- so that facade.cpp is written once against
 // that API and compiles unchanged against the real classes (MLPL_WITH_OPENCV).  Same class names and the same
 // `typedef const _InputArray& InputArray` shape as OpenCV, so the facade's signatures read exactly like the reference's.
 class _InputArray {
@@ -128,6 +128,10 @@ class _OutputArray : public _InputArray {
     Mat &getMatRef(int = -1) const { return *m_; }
     void release() const {
         if (m_) *m_ = Mat();
+    }
+    // OpenCV's _OutputArray::clear(): Mat::resize(0) on a matrix -- no rows, columns and type kept (empty() holds afterwards)
+    void clear() const {
+        if (m_) m_->rows = 0;
     }
 };
 class _InputOutputArray : public _OutputArray {

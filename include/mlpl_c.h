@@ -465,6 +465,40 @@ int mlpl_sorted_match_idx(const mlpl_dmatch *matches, int n, uint32_t *sorted_id
 int mlpl_ransac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double thresh,
                                     int max_iters, double confidence, const uint32_t *seeds, int recover_pose, double dist, mlpl_pair_result *out,
                                     uint8_t *d_masks, void *stream);
+/*
+ * poselib::refineEssentialLinear(p1, p2, E, mask, refineMethod, nr_inliers, R, t, th, num_iterative_steps, threshold_multiplier,
+ * pseudoHuberThreshold_multiplier, maxRelativeInlierCntLoss) (P/include/poselib/pose_linear_refinement.h, P/source/pose_linear_refinement.cpp:85-635):
+ * the iteratively re-weighted linear refit of E on its inliers.  method = solver | weights as poselib::RefinePostAlg: solver 0x1 PR_8PT,
+ * 0x2 PR_NISTER, 0x3 PR_STEWENIUS (one exact five-point solver serves both, as in USAC), weights 0x10 PR_TORR_WEIGHTS, 0x20
+ * PR_PSEUDOHUBER_WEIGHTS (threshold th * ph_mult), 0x30 PR_NO_WEIGHTS.  Per step j < steps: weights of the current inliers, refit on them
+ * (of several five-point solutions the one with the smallest Sampson-error sum over the inlier list, early exit tested every 4th list
+ * position), every point's Sampson L2 error on bearing vectors against th_mult th^2 - (j + 1) (th_mult th^2 - th^2) / steps; the step is
+ * kept when its count is at least (1 - max_loss) times the current one.  One workgroup per problem, all steps in one launch.
+ * p1, p2: n x 2 doubles (camera coordinates, host); E[9] in / out; mask: n bytes in / out (nonzero = inlier; out: 0 / 1).
+ * Returns 0 (reference: true) with E, mask, *n_inliers and *steps_done (accepted steps; both outputs may be NULL) written;
+ * MLPL_E_FAILED (reference: false: fewer than 6 starting inliers, or the first step lost too many) with E and mask untouched.
+ * As the reference: a solver nibble of 0 or above 4 ("not supported") and steps = 0 return 0 with E unchanged and the mask made 0 / 1;
+ * with PR_NISTER / PR_STEWENIUS, weight bits other than 0x10 / 0x20 run the unweighted solver.
+ * Deliberate deviations: PR_KNEIP (0x4) returns MLPL_E_UNSUPPORTED (OpenGV's eigensolver is not built); PR_8PT with weight bits other
+ * than 0x10 / 0x20 / 0x30 returns MLPL_E_BAD_INPUT (the reference reads uninitialised weights there); a PR_8PT fit on fewer than 8
+ * points counts as a failed refit (the reference's assert(n > 7) is compiled out and its null space is not unique).  The method is
+ * checked before anything else.  R / t of the reference are the caller's business: with every solver built here a passed R is cleared.
+ */
+int mlpl_refine_essential_linear(mlpl_ctx *ctx, const double *p1, const double *p2, int n, int method, double th, int steps, double th_mult,
+                                 double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done);
+/* The same for a batch in one launch, in the layout mlpl_ransac / usac / arrsac_essential_batch_dev write: problem b = d_p1 / d_p2 + b * stride * 2
+ * doubles (device), counts[b] <= stride of them (host), th[b] (host), E + 9 b (host, in / out), mask at d_masks + b * stride (device, in / out).
+ * Outputs per problem (host): status[b] (0 or MLPL_E_FAILED; a failed problem keeps E and mask), n_inliers[b], steps_done[b] (optional).
+ * Every problem's result is bit-identical to what mlpl_refine_essential_linear returns for it (the same kernel).  Returns 0 or the
+ * call's error (MLPL_E_UNSUPPORTED / MLPL_E_BAD_INPUT as above). */
+int mlpl_refine_essential_linear_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                           const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
+                                           uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, void *stream);
+/* mlpl_recover_pose_dev for a batch in the same layout (the batched cheirality step of the pair entries): E + 9 b (host), d_masks NULL (all
+ * points) or [n_problems][stride] on the device (in / out: the chosen candidate's mask), n_good[b], R + 9 b, t + 3 b (host).  Every problem's
+ * result equals what mlpl_recover_pose_dev returns for it. */
+int mlpl_recover_pose_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                const double *E, double dist, uint8_t *d_masks, int32_t *n_good, double *R, double *t, void *stream);
 /* d_matches_out: NULL, or a device block [n_pairs][nq] that receives every pair's match list (out[i].n_matches valid entries each,
  * ascending queryIdx) -- what a caller gathers beside the pose records (needs refit = 0).
  * Statistics of the last mlpl_pair_pose_batch_dev call: {RANSAC passes, pair slots summed over the passes, pairs redone by the

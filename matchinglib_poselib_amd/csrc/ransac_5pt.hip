@@ -3356,6 +3356,7 @@ void hub_streams_free(void *p) {
 #include "usac_impl.h"
 #include "pair_batch_impl.h"
 #include "pair_batch_usac.h"
+#include "linear_refine_impl.h"
 
 void free_rand_cache(void *p) { delete static_cast<RandCache *>(p); }
 
@@ -4154,6 +4155,60 @@ int mlpl_robust_essential_refine(mlpl_ctx *ctx, const double *p1, const double *
     std::memcpy(E_refined, h, 72);
     if (info) std::memcpy(info, h + 9, 8);
     return MLPL_OK;
+}
+
+int mlpl_refine_essential_linear(mlpl_ctx *ctx, const double *p1, const double *p2, int n, int method, double th, int steps, double th_mult,
+                                 double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done) {
+    static const char *who = "mlpl_refine_essential_linear";
+    LinRefineArgs probe{};
+    int rc;
+    if ((rc = linear_refine_method(method, probe, who))) return rc;
+    if (!ctx || !p1 || !p2 || !E || !mask || n < 0) {
+        set_error("%s: bad arguments", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nn = (size_t)std::max(n, 1);
+    void *dp1, *dp2, *dmask;
+    if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
+    if ((rc = ws_get(ctx, WS_MATCH, nn, &dmask))) return rc;
+    if (n > 0) {
+        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    const int32_t count = n;
+    int32_t st = 0, ninl = 0, done = 0;
+    if ((rc = linear_refine_batch(ctx, 1, (const double *)dp1, (const double *)dp2, (int)nn, &count, &th, method, steps, th_mult, ph_mult, max_loss,
+                                  E, (uint8_t *)dmask, &ninl, &st, &done, s, who)))
+        return rc;
+    if (st != 0) return st;
+    if (n > 0) MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    if (n_inliers) *n_inliers = ninl;
+    if (steps_done) *steps_done = done;
+    return MLPL_OK;
+}
+
+int mlpl_refine_essential_linear_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                           const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
+                                           uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, void *stream) {
+    if (!ctx) {
+        set_error("mlpl_refine_essential_linear_batch_dev: ctx is mandatory");
+        return MLPL_E_BAD_INPUT;
+    }
+    return linear_refine_batch(ctx, n_problems, d_p1, d_p2, stride, counts, th, method, steps, th_mult, ph_mult, max_loss, E, d_masks, n_inliers,
+                               status, steps_done, pick_stream(ctx, stream), "mlpl_refine_essential_linear_batch_dev");
+}
+
+int mlpl_recover_pose_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                const double *E, double dist, uint8_t *d_masks, int32_t *n_good, double *R, double *t, void *stream) {
+    if (!ctx) {
+        set_error("mlpl_recover_pose_batch_dev: ctx is mandatory");
+        return MLPL_E_BAD_INPUT;
+    }
+    return recover_pose_batch(ctx, n_problems, d_p1, d_p2, stride, counts, E, dist, d_masks, n_good, R, t, pick_stream(ctx, stream));
 }
 
 int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,

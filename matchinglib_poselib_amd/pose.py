@@ -281,6 +281,82 @@ def robust_essential_refine(p1, p2, E_init, th: float, mask=None, ctx: Optional[
     return E, int(info[0]), int(info[1])
 
 
+# poselib::RefinePostAlg (P/include/poselib/pose_estim.h:79-88): a solver nibble OR-ed with a weighting
+PR_8PT, PR_NISTER, PR_STEWENIUS, PR_KNEIP = 0x1, 0x2, 0x3, 0x4
+PR_TORR_WEIGHTS, PR_PSEUDOHUBER_WEIGHTS, PR_NO_WEIGHTS = 0x10, 0x20, 0x30
+
+
+def refine_essential_linear(p1, p2, E, mask, refine_method: int = PR_8PT | PR_PSEUDOHUBER_WEIGHTS, th: float = 0.008, num_iterative_steps: int = 4,
+                            threshold_multiplier: float = 2.0, pseudo_huber_threshold_multiplier: float = 0.1,
+                            max_relative_inlier_cnt_loss: float = 0.15, ctx: Optional[Context] = None) -> dict:
+    """poselib::refineEssentialLinear (pose_linear_refinement.cpp:85-309) -> dict(ok, E, mask, n_inliers, steps_done).  ok = False is the
+    reference's false (E and mask returned unchanged); PR_KNEIP raises MlplError(MLPL_E_UNSUPPORTED), PR_8PT with weight bits other than
+    0x10 / 0x20 / 0x30 MlplError(MLPL_E_BAD_INPUT)."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    if p2.shape[0] != n:
+        raise ValueError("p1 and p2 differ in length")
+    E_io = np.array(E, np.float64).reshape(3, 3).copy()
+    m = np.array(mask, np.uint8).reshape(-1).copy()
+    if m.shape[0] != n:
+        raise ValueError("the mask must hold one byte per correspondence")
+    ninl, done = C.c_int(0), C.c_int(0)
+    rc = ctx.lib.mlpl_refine_essential_linear(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, int(refine_method), float(th), int(num_iterative_steps),
+                                              float(threshold_multiplier), float(pseudo_huber_threshold_multiplier),
+                                              float(max_relative_inlier_cnt_loss), E_io.ctypes.data, m.ctypes.data, C.byref(ninl), C.byref(done))
+    if rc not in (0, _lib.MLPL_E_FAILED):
+        raise MlplError(rc, "mlpl_refine_essential_linear", _lib.last_error())
+    return dict(ok=(rc == 0), E=E_io, mask=m, n_inliers=ninl.value if rc == 0 else 0, steps_done=done.value if rc == 0 else 0)
+
+
+def refine_essential_linear_batch(d_p1, d_p2, counts, E, d_masks, th, refine_method: int = PR_8PT | PR_PSEUDOHUBER_WEIGHTS,
+                                  num_iterative_steps: int = 4, threshold_multiplier: float = 2.0, pseudo_huber_threshold_multiplier: float = 0.1,
+                                  max_relative_inlier_cnt_loss: float = 0.15, ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_essential_linear_batch_dev: d_p1, d_p2 float64 CUDA tensors [B, stride, 2], counts[b] valid rows, E float64 [B, 9] or
+    [B, 3, 3] (host), d_masks uint8 CUDA tensor [B, stride] (refined in place), th a scalar or one per problem.  One launch for the batch.
+    Returns dict(status int32 [B] (0 or MLPL_E_FAILED), E [B, 3, 3], n_inliers [B], steps_done [B])."""
+    import torch
+
+    B, stride = d_p1.shape[0], d_p1.shape[1]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (B, stride, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    assert d_masks.is_cuda and d_masks.dtype == torch.uint8 and d_masks.shape == (B, stride) and d_masks.is_contiguous()
+    ctx = ctx or default_context(d_p1.device.index or 0)
+    cn = np.ascontiguousarray(counts, np.int32).reshape(B)
+    thv = np.ascontiguousarray(np.broadcast_to(np.asarray(th, np.float64), (B,)))
+    E_io = np.array(E, np.float64).reshape(B, 9).copy()
+    ninl, status, done = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    rc = ctx.lib.mlpl_refine_essential_linear_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, thv.ctypes.data,
+                                                        int(refine_method), int(num_iterative_steps), float(threshold_multiplier),
+                                                        float(pseudo_huber_threshold_multiplier), float(max_relative_inlier_cnt_loss), E_io.ctypes.data,
+                                                        d_masks.data_ptr(), ninl.ctypes.data, status.ctypes.data, done.ctypes.data,
+                                                        torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_refine_essential_linear_batch_dev", _lib.last_error())
+    return dict(status=status, E=E_io.reshape(B, 3, 3), n_inliers=ninl, steps_done=done)
+
+
+def recover_pose_batch(d_p1, d_p2, counts, E, d_masks=None, dist: float = 50.0, ctx: Optional[Context] = None) -> dict:
+    """mlpl_recover_pose_batch_dev: the cheirality step (getPoseTriangPts without points) for a batch in the layout above; d_masks (uint8 CUDA
+    tensor [B, stride] or None = all points) receives the chosen candidate's mask.  Returns dict(n_good [B], R [B, 3, 3], t [B, 3])."""
+    import torch
+
+    B, stride = d_p1.shape[0], d_p1.shape[1]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (B, stride, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    if d_masks is not None:
+        assert d_masks.is_cuda and d_masks.dtype == torch.uint8 and d_masks.shape == (B, stride) and d_masks.is_contiguous()
+    ctx = ctx or default_context(d_p1.device.index or 0)
+    cn = np.ascontiguousarray(counts, np.int32).reshape(B)
+    Eh = np.ascontiguousarray(np.asarray(E, np.float64).reshape(B, 9))
+    n_good, R, t = np.zeros(B, np.int32), np.zeros((B, 3, 3)), np.zeros((B, 3))
+    rc = ctx.lib.mlpl_recover_pose_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, Eh.ctypes.data, float(dist),
+                                             None if d_masks is None else d_masks.data_ptr(), n_good.ctypes.data, R.ctypes.data, t.ctypes.data,
+                                             torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_recover_pose_batch_dev", _lib.last_error())
+    return dict(n_good=n_good, R=R, t=t)
+
+
 def ransac_essential_device(p1, p2, thresh: float, confidence: float = 0.999, max_iters: int = 1000, refit: bool = True,
                             seed: int = 0, ctx: Optional[Context] = None, mask_out=None, stream: Optional[int] = None) -> dict:
     """Same as ransac_essential on device-resident torch tensors (float64 [n,2]); the mask stays on the device."""

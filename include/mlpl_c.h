@@ -78,7 +78,9 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *       prefetch of 4 or 6, which beats "hamming_mfma_prio"; prefetch and prio 3 exist with 8-wave workgroups only and are ignored elsewhere.
  *       "hamming_expand_fine" (default 1) = small launches expand the train set with one thread per (tile, K-step, lane).
  *   L2: "l2_mfma_waves" 0|4|8 and "l2_mfma_blocks_per_cu" shape the int8 matrix-core kernel of the forced mode (see mlpl_set_l2_path);
- *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0).
+ *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0);
+ *     "l2_fold_counts" (default 1) = mlpl_match_l2_dev's fold over the train splits evaluates the ratio predicate and writes the pass
+ *     counts itself (four launches), 0 = separate merge and counting launches (five; A/B and tests; same results).
  *   RANSAC: "ransac_device_draw" (default 1) = large passes draw their samples on the device (mlpl_debug_ransac_draw); "ransac_chunk" hypotheses per device pass (0 = 32768 = the maximum; the sequential best/niters rule is replayed across
  *     passes); "ransac_lazy_sums" (default 1) = the passes count inliers without the division and compute error sums only for the
  *     models that can still win, 0 = sums for every model; "ransac_f32_filter" (default 1) = the counting kernels decide in packed single
@@ -202,6 +204,18 @@ int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_s
                            const uint8_t *d_t, int nt, size_t t_stride, size_t t_batch_stride, int nbytes,
                            int ratio_test, float ratio, int batch, int32_t *d_idx, int32_t *d_dist,
                            mlpl_dmatch *d_out, int32_t *d_n_out, void *stream);
+
+/* The same for CV_32F descriptors: the float half of the LINEAR branch, M/source/matchers.cpp:632-707 -- cvflann::Index<L2<float>>
+ * knnSearch (:634-664: squared L2 in cvflann's summation order) and the ratio loop (:677-701: keep q iff d0 < 0.75f * d1; rows in
+ * ascending queryIdx, imgIdx = -1, distance = d0).  Strides in ELEMENTS and argument limits as mlpl_knn2_l2sq_f32_dev (dim in [1,1024],
+ * nt >= k, batch <= 65535); follows mlpl_set_l2_path and option "l2_float_mfma" exactly as that entry does.  Every output -- d_idx,
+ * d_dist, d_out[0..n), d_n_out -- is bit-identical to mlpl_knn2_l2sq_f32_dev followed by mlpl_ratio_compact_f32_dev on every L2 path;
+ * wherever the path ends in a fold over train splits (exact, int8, auto) that fold evaluates the predicate and counts the passes
+ * itself (option "l2_fold_counts"), so the call is four launches instead of five.  nq == 0: OK, d_n_out[b] = 0. */
+int mlpl_match_l2_dev(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride,
+                      const float *d_t, int nt, size_t t_stride, size_t t_batch_stride, int dim,
+                      int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
+                      mlpl_dmatch *d_out, int32_t *d_n_out, void *stream);
 
 /* ---- correspondence gather (pre-step of the pose path) -------------------------------------------------------
  * Replaces the gather + ImgToCamCoordTrans of StereoRefine::addNewCorrespondences (P/source/stereo_pose_refinement.cpp:
@@ -414,6 +428,12 @@ typedef struct {
 int mlpl_pair_pose_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                        const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
                        int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream);
+/* The same pair with CV_32F descriptors (SIFT, RootSIFT, KAZE ...: the float half of getMatches "LINEAR", M/source/matchers.cpp:632-707):
+ * squared-L2 2-NN + 0.75 ratio test (mlpl_match_l2_dev) in place of the Hamming step, everything behind it unchanged.  d_q / d_t: dense
+ * nq / nt x dim floats, dim in [1,1024].  Record fields, status codes and host hops as mlpl_pair_pose_dev. */
+int mlpl_pair_pose_f32_dev(mlpl_ctx *ctx, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                           const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
+                           int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream);
 
 /*
  * A BATCH of image pairs through the same pipeline with the pair as a grid dimension of every launch (the reference harness loop over
@@ -426,6 +446,13 @@ int mlpl_pair_pose_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, const uint8_t 
 int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                              const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
                              int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream);
+/* mlpl_pair_pose_batch_dev on CV_32F descriptors (M/source/matchers.cpp:632-707 as the matching step): d_q / d_t are
+ * [n_pairs][nq][dim] / [n_pairs][nt][dim] floats, `dim` stands where `nbytes` stood; everything else -- record fields and status codes
+ * (-1 fewer than 16 matches, -2 estimator failure), host hops, d_matches_out, mlpl_pair_batch_last_stats, refit != 0 falling back to the
+ * single-pair entry (mlpl_pair_pose_f32_dev) -- as above.  Every pair's record equals what mlpl_pair_pose_f32_dev returns for it. */
+int mlpl_pair_pose_batch_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                                 const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
+                                 int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream);
 /* mlpl_pair_pose_batch_dev (refit = 0) with `lanes` calls in flight on one GPU: lane l = (ctxs[l], streams[l]: a context and a stream of
  * its own, same device) runs the l-th contiguous share of the batch on its own host thread inside this call, which returns when every
  * lane has finished AND its stream is idle.  Inputs must be complete before the call (they were produced on another stream).
@@ -447,12 +474,24 @@ int mlpl_pair_pose_batch_lanes_dev(mlpl_ctx *const *ctxs, void *const *streams, 
 int mlpl_pair_pose_batch_usac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                                   const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
                                   const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream);
+/* The USAC batch on CV_32F descriptors (matching step: M/source/matchers.cpp:632-707; [n_pairs][nq][dim] / [n_pairs][nt][dim] floats): the
+ * record per pair is what mlpl_match_l2_dev + mlpl_gather_match_points_dev -> mlpl_usac_essential_dev -> mlpl_recover_pose_dev return
+ * for it; the PROSAC order is the same std::sort of the (float) matching costs; the cohorts are fed as above -- the later cohorts are
+ * matched beside the earlier cohorts' estimators, through the one context: the float matcher's per-context blocks are sized by the
+ * first (largest) cohort, and its data-kind hint word may be stale across cohorts, which can cost speed and never results. */
+int mlpl_pair_pose_batch_usac_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                                      const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
+                                      const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream);
 /* ... and with ARRSAC, estimateEssentialMat's default method (pose_estim.h:207; `refine` = robustEssentialRefine on the winner's inliers):
  * mlpl_arrsac_essential_batch_dev on the pairs' correspondences.  rng_states[2 * n_pairs]: a pair of cv::RNG states per image pair (in / out).
  * Record per pair: status 0 / -1 / -2 (ARRSAC failed), iters = 0, n_inliers = inliers of the unrefined winner, n_good, E, R, t. */
 int mlpl_pair_pose_batch_arrsac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                                     const float *d_kp2, const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states, double dist,
                                     mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream);
+/* The ARRSAC batch on CV_32F descriptors (matching step: M/source/matchers.cpp:632-707), otherwise as mlpl_pair_pose_batch_arrsac_dev. */
+int mlpl_pair_pose_batch_arrsac_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                                        const float *d_kp2, const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states,
+                                        double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream);
 /* poselib::getSortedMatchIdx (P/source/pose_helper.cpp:2896-2923) on a HOST match list: the indices of the matches in the order
  * std::sort leaves them when comparing the distances -- the PROSAC order estimateEssentialOrPoseUSAC and the batch entry above use. */
 int mlpl_sorted_match_idx(const mlpl_dmatch *matches, int n, uint32_t *sorted_idx);

@@ -91,6 +91,21 @@ int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, lo
  *   out[10] train splits;  out[11] 64-bit K-steps of the matrix-core kernels (0 VALU). */
 int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[12]);
 
+/* Diagnostics: what the last float knn / match call of this context (mlpl_knn2_l2sq_f32*, mlpl_match_l2_dev, the float pair entries)
+ * chose.  Writes 4 ints and returns 4: out[0] path -- 1 exact fp32 kernel, 2 int8 matrix-core path (forced), 3 the auto path's fused
+ * kernel (int8 or exact by the device flag), 4 fp16 candidate path, 0 nothing launched (nq = 0); out[1] train splits the fold reads
+ * (auto: the larger of the two tables; 0 on the fp16 path); out[2] 1 = the fold kernel produced the pass counts of the ratio test
+ * (mlpl_match_l2_dev with option "l2_fold_counts"); out[3] kernel launches of the call (memsets and copies not counted). */
+int mlpl_debug_last_l2_match(mlpl_ctx *ctx, int out[4]);
+
+/* Tests: the float knn with the fused fold alone (no ratio_write_kernel behind it), on the context's own stream: d_idx / d_dist as
+ * mlpl_knn2_l2sq_f32_dev writes them, counts[batch][ceil(nq / 64)] (host) = the pass counts of the ratio predicate per group of 64
+ * queries as knn_l2_fold_ratio_kernel stored them (-1: a group no workgroup wrote).  Returns the number of counts, 0 when the path taken
+ * has no fold (the fp16 candidate path), or a negative error.  Arguments as mlpl_match_l2_dev; the inputs must be complete on the device. */
+int mlpl_debug_l2_fold_counts(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride, const float *d_t, int nt,
+                              size_t t_stride, size_t t_batch_stride, int dim, int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
+                              int32_t *counts);
+
 /* Tests: one count-only scoring pass exactly as a RANSAC pass runs it.  The correspondences are packed as for RANSAC; E holds n_live
  * models (9 doubles each), padded on the device to n_bound rows with NaN models; the live count n_live is read on the device; the count
  * of live model m goes to table_inout[ids ? ids[m] : m] (table_len ints, uploaded as given and read back: slots no id names keep their

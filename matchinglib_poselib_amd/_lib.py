@@ -78,6 +78,12 @@ _SIGNATURES = {
     "mlpl_match_hamming_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_int, c_size_t,
                                        c_size_t, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "mlpl_match_l2_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_int, c_size_t,
+                                  c_size_t, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    "mlpl_debug_last_l2_match": (c_int, [c_void_p, c_void_p]),
+    "mlpl_debug_l2_fold_counts": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_int, c_size_t, c_size_t, c_int, c_int, c_float, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
     "mlpl_gather_match_points_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
     "mlpl_img_to_cam": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
@@ -128,6 +134,15 @@ _SIGNATURES = {
                                    c_int, c_double, c_int, c_u32, c_double, c_void_p, c_void_p]),
     "mlpl_pair_pose_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                          c_int, c_double, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    # the CV_32F forms: `dim` floats per row where the forms above have `nbytes` bytes
+    "mlpl_pair_pose_f32_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                       c_int, c_double, c_int, c_u32, c_double, c_void_p, c_void_p]),
+    "mlpl_pair_pose_batch_f32_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                             c_int, c_double, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_pair_pose_batch_usac_f32_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                  c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_pair_pose_batch_arrsac_f32_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int,
+                                                    c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "mlpl_pair_pose_batch_lanes_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_double, c_int, c_double, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "mlpl_pair_pose_batch_usac_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -252,6 +267,14 @@ class Context:
         n = self._lib.mlpl_debug_last_kernels(self._h, out)
         if n < 0:
             raise MlplError(n, "mlpl_debug_last_kernels", last_error())
+        return list(out[:n])
+
+    def last_l2_match(self) -> list:
+        """mlpl_debug_last_l2_match (include/mlpl_debug.h): {path, train splits, counts by the fold, launches} of the last float match."""
+        out = (C.c_int * 4)()
+        n = self._lib.mlpl_debug_last_l2_match(self._h, out)
+        if n < 0:
+            raise MlplError(n, "mlpl_debug_last_l2_match", last_error())
         return list(out[:n])
 
     def close(self):

@@ -145,15 +145,31 @@ _PAIR_RESULT_DTYPE = np.dtype([("n_matches", np.int32), ("n_inliers", np.int32),
 assert _PAIR_RESULT_DTYPE.itemsize == C.sizeof(_PairResult)
 
 
+def _desc_entry(lib, d_q, d_t, name: str):
+    """The C entry for the descriptors' dtype: uint8 -> `name` (Hamming), float32 -> its _f32 form (squared L2); anything else is refused."""
+    import torch
+
+    if d_q.dtype != d_t.dtype:
+        raise TypeError(f"{name}: query and train descriptors differ in dtype ({d_q.dtype}, {d_t.dtype})")
+    if d_q.dtype == torch.uint8:
+        return getattr(lib, name), name
+    if d_q.dtype == torch.float32:
+        f32 = name[:-len("_dev")] + "_f32_dev"
+        return getattr(lib, f32), f32
+    raise TypeError(f"{name}: descriptors must be torch.uint8 (CV_8U) or torch.float32 (CV_32F), not {d_q.dtype}")
+
+
 def process_pair_on_device(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, th_pix: float = 0.8, max_iters: int = 1000,
                            confidence: float = 0.999, refit: bool = False, seed: int = 0, dist: float = 50.0, pair_id: int = 0,
                            scratch: Optional[dict] = None) -> np.ndarray:
-    """One image pair, device-resident inputs (torch CUDA tensors): Hamming 2-NN + ratio -> gather matched keypoints
-    (ImgToCamCoordTrans) -> RANSAC essential matrix -> cheirality, in one library call (mlpl_pair_pose_dev: two host hops,
-    nothing else leaves the device).  Returns one RECORD_DTYPE record.  `scratch` is accepted for compatibility and unused."""
+    """One image pair, device-resident inputs (torch CUDA tensors): 2-NN + ratio (Hamming for uint8 descriptors, squared L2 for float32)
+    -> gather matched keypoints (ImgToCamCoordTrans) -> RANSAC essential matrix -> cheirality, in one library call (mlpl_pair_pose_dev /
+    mlpl_pair_pose_f32_dev: two host hops, nothing else leaves the device).  Returns one RECORD_DTYPE record.  `scratch` is accepted
+    for compatibility and unused."""
     import torch
 
-    assert d_q.is_cuda and d_q.dtype == torch.uint8 and d_q.is_contiguous() and d_t.is_contiguous()
+    entry, ename = _desc_entry(ctx.lib, d_q, d_t, "mlpl_pair_pose_dev")
+    assert d_q.is_cuda and d_q.dim() == 2 and d_t.dim() == 2 and d_q.shape[1] == d_t.shape[1] and d_q.is_contiguous() and d_t.is_contiguous()
     assert d_kp1.dtype == torch.float32 and d_kp2.dtype == torch.float32 and d_kp1.is_contiguous() and d_kp2.is_contiguous()
     rec = np.zeros(1, RECORD_DTYPE)
     rec["pair_id"] = pair_id
@@ -162,9 +178,9 @@ def process_pair_on_device(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, th_pix:
     th = th_pix * 4.0 / (np.sqrt(2.0) * (K0[0] + K0[1] + K1[0] + K1[1]))  # stereo_pose_refinement.h:280-286
     res = _PairResult()
     st = torch.cuda.current_stream(d_q.device).cuda_stream
-    check(ctx.lib.mlpl_pair_pose_dev(ctx.handle, d_q.data_ptr(), d_q.shape[0], d_t.data_ptr(), d_t.shape[0], d_q.shape[1],
-                                     d_kp1.data_ptr(), d_kp2.data_ptr(), k0, k1, float(th), int(max_iters), float(confidence),
-                                     1 if refit else 0, int(seed) & 0xFFFFFFFF, float(dist), C.addressof(res), st), "mlpl_pair_pose_dev")
+    check(entry(ctx.handle, d_q.data_ptr(), d_q.shape[0], d_t.data_ptr(), d_t.shape[0], d_q.shape[1],
+                d_kp1.data_ptr(), d_kp2.data_ptr(), k0, k1, float(th), int(max_iters), float(confidence),
+                1 if refit else 0, int(seed) & 0xFFFFFFFF, float(dist), C.addressof(res), st), ename)
     rec["n_matches"] = res.n_matches
     rec["status"] = res.status
     if res.status == 0:
@@ -177,14 +193,16 @@ def process_pair_on_device(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, th_pix:
 
 def process_pairs_batched(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, seeds, th_pix: float = 0.8, max_iters: int = 1000,
                           confidence: float = 0.999, refit: bool = False, dist: float = 50.0, pair_ids=None, matches_out=None) -> np.ndarray:
-    """A batch of image pairs in ONE library call (mlpl_pair_pose_batch_dev): device tensors d_q [B, nq, nbytes] uint8, d_t [B, nt, nbytes],
-    d_kp1 [B, nq, 2] float32, d_kp2 [B, nt, 2]; seeds: B RANSAC seeds.  The pair is a grid dimension of every launch -- no host threads, a
+    """A batch of image pairs in ONE library call (mlpl_pair_pose_batch_dev): device tensors d_q [B, nq, nbytes] uint8, d_t [B, nt, nbytes]
+    -- or float32 [B, nq, dim] / [B, nt, dim], which go to mlpl_pair_pose_batch_f32_dev --, d_kp1 [B, nq, 2] float32, d_kp2 [B, nt, 2];
+    seeds: B RANSAC seeds.  The pair is a grid dimension of every launch -- no host threads, a
     handful of host hops per 256 pairs -- and every record equals process_pair_on_device's for that pair.  matches_out: optional int32
     CUDA tensor [B, nq, 4] that receives the match lists (cv::DMatch rows, n_matches valid per pair).  Returns B RECORD_DTYPE records."""
     import torch
 
     B = d_q.shape[0]
-    assert d_q.is_cuda and d_q.dtype == torch.uint8 and d_q.dim() == 3 and d_t.dim() == 3 and d_t.shape[0] == B
+    entry, ename = _desc_entry(ctx.lib, d_q, d_t, "mlpl_pair_pose_batch_dev")
+    assert d_q.is_cuda and d_q.dim() == 3 and d_t.dim() == 3 and d_t.shape[0] == B and d_q.shape[2] == d_t.shape[2]
     assert d_kp1.dtype == torch.float32 and d_kp2.dtype == torch.float32 and d_kp1.shape == (B, d_q.shape[1], 2) and d_kp2.shape == (B, d_t.shape[1], 2)
     assert d_q.is_contiguous() and d_t.is_contiguous() and d_kp1.is_contiguous() and d_kp2.is_contiguous()
     k0 = (C.c_double * 4)(*K0)
@@ -196,10 +214,9 @@ def process_pairs_batched(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, seeds, t
     st = torch.cuda.current_stream(d_q.device).cuda_stream
     if matches_out is not None:
         assert matches_out.is_cuda and matches_out.dtype == torch.int32 and matches_out.shape == (B, d_q.shape[1], 4) and matches_out.is_contiguous()
-    check(ctx.lib.mlpl_pair_pose_batch_dev(ctx.handle, B, d_q.data_ptr(), d_q.shape[1], d_t.data_ptr(), d_t.shape[1], d_q.shape[2], d_kp1.data_ptr(),
-                                           d_kp2.data_ptr(), k0, k1, float(th), int(max_iters), float(confidence), 1 if refit else 0, sd.ctypes.data,
-                                           float(dist), C.addressof(res), matches_out.data_ptr() if matches_out is not None else None, st),
-          "mlpl_pair_pose_batch_dev")
+    check(entry(ctx.handle, B, d_q.data_ptr(), d_q.shape[1], d_t.data_ptr(), d_t.shape[1], d_q.shape[2], d_kp1.data_ptr(),
+                d_kp2.data_ptr(), k0, k1, float(th), int(max_iters), float(confidence), 1 if refit else 0, sd.ctypes.data,
+                float(dist), C.addressof(res), matches_out.data_ptr() if matches_out is not None else None, st), ename)
     raw = np.frombuffer(res, _PAIR_RESULT_DTYPE, count=B)   # the library's result block, field by field (no per-pair Python)
     rec = np.zeros(B, RECORD_DTYPE)
     rec["pair_id"] = np.arange(B) if pair_ids is None else np.asarray(pair_ids)
@@ -214,13 +231,14 @@ def process_pairs_batched_usac(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, see
                                refine: int = 0, check_degeneracy: int = 0, sprt_delta: float = 0.05, sprt_epsilon: float = 0.15, sprt_ms: float = 6.0,
                                sprt_tm: float = 2736.0, max_hyp: int = 50000, dist: float = 50.0, pair_ids=None, matches_out=None) -> Tuple[np.ndarray, np.ndarray]:
     """process_pairs_batched with USAC (the reference harness' default RobMethod; defaults = its cfgUSAC: POSE_STEWENIUS + REF_WEIGHTS) as the
-    robust estimator: mlpl_pair_pose_batch_usac_dev.  prosac: PROSAC sampling in the order of the matching costs.
+    robust estimator: mlpl_pair_pose_batch_usac_dev (uint8 descriptors) / mlpl_pair_pose_batch_usac_f32_dev (float32).  prosac: PROSAC sampling in the order of the matching costs.
     Returns (records [B] RECORD_DTYPE, the library's raw result block [B]: n_matches, n_inliers, n_good, status, iters, E, R, t)."""
     import torch
     from .pose import UsacParams
 
     B = d_q.shape[0]
-    assert d_q.is_cuda and d_q.dtype == torch.uint8 and d_q.dim() == 3 and d_t.dim() == 3 and d_t.shape[0] == B
+    entry, ename = _desc_entry(ctx.lib, d_q, d_t, "mlpl_pair_pose_batch_usac_dev")
+    assert d_q.is_cuda and d_q.dim() == 3 and d_t.dim() == 3 and d_t.shape[0] == B and d_q.shape[2] == d_t.shape[2]
     assert d_kp1.dtype == torch.float32 and d_kp2.dtype == torch.float32 and d_kp1.shape == (B, d_q.shape[1], 2) and d_kp2.shape == (B, d_t.shape[1], 2)
     assert d_q.is_contiguous() and d_t.is_contiguous() and d_kp1.is_contiguous() and d_kp2.is_contiguous()
     k0 = (C.c_double * 4)(*K0)
@@ -237,9 +255,9 @@ def process_pairs_batched_usac(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, see
     st = torch.cuda.current_stream(d_q.device).cuda_stream
     if matches_out is not None:
         assert matches_out.is_cuda and matches_out.dtype == torch.int32 and matches_out.shape == (B, d_q.shape[1], 4) and matches_out.is_contiguous()
-    check(ctx.lib.mlpl_pair_pose_batch_usac_dev(ctx.handle, B, d_q.data_ptr(), d_q.shape[1], d_t.data_ptr(), d_t.shape[1], d_q.shape[2], d_kp1.data_ptr(),
-                                                d_kp2.data_ptr(), k0, k1, C.addressof(P), 1 if prosac else 0, sd.ctypes.data, float(dist), C.addressof(res),
-                                                matches_out.data_ptr() if matches_out is not None else None, st), "mlpl_pair_pose_batch_usac_dev")
+    check(entry(ctx.handle, B, d_q.data_ptr(), d_q.shape[1], d_t.data_ptr(), d_t.shape[1], d_q.shape[2], d_kp1.data_ptr(),
+                d_kp2.data_ptr(), k0, k1, C.addressof(P), 1 if prosac else 0, sd.ctypes.data, float(dist), C.addressof(res),
+                matches_out.data_ptr() if matches_out is not None else None, st), ename)
     raw = np.frombuffer(res, _PAIR_RESULT_DTYPE, count=B).copy()
     rec = np.zeros(B, RECORD_DTYPE)
     rec["pair_id"] = np.arange(B) if pair_ids is None else np.asarray(pair_ids)
@@ -252,13 +270,14 @@ def process_pairs_batched_usac(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, see
 
 def process_pairs_batched_arrsac(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, th_pix: float = 0.8, refine: bool = True, rng_states=None, dist: float = 50.0,
                                  matches_out=None):
-    """process_pairs_batched with ARRSAC (estimateEssentialMat's default method) as the robust estimator: mlpl_pair_pose_batch_arrsac_dev.
-    rng_states: uint64 [B, 2], advanced in place (default: fresh cv::RNG streams for every pair).  Returns (records, raw result block)."""
+    """process_pairs_batched with ARRSAC (estimateEssentialMat's default method) as the robust estimator: mlpl_pair_pose_batch_arrsac_dev
+    (uint8 descriptors) / mlpl_pair_pose_batch_arrsac_f32_dev (float32).  rng_states: uint64 [B, 2], advanced in place (default: fresh cv::RNG streams for every pair).  Returns (records, raw result block)."""
     import torch
     from .pose import ARRSAC_RNG_FRESH
 
     B = d_q.shape[0]
-    assert d_q.is_cuda and d_q.dtype == torch.uint8 and d_q.dim() == 3 and d_t.dim() == 3 and d_t.shape[0] == B
+    entry, ename = _desc_entry(ctx.lib, d_q, d_t, "mlpl_pair_pose_batch_arrsac_dev")
+    assert d_q.is_cuda and d_q.dim() == 3 and d_t.dim() == 3 and d_t.shape[0] == B and d_q.shape[2] == d_t.shape[2]
     assert d_q.is_contiguous() and d_t.is_contiguous() and d_kp1.is_contiguous() and d_kp2.is_contiguous()
     k0 = (C.c_double * 4)(*K0)
     k1 = (C.c_double * 4)(*K1)
@@ -267,9 +286,9 @@ def process_pairs_batched_arrsac(ctx: Context, d_q, d_t, d_kp1, d_kp2, K0, K1, t
     assert st.dtype == np.uint64 and st.shape == (B, 2) and st.flags.c_contiguous
     res = (_PairResult * B)()
     stream = torch.cuda.current_stream(d_q.device).cuda_stream
-    check(ctx.lib.mlpl_pair_pose_batch_arrsac_dev(ctx.handle, B, d_q.data_ptr(), d_q.shape[1], d_t.data_ptr(), d_t.shape[1], d_q.shape[2], d_kp1.data_ptr(),
-                                                  d_kp2.data_ptr(), k0, k1, float(th), 1 if refine else 0, st.ctypes.data, float(dist), C.addressof(res),
-                                                  matches_out.data_ptr() if matches_out is not None else None, stream), "mlpl_pair_pose_batch_arrsac_dev")
+    check(entry(ctx.handle, B, d_q.data_ptr(), d_q.shape[1], d_t.data_ptr(), d_t.shape[1], d_q.shape[2], d_kp1.data_ptr(),
+                d_kp2.data_ptr(), k0, k1, float(th), 1 if refine else 0, st.ctypes.data, float(dist), C.addressof(res),
+                matches_out.data_ptr() if matches_out is not None else None, stream), ename)
     raw = np.frombuffer(res, _PAIR_RESULT_DTYPE, count=B).copy()
     rec = np.zeros(B, RECORD_DTYPE)
     rec["pair_id"] = np.arange(B)

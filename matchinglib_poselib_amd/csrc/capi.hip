@@ -158,6 +158,7 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
     ctx->opt_arrsac_refine_warm_start = 1;
     ctx->opt_usac_sprt_fast = 1;
     ctx->opt_l2_float_mfma = 1;
+    ctx->opt_l2_fold_counts = 1;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -211,8 +212,27 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx) {
     return MLPL_OK;
 }
 
+// Knobs kept in a table: one row serves mlpl_set_option and mlpl_get_option (name, field, accepted range).  The chains below are the
+// older knobs, whose value sets are not all ranges; tests/option_guard.py mirrors exactly those.
+static const struct {
+    const char *name;
+    int mlpl_ctx::*field;
+    int lo, hi;
+} kRangeOptions[] = {
+    {"l2_fold_counts", &mlpl_ctx::opt_l2_fold_counts, 0, 1},
+};
+
 int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
     if (!ctx || !name) return MLPL_E_BAD_INPUT;
+    for (const auto &o : kRangeOptions)
+        if (!std::strcmp(name, o.name)) {
+            if (value < o.lo || value > o.hi) {
+                set_error("mlpl_set_option: unknown option or bad value: %s=%d", name, value);
+                return MLPL_E_BAD_INPUT;
+            }
+            ctx->*(o.field) = value;
+            return MLPL_OK;
+        }
     if (!std::strcmp(name, "hamming_variant") && value >= 0 && value <= 3) ctx->opt_hamming_variant = value;
     else if (!std::strcmp(name, "hamming_mfma_qt") && (value == 0 || value == 1 || value == 2 || value == 4)) ctx->opt_hamming_mfma_qt = value;
     else if (!std::strcmp(name, "hamming_mfma_blocks_per_cu") && value >= 1 && value <= 64) ctx->opt_hamming_mfma_blocks_per_cu = value;
@@ -273,6 +293,11 @@ int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
 
 int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value) {
     if (!ctx || !name || !value) return MLPL_E_BAD_INPUT;
+    for (const auto &o : kRangeOptions)
+        if (!std::strcmp(name, o.name)) {
+            *value = ctx->*(o.field);
+            return MLPL_OK;
+        }
     // every name mlpl_set_option accepts, in its order
     if (!std::strcmp(name, "hamming_variant")) *value = ctx->opt_hamming_variant;
     else if (!std::strcmp(name, "hamming_mfma_qt")) *value = ctx->opt_hamming_mfma_qt;
@@ -337,6 +362,12 @@ int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[12]) {
     out[0] = ctx->dbg_count_kernel[0], out[1] = ctx->dbg_count_kernel[1];
     for (int i = 0; i < 10; ++i) out[2 + i] = ctx->dbg_hamming_kernel[i];
     return 12;
+}
+
+int mlpl_debug_last_l2_match(mlpl_ctx *ctx, int out[4]) {
+    if (!ctx || !out) return MLPL_E_BAD_INPUT;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->dbg_l2_match[i];
+    return 4;
 }
 
 int mlpl_debug_hamming_stamps(mlpl_ctx *ctx, unsigned long long *out, int max_items) {
@@ -497,6 +528,50 @@ int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_s
     if (rc) return rc;
     if (emit.emitted) return MLPL_OK;  // (the latency shape: the merge kernel wrote the matches and their number)
     return launch_ratio_compact(ctx, d_idx, d_dist, 0, nq, k, batch, ratio, d_out, d_n_out, s, (int32_t *)gc);
+}
+
+int mlpl_match_l2_dev(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride, const float *d_t, int nt,
+                      size_t t_stride, size_t t_batch_stride, int dim, int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
+                      mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) {
+    if (!ctx) return MLPL_E_BAD_INPUT;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = pick_stream(ctx, stream);
+    const int k = ratio_test ? 2 : 1;
+    // The pass counts come out of the split fold (knn_l2_fold_ratio_kernel) wherever a fold runs; the fp16 candidate path ends in its own
+    // re-rank kernel and leaves them to ratio_count_kernel.  (Arguments out of range: launch_knn_l2 refuses them, nothing is sized by them.)
+    void *gc = nullptr;
+    if (ctx->opt_l2_fold_counts && nq > 0 && batch >= 1 && batch <= 65535) {
+        const int ncnt = (nq + kCountGroup - 1) / kCountGroup;
+        int rc = ws_get(ctx, WS_COUNT, (size_t)batch * ncnt * sizeof(int32_t), &gc);
+        if (rc) return rc;
+    }
+    int counted = 0;
+    int rc = launch_knn_l2(ctx, d_q, nq, q_stride, q_batch_stride, d_t, nt, t_stride, t_batch_stride, dim, k, batch, d_idx, d_dist, s, 0, ratio,
+                           (int32_t *)gc, &counted);
+    if (rc) return rc;
+    rc = launch_ratio_compact(ctx, d_idx, d_dist, 1, nq, k, batch, ratio, d_out, d_n_out, s, counted ? (int32_t *)gc : nullptr);
+    if (rc == MLPL_OK && nq > 0) ctx->dbg_l2_match[3] += counted ? 1 : 2;  // ratio_write_kernel [+ ratio_count_kernel]
+    return rc;
+}
+
+// (tests) the float knn with the fused fold alone: the counts the fold stored, read back
+int mlpl_debug_l2_fold_counts(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride, const float *d_t, int nt,
+                               size_t t_stride, size_t t_batch_stride, int dim, int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
+                               int32_t *counts) {
+    if (!ctx || !counts || nq < 1 || batch < 1 || batch > 65535) return MLPL_E_BAD_INPUT;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    const int ncnt = (nq + kCountGroup - 1) / kCountGroup;
+    void *gc = nullptr;
+    int rc = ws_get(ctx, WS_COUNT, (size_t)batch * ncnt * sizeof(int32_t), &gc);
+    if (rc) return rc;
+    MLPL_HIP_TRY(hipMemsetAsync(gc, 0xFF, (size_t)batch * ncnt * sizeof(int32_t), ctx->stream));  // (-1: a group nobody wrote shows)
+    int counted = 0;
+    rc = launch_knn_l2(ctx, d_q, nq, q_stride, q_batch_stride, d_t, nt, t_stride, t_batch_stride, dim, ratio_test ? 2 : 1, batch, d_idx, d_dist, ctx->stream, 0,
+                       ratio, (int32_t *)gc, &counted);
+    if (rc) return rc;
+    MLPL_HIP_TRY(hipMemcpyAsync(counts, gc, (size_t)batch * ncnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MLPL_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return counted ? batch * ncnt : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -253,11 +253,105 @@ void launch_knn_l2_merge(const void *part, int nsplit, const void *part_m, int n
     }
 }
 
+
+// knn_l2_merge_kernel with the ratio predicate and the pass counts of ratio_write_kernel fused in (mlpl_match_l2_dev): the fold holds
+// (d0, d1) of every query in registers when it stores them, so the workgroup evaluates ratio_pred<true>'s expression on them -- k == 1:
+// every query passes, k == 2: d0 < __fmul_rn(ratio, d1) -- and stores one count per kCountGroup = 64 queries, the layout
+// ratio_write_kernel reads (plain stores, no atomics: a workgroup owns whole count groups; the launch boundary publishes them).
+//   LANES = 1:  256 threads = 4 count groups, one per wave, counted with a ballot.
+//   LANES = 16: 1024 threads = 64 queries = one count group; every wave ballots its 4 queries, one LDS reduction over the 16 waves.
+// Fold, gate choice and stores are knn_l2_merge_kernel's; no thread leaves early (ballot / barrier), queries qi >= nq never pass.
+template <int LANES>
+__global__ __launch_bounds__(LANES == 1 ? 256 : 1024) void knn_l2_fold_ratio_kernel(const ulonglong2 *__restrict__ part, int nsplit,
+                                                                                     const ulonglong2 *__restrict__ part_m, int nsplit_m,
+                                                                                     L2Gate gate, int nq, int k, float ratio,
+                                                                                     int32_t *__restrict__ idx, float *__restrict__ dist,
+                                                                                     int32_t *__restrict__ group_counts) {
+    static_assert(LANES == 1 || LANES == 16, "one count group per wave, or one per workgroup");
+    static_assert(kCountGroup == 64, "a count group is one wave of queries");
+    constexpr int kThreads = LANES == 1 ? 256 : 1024;
+    constexpr int kQueries = kThreads / LANES;  // 256 (four count groups) or 64 (one)
+    if (part_m && !(gate.flag && *gate.flag == gate.gen)) {
+        part = part_m;
+        nsplit = nsplit_m;
+    }
+    const int b = blockIdx.y;
+    const int sub = threadIdx.x & (LANES - 1);
+    const int qi = blockIdx.x * kQueries + threadIdx.x / LANES;
+    u64 b0 = ~0ull, b1 = ~0ull;
+    if (qi < nq) {
+        for (int s = sub; s < nsplit; s += LANES) {
+            const ulonglong2 p = part[((size_t)b * nsplit + s) * nq + qi];
+            if (p.x != ~0ull) top2_update(b0, b1, p.x);
+            if (p.y != ~0ull) top2_update(b0, b1, p.y);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < LANES; off <<= 1) {
+        const u64 o0 = __shfl_xor(b0, off), o1 = __shfl_xor(b1, off);
+        top2_update(b0, b1, o0);
+        top2_update(b0, b1, o1);
+    }
+    bool pass = false;
+    if (sub == 0 && qi < nq) {
+        const size_t o = ((size_t)b * nq + qi) * k;
+        const float d0 = __uint_as_float((uint32_t)(b0 >> 32));
+        idx[o] = (int32_t)(b0 & 0xFFFFFFFFull);
+        dist[o] = d0;
+        pass = true;
+        if (k == 2) {
+            const float d1 = __uint_as_float((uint32_t)(b1 >> 32));
+            idx[o + 1] = (int32_t)(b1 & 0xFFFFFFFFull);
+            dist[o + 1] = d1;
+            pass = d0 < __fmul_rn(ratio, d1);
+        }
+    }
+    const int ncnt = (nq + kCountGroup - 1) / kCountGroup;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int cnt = __popcll(__ballot(pass));
+    if constexpr (LANES == 1) {
+        const int g = blockIdx.x * (kQueries / kCountGroup) + wave;
+        if (lane == 0 && g < ncnt) group_counts[(size_t)b * ncnt + g] = cnt;
+    } else {
+        __shared__ int wave_cnt[kThreads / 64];
+        if (lane == 0) wave_cnt[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int tot = 0;
+#pragma unroll
+            for (int w = 0; w < kThreads / 64; ++w) tot += wave_cnt[w];
+            group_counts[(size_t)b * ncnt + blockIdx.x] = tot;  // gridDim.x == ncnt
+        }
+    }
+}
+
+// d_group_counts != nullptr: the fused fold (the counts are written), else the plain merge
+void launch_knn_l2_fold(const void *part, int nsplit, const void *part_m, int nsplit_m, L2Gate gate, int nq, int k, int batch, int32_t *d_idx,
+                        float *d_dist, hipStream_t s, float ratio, int32_t *d_group_counts) {
+    if (!d_group_counts) {
+        launch_knn_l2_merge(part, nsplit, part_m, nsplit_m, gate, nq, k, batch, d_idx, d_dist, s);
+        return;
+    }
+    if (std::max(nsplit, nsplit_m) <= 4) {
+        dim3 mgrid((nq + 255) / 256, batch);
+        hipLaunchKernelGGL(knn_l2_fold_ratio_kernel<1>, mgrid, dim3(256), 0, s, (const ulonglong2 *)part, nsplit, (const ulonglong2 *)part_m,
+                           nsplit_m, gate, nq, k, ratio, d_idx, d_dist, d_group_counts);
+    } else {
+        dim3 mgrid((nq + kCountGroup - 1) / kCountGroup, batch);
+        hipLaunchKernelGGL(knn_l2_fold_ratio_kernel<16>, mgrid, dim3(1024), 0, s, (const ulonglong2 *)part, nsplit, (const ulonglong2 *)part_m,
+                           nsplit_m, gate, nq, k, ratio, d_idx, d_dist, d_group_counts);
+    }
+}
+
 }  // namespace
 
 int launch_knn_l2(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_bstride, const float *d_t, int nt,
                   size_t t_stride, size_t t_bstride, int dim, int k, int batch, int32_t *d_idx, float *d_dist,
-                  hipStream_t s, int nms_order) {
+                  hipStream_t s, int nms_order, float ratio, int32_t *d_group_counts, int *counts_done) {
+    if (counts_done) *counts_done = 0;
+    int *const dbg = ctx->dbg_l2_match;  // {path, train splits, counts by the fold, launches} of this call (mlpl_debug_last_l2_match)
+    dbg[0] = dbg[1] = dbg[2] = dbg[3] = 0;
+    if (nms_order) d_group_counts = nullptr;
     if (!d_q || !d_t || !d_idx || !d_dist || nq < 0 || batch < 1 || batch > 65535 || (k != 1 && k != 2) || nt < k ||
         dim < 1 || dim > 1024 || q_stride < (size_t)dim || t_stride < (size_t)dim) {
         set_error("knn_l2: bad arguments (nq=%d nt=%d dim=%d k=%d batch=%d)", nq, nt, dim, k, batch);
@@ -302,6 +396,7 @@ int launch_knn_l2(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size
         if ((rc = launch_knn_l2_f16(ctx, d_q, nq, q_stride, q_bstride, d_t, nt, t_stride, t_bstride, dim, k, batch, gen, dflag,
                                     ctx->l2_mode == 0 ? ctx->l2_hint_dev : nullptr, d_idx, d_dist, s)))
             return rc;
+        dbg[0] = 4, dbg[3] = 4;  // preparation, two candidate passes, re-rank (its own fold: the counts stay with ratio_count_kernel)
         if (ctx->l2_mode == 3) {  // forcing is a test / diagnostic mode: report out-of-range data as an error (one host hop; the result is still exact)
             int hbad = 0;
             MLPL_HIP_TRY(hipMemcpyAsync(&hbad, dflag + 1, 4, hipMemcpyDeviceToHost, s));
@@ -323,8 +418,10 @@ int launch_knn_l2(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size
             part_m = plan.args.part;
             nsplit_m = plan.args.nsplit;
             if (ctx->l2_mode == 2) {
-                launch_knn_l2_merge(nullptr, 0, part_m, nsplit_m, L2Gate{nullptr, 0}, nq, k, batch, d_idx, d_dist, s);
+                launch_knn_l2_fold(nullptr, 0, part_m, nsplit_m, L2Gate{nullptr, 0}, nq, k, batch, d_idx, d_dist, s, ratio, d_group_counts);
                 MLPL_HIP_TRY(hipGetLastError());
+                dbg[0] = 2, dbg[1] = nsplit_m, dbg[2] = d_group_counts ? 1 : 0, dbg[3] = 3;  // preparation, tile loop, fold
+                if (counts_done) *counts_done = dbg[2];
                 return MLPL_OK;
             }
             gate = plan.gate;
@@ -388,8 +485,11 @@ int launch_knn_l2(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size
         else MLPL_L2_LAUNCH(0);
 #undef MLPL_L2_LAUNCH
     }
-    launch_knn_l2_merge(part, nsplit, part_m, nsplit_m, gate, nq, k, batch, d_idx, d_dist, s);
+    launch_knn_l2_fold(part, nsplit, part_m, nsplit_m, gate, nq, k, batch, d_idx, d_dist, s, ratio, d_group_counts);
     MLPL_HIP_TRY(hipGetLastError());
+    // auto: preparation, the kernel with both paths, fold (train splits: the larger table's); exact: kernel, fold
+    dbg[0] = fused ? 3 : 1, dbg[1] = std::max(nsplit, nsplit_m), dbg[2] = d_group_counts ? 1 : 0, dbg[3] = fused ? 3 : 2;
+    if (counts_done) *counts_done = dbg[2];
     return MLPL_OK;
 }
 

@@ -99,6 +99,9 @@ struct mlpl_ctx {
                             // previous call's data were seen to be non-integer (hint, no host hop), 2 = always enqueue that path
     int *l2_hint_host;      // pinned + device-mapped: 2 * generation + (not integer-valued) of the last auto call that has finished on the device
     int *l2_hint_dev;
+    int opt_l2_fold_counts; // 1 (default) = mlpl_match_l2_dev's split fold evaluates the ratio predicate and writes the pass counts (knn_l2_fold_ratio_kernel);
+                            // 0 = knn_l2_merge_kernel + ratio_count_kernel (A/B, tests)
+    int dbg_l2_match[4];    // mlpl_debug_last_l2_match: {path, train splits, counts by the fold, launches} of the last float knn / match call
     void *l2_flag_ptr;  // the flag buffer l2_gen counts for
     int num_cus;
     // tuning knobs (mlpl_set_option)
@@ -234,7 +237,11 @@ int launch_knn_hamming(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_strid
                        int32_t *d_group_counts = nullptr, HammingEmitOut *emit_out = nullptr);
 int launch_knn_l2(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_bstride, const float *d_t,
                   int nt, size_t t_stride, size_t t_bstride, int dim, int k, int batch, int32_t *d_idx,
-                  float *d_dist, hipStream_t s, int nms_order = 0);
+                  float *d_dist, hipStream_t s, int nms_order = 0, float ratio = 0.f, int32_t *d_group_counts = nullptr,
+                  int *counts_done = nullptr);
+// (d_group_counts: the caller wants the pass counts of the ratio predicate at `ratio` in the layout ratio_write_kernel reads, as
+// launch_knn_hamming's; *counts_done = 1 when the path taken wrote them -- every path that ends in the split fold --, 0 when the caller
+// still has to run ratio_count_kernel: the fp16 candidate path, which ends in its own re-rank kernel)
 // group_counts_ready: d_group_counts (one int per kCountGroup queries per batch item, in the context workspace slot
 // WS_COUNT) was already filled by knn_hamming_merge_kernel; otherwise a counting pass runs first.
 constexpr int kRatioGroup = 256;  // queries per ratio_write block
@@ -246,6 +253,24 @@ int launch_ratio_compact(mlpl_ctx *ctx, const int32_t *d_idx, const void *d_dist
 int launch_gather_match_points(const mlpl_dmatch *d_matches, int n, const float *d_kp1, const float *d_kp2, const double K0[4],
                                const double K1[4], double *d_p1, double *d_p2, hipStream_t s);
 void free_rand_cache(void *p);
+
+// The descriptors of a batch of image pairs, dense: q [pairs][nq][cols], t [pairs][nt][cols] elements of `type` -- 0 = CV_8U (bytes,
+// Hamming), 5 = CV_32F (floats, squared L2), as mlpl_get_matches_linear's desc_type.  q == nullptr: no descriptors (correspondence mode).
+struct DescView {
+    const void *q, *t;
+    int cols, type;
+    size_t elem() const { return type == 5 ? sizeof(float) : 1; }
+    DescView pair(size_t b, int nq, int nt) const {
+        return DescView{(const char *)q + b * nq * cols * elem(), (const char *)t + b * nt * cols * elem(), cols, type};
+    }
+};
+// The matching step of the pair entries: mlpl_match_hamming_dev / mlpl_match_l2_dev (ratio test at 0.75f) on `batch` pairs of the view,
+// q_bstride / t_bstride in elements.  The idx / dist slots are 4 bytes per element either way.
+int match_dev(mlpl_ctx *ctx, const DescView &v, int nq, size_t q_bstride, int nt, size_t t_bstride, int batch, int32_t *d_idx, void *d_dist,
+              mlpl_dmatch *d_out, int32_t *d_n_out, hipStream_t s);
+// mlpl_pair_pose_dev / mlpl_pair_pose_f32_dev on the first pair of the view
+int pair_pose_one(mlpl_ctx *ctx, const DescView &v, int nq, int nt, const float *d_kp1, const float *d_kp2, const double K0[4], const double K1[4],
+                  double thresh, int max_iters, double confidence, int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream);
 
 // cheirality for a batch of pairs (recover_pose.hip): decomposition, four triangulations, the reference's candidate choice and the mask
 // of the chosen candidate, all on the device; d_out[pair] = {valid 3-D points, candidate (-1 none), R, t}

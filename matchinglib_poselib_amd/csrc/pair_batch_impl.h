@@ -3,7 +3,7 @@
 //
 // mlpl_pair_pose_dev runs one pair as ~14 launches and two host hops; its RANSAC half is latency-bound (1000 hypotheses do not fill a
 // quarter of the chip), so a rank had to keep several pairs in flight from host threads.  Here B pairs share every launch:
-//   matching          mlpl_match_hamming_dev(batch = B)                                          (one launch chain, as before)
+//   matching          match_dev(batch = B): mlpl_match_hamming_dev (CV_8U) or mlpl_match_l2_dev (CV_32F) (one launch chain, as before)
 //   hop 1             the B match counts (they size the sample tables: getSubset draws rand() % count, modelest.cpp:585)
 //   gather + pack     blockIdx.y = pair
 //   RANSAC passes     the first 324 iterations of EVERY pair as one pass, then the remaining iterations of the pairs the adaptive bound
@@ -109,15 +109,16 @@ __global__ __launch_bounds__(64) void draw_samples_kernel(const PairSlot *__rest
 
 }  // namespace
 
-// Correspondence mode (d_q == nullptr): the batch starts behind the matching -- problem b's correspondences are ext_p1 / ext_p2 + b * nq * 2
+// dv: the pairs' descriptors (CV_8U or CV_32F; the estimators behind the matcher do not depend on the type).
+// Correspondence mode (dv.q == nullptr): the batch starts behind the matching -- problem b's correspondences are ext_p1 / ext_p2 + b * nq * 2
 // (camera coordinates, device), ext_counts[b] of them (host); want_pose = 0 stops after the inlier masks; d_masks_ext: the caller's [B][nq]
 // mask block or nullptr.  This is mlpl_ransac_essential_batch_dev.
-int pair_pose_batch_dev(mlpl_ctx *ctx, int B, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
+int pair_pose_batch_dev(mlpl_ctx *ctx, int B, const DescView &dv, int nq, int nt, const float *d_kp1,
                         const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
                         const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, hipStream_t s,
                         const double *ext_p1 = nullptr, const double *ext_p2 = nullptr, const int32_t *ext_counts = nullptr, int want_pose = 1,
                         uint8_t *d_masks_ext = nullptr) {
-    const bool points_mode = d_q == nullptr;
+    const bool points_mode = dv.q == nullptr;
     const int min_count = points_mode ? 6 : 16;  // mlpl_ransac_essential's limit / the reference's working minimum for a matched pair
     // host-hop timeline of this call (diagnostics, mlpl_debug_hop_trace): microseconds since entry at which each wait on the stream returned
     const auto t_entry = std::chrono::steady_clock::now();
@@ -194,9 +195,15 @@ int pair_pose_batch_dev(mlpl_ctx *ctx, int B, const uint8_t *d_q, int nq, const 
         MLPL_HIP_TRY(hipMemcpyAsync(d_counts, h_counts, (size_t)B * 4, hipMemcpyHostToDevice, s));
     } else {
         // ---- matching, all pairs ----
-        rc = mlpl_match_hamming_dev(ctx, d_q, nq, (size_t)nbytes, (size_t)nq * nbytes, d_t, nt, (size_t)nbytes, (size_t)nt * nbytes, nbytes, 1, 0.75f, B,
-                                    (int32_t *)(b0 + off_idx), (int32_t *)(b0 + off_dist), d_m, d_counts, s);
+        rc = match_dev(ctx, dv, nq, (size_t)nq * dv.cols, nt, (size_t)nt * dv.cols, B, (int32_t *)(b0 + off_idx), b0 + off_dist, d_m, d_counts, s);
         if (rc) return rc;
+        // The matchers take their partial tables from WS_PARTIAL (and the float matcher its row constants from WS_AUX3), slots this entry
+        // sized above for its own tables: a matcher that needs more regrows the slot (behind a device synchronisation), so the pointers
+        // are read again here.  Slots only grow: both blocks now hold this entry's tables as well, and the stream orders the two uses.
+        if ((rc = ws_get(ctx, WS_AUX3, (size_t)B * pack_stride4 * sizeof(double4), &p))) return rc;
+        d_pack = (double4 *)p;
+        if ((rc = ws_get(ctx, WS_PARTIAL, hyps * sizeof(PolyRec), &p))) return rc;
+        d_recs = (PolyRec *)p;
         MLPL_HIP_TRY(hipMemcpyAsync(h_counts, d_counts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     }
     MLPL_HIP_TRY(hipMemsetAsync(d_rng_pos, 0, (size_t)B * 8, s));  // positions and overflow flags
@@ -399,8 +406,8 @@ int pair_pose_batch_dev(mlpl_ctx *ctx, int B, const uint8_t *d_q, int nq, const 
             continue;
         }
         ctx->ransac_force_table = 1;
-        rc = mlpl_pair_pose_dev(ctx, d_q + (size_t)b * nq * nbytes, nq, d_t + (size_t)b * nt * nbytes, nt, nbytes, d_kp1 + (size_t)b * nq * 2,
-                                d_kp2 + (size_t)b * nt * 2, K0, K1, thresh, max_iters, confidence, 0, seeds[b], dist, &out[b], s);
+        rc = pair_pose_one(ctx, dv.pair((size_t)b, nq, nt), nq, nt, d_kp1 + (size_t)b * nq * 2, d_kp2 + (size_t)b * nt * 2, K0, K1, thresh, max_iters,
+                           confidence, 0, seeds[b], dist, &out[b], s);
         // (the caller's match block already holds this pair's matches: the same kernels produced them)
         ctx->ransac_force_table = 0;
         if (rc) return rc;

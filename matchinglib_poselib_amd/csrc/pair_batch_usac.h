@@ -1,7 +1,7 @@
 // pair_batch_usac.h -- a batch of image pairs with USAC as the robust estimator (the harness default RobMethod, T/poselib-test/main.cpp:734).
 // Included by ransac_5pt.hip inside namespace mlpl after usac_impl.h and pair_batch_impl.h.
 //
-//   matching          mlpl_match_hamming_dev(batch = B)                        as in pair_batch_impl.h
+//   matching          match_dev(batch = cohort): Hamming or squared L2         as in pair_batch_impl.h
 //   hop               the B match counts (and, for PROSAC, the matching costs: the order is getSortedMatchIdx' std::sort of them)
 //   gather            blockIdx.y = pair: matched keypoints -> camera coordinates (ImgToCamCoordTrans)
 //   USAC              usac_essential_batch_dev: every pair's sequential program on its own stack (a fiber), every launch merged over the pairs
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void match_cost_kernel(const mlpl_dmatch *__re
 }
 
 // tmpl != nullptr: USAC with these parameters (seeds[B], prosac); else ARRSAC (arr_thresh, arr_refine, arr_states[B][2] in / out)
-int pair_pose_batch_usac_dev(mlpl_ctx *ctx, int B, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
+int pair_pose_batch_usac_dev(mlpl_ctx *ctx, int B, const DescView &dv, int nq, int nt, const float *d_kp1,
                              const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *tmpl, int prosac,
                              const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, hipStream_t s,
                              double arr_thresh = 0, int arr_refine = 0, uint64_t *arr_states = nullptr) {
@@ -111,9 +111,13 @@ int pair_pose_batch_usac_dev(mlpl_ctx *ctx, int B, const uint8_t *d_q, int nq, c
     } feed_drain{hres->feed};
     for (int c = 0; c < n_cohorts; ++c) {
         const int b0 = c * cohort, nb = std::min(cohort, B - b0);
-        rc = mlpl_match_hamming_dev(ctx, d_q + (size_t)b0 * nq * nbytes, nq, (size_t)nbytes, (size_t)nq * nbytes, d_t + (size_t)b0 * nt * nbytes, nt, (size_t)nbytes,
-                                    (size_t)nt * nbytes, nbytes, 1, 0.75f, nb, (int32_t *)(base + off_idx) + (size_t)b0 * n * 2, (int32_t *)(base + off_dist) + (size_t)b0 * n * 2, d_m + (size_t)b0 * n,
-                                    d_counts + b0, s);
+        // Every cohort's matching goes through the one context on the one feed stream.  The first cohort is the largest (nb = min(cohort,
+        // B - b0)), so the matchers' per-context blocks (Hamming: packed rows, partial table, tickets; float: WS_PARTIAL, WS_L2_FLAG with
+        // its generation, the operand-preparation buffers) are sized by it and never regrow while an earlier cohort's kernels are in
+        // flight -- and a regrow would wait for the device first (ws_get).  The float launcher keeps its hint word in a pinned block of
+        // its own, not in this entry's: a stale hint (the host reads it while earlier cohorts still run) may cost speed, never results.
+        rc = match_dev(ctx, dv.pair((size_t)b0, nq, nt), nq, (size_t)nq * dv.cols, nt, (size_t)nt * dv.cols, nb, (int32_t *)(base + off_idx) + (size_t)b0 * n * 2,
+                       (int32_t *)(base + off_dist) + (size_t)b0 * n * 2, d_m + (size_t)b0 * n, d_counts + b0, s);
         if (rc) return rc;
         MLPL_HIP_TRY(hipMemcpyAsync(h_counts + b0, d_counts + b0, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
         if (prosac) {  // the costs of the matches, through the (now free) table of nearest-neighbour indices of this cohort

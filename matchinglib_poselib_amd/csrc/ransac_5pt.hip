@@ -4211,12 +4211,13 @@ int mlpl_recover_pose_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p
     return recover_pose_batch(ctx, n_problems, d_p1, d_p2, stride, counts, E, dist, d_masks, n_good, R, t, pick_stream(ctx, stream));
 }
 
-int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
-                             const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
-                             int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
-    if (!ctx || !d_q || !d_t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !seeds || n_pairs < 1 || nq < 1 || nt < 2 || nbytes < 1 || max_iters < 1 ||
-        !(thresh > 0)) {
-        set_error("mlpl_pair_pose_batch_dev: bad arguments");
+// the body of mlpl_pair_pose_batch_dev / mlpl_pair_pose_batch_f32_dev
+static int pair_pose_batch_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv, int nq, int nt, const float *d_kp1, const float *d_kp2, const double K0[4],
+                                 const double K1[4], double thresh, int max_iters, double confidence, int refit, const uint32_t *seeds, double dist,
+                                 mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream, const char *who) {
+    if (!ctx || !dv.q || !dv.t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !seeds || n_pairs < 1 || nq < 1 || nt < 2 || dv.cols < 1 || max_iters < 1 ||
+        !(thresh > 0) || (dv.type == 5 && dv.cols > 1024)) {
+        set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
@@ -4225,12 +4226,12 @@ int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int
     std::memset(ctx->last_batch_stats, 0, sizeof(ctx->last_batch_stats));
     if (refit) {  // the refit step is not batched: the single-pair pipeline, pair by pair (matches are not exported on this path)
         if (d_matches_out) {
-            set_error("mlpl_pair_pose_batch_dev: d_matches_out needs refit = 0");
+            set_error("%s: d_matches_out needs refit = 0", who);
             return MLPL_E_UNSUPPORTED;
         }
         for (int b = 0; b < n_pairs; ++b) {
-            const int rc = mlpl_pair_pose_dev(ctx, d_q + (size_t)b * nq * nbytes, nq, d_t + (size_t)b * nt * nbytes, nt, nbytes, d_kp1 + (size_t)b * nq * 2,
-                                              d_kp2 + (size_t)b * nt * 2, K0, K1, thresh, max_iters, confidence, refit, seeds[b], dist, &out[b], stream);
+            const int rc = pair_pose_one(ctx, dv.pair((size_t)b, nq, nt), nq, nt, d_kp1 + (size_t)b * nq * 2, d_kp2 + (size_t)b * nt * 2, K0, K1, thresh,
+                                         max_iters, confidence, refit, seeds[b], dist, &out[b], stream);
             if (rc) return rc;
         }
         return MLPL_OK;
@@ -4241,14 +4242,27 @@ int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int
     long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int at = 0; at < n_pairs; at += per) {
         const int B = std::min(per, n_pairs - at);
-        const int rc = pair_pose_batch_dev(ctx, B, d_q + (size_t)at * nq * nbytes, nq, d_t + (size_t)at * nt * nbytes, nt, nbytes,
-                                           d_kp1 + (size_t)at * nq * 2, d_kp2 + (size_t)at * nt * 2, K0, K1, thresh, max_iters, confidence, seeds + at,
-                                           dist, out + at, d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s);
+        const int rc = pair_pose_batch_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt, d_kp1 + (size_t)at * nq * 2, d_kp2 + (size_t)at * nt * 2, K0, K1, thresh,
+                                           max_iters, confidence, seeds + at, dist, out + at, d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s);
         if (rc) return rc;
         for (int i = 0; i < 8; ++i) acc[i] += ctx->last_batch_stats[i];
     }
     std::memcpy(ctx->last_batch_stats, acc, sizeof(acc));
     return MLPL_OK;
+}
+
+int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
+                             const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
+                             int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+    return pair_pose_batch_entry(ctx, n_pairs, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, max_iters, confidence, refit, seeds, dist,
+                                 out, d_matches_out, stream, "mlpl_pair_pose_batch_dev");
+}
+
+int mlpl_pair_pose_batch_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                                 const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
+                                 int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+    return pair_pose_batch_entry(ctx, n_pairs, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, max_iters, confidence, refit, seeds, dist,
+                                 out, d_matches_out, stream, "mlpl_pair_pose_batch_f32_dev");
 }
 
 // Two (or more) batched calls in flight on one GPU, inside the library: lane l = (ctxs[l], streams[l]) takes the l-th contiguous share of
@@ -4336,30 +4350,71 @@ int mlpl_sorted_match_idx(const mlpl_dmatch *matches, int n, uint32_t *sorted_id
 }
 
 static int usac_check_params(const mlpl_usac_params *P, int n, const char *who);
-int mlpl_pair_pose_batch_usac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
-                                  const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
-                                  const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
-    if (!ctx || !d_q || !d_t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !seeds || !usac || n_pairs < 1 || nq < 1 || nt < 2 || nbytes < 1) {
-        set_error("mlpl_pair_pose_batch_usac_dev: bad arguments");
+static int pair_pose_batch_usac_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv, int nq, int nt, const float *d_kp1, const float *d_kp2,
+                                      const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac, const uint32_t *seeds, double dist,
+                                      mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream, const char *who) {
+    if (!ctx || !dv.q || !dv.t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !seeds || !usac || n_pairs < 1 || nq < 1 || nt < 2 || dv.cols < 1 ||
+        (dv.type == 5 && dv.cols > 1024)) {
+        set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
     int rc;
     mlpl_usac_params chk = *usac;
     chk.sorted_idx = nullptr;
-    if ((rc = usac_check_params(&chk, 0, "mlpl_pair_pose_batch_usac_dev"))) return rc;
+    if ((rc = usac_check_params(&chk, 0, who))) return rc;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
     const int per = ctx->opt_pair_batch_seq > 0 ? ctx->opt_pair_batch_seq : kSeqBatchPairsPerCall;
     try {
         for (int at = 0; at < n_pairs; at += per) {
             const int B = std::min(per, n_pairs - at);
-            rc = pair_pose_batch_usac_dev(ctx, B, d_q + (size_t)at * nq * nbytes, nq, d_t + (size_t)at * nt * nbytes, nt, nbytes, d_kp1 + (size_t)at * nq * 2,
+            rc = pair_pose_batch_usac_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt, d_kp1 + (size_t)at * nq * 2,
                                           d_kp2 + (size_t)at * nt * 2, K0, K1, &chk, prosac, seeds + at, dist, out + at,
                                           d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s);
             if (rc) return rc;
         }
     } catch (const std::bad_alloc &) {
-        set_error("mlpl_pair_pose_batch_usac_dev: out of host memory");
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+    return MLPL_OK;
+}
+
+int mlpl_pair_pose_batch_usac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
+                                  const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
+                                  const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+    return pair_pose_batch_usac_entry(ctx, n_pairs, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, usac, prosac, seeds, dist, out, d_matches_out,
+                                      stream, "mlpl_pair_pose_batch_usac_dev");
+}
+
+int mlpl_pair_pose_batch_usac_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                                      const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
+                                      const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+    return pair_pose_batch_usac_entry(ctx, n_pairs, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, usac, prosac, seeds, dist, out, d_matches_out,
+                                      stream, "mlpl_pair_pose_batch_usac_f32_dev");
+}
+
+static int pair_pose_batch_arrsac_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv, int nq, int nt, const float *d_kp1, const float *d_kp2,
+                                        const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states, double dist,
+                                        mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream, const char *who) {
+    if (!ctx || !dv.q || !dv.t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !rng_states || n_pairs < 1 || nq < 1 || nt < 2 || dv.cols < 1 || !(thresh > 0) ||
+        (dv.type == 5 && dv.cols > 1024)) {
+        set_error("%s: bad arguments", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = pick_stream(ctx, stream);
+    const int per = ctx->opt_pair_batch_seq > 0 ? ctx->opt_pair_batch_seq : kSeqBatchPairsPerCall;
+    try {
+        for (int at = 0; at < n_pairs; at += per) {
+            const int B = std::min(per, n_pairs - at);
+            const int rc = pair_pose_batch_usac_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt,
+                                                    d_kp1 + (size_t)at * nq * 2, d_kp2 + (size_t)at * nt * 2, K0, K1, nullptr, 0, nullptr, dist, out + at,
+                                                    d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s, thresh, refine, rng_states + 2 * (size_t)at);
+            if (rc) return rc;
+        }
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
         return MLPL_E_NOMEM;
     }
     return MLPL_OK;
@@ -4368,26 +4423,15 @@ int mlpl_pair_pose_batch_usac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q
 int mlpl_pair_pose_batch_arrsac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                                     const float *d_kp2, const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states, double dist,
                                     mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
-    if (!ctx || !d_q || !d_t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !rng_states || n_pairs < 1 || nq < 1 || nt < 2 || nbytes < 1 || !(thresh > 0)) {
-        set_error("mlpl_pair_pose_batch_arrsac_dev: bad arguments");
-        return MLPL_E_BAD_INPUT;
-    }
-    MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = pick_stream(ctx, stream);
-    const int per = ctx->opt_pair_batch_seq > 0 ? ctx->opt_pair_batch_seq : kSeqBatchPairsPerCall;
-    try {
-        for (int at = 0; at < n_pairs; at += per) {
-            const int B = std::min(per, n_pairs - at);
-            const int rc = pair_pose_batch_usac_dev(ctx, B, d_q + (size_t)at * nq * nbytes, nq, d_t + (size_t)at * nt * nbytes, nt, nbytes,
-                                                    d_kp1 + (size_t)at * nq * 2, d_kp2 + (size_t)at * nt * 2, K0, K1, nullptr, 0, nullptr, dist, out + at,
-                                                    d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s, thresh, refine, rng_states + 2 * (size_t)at);
-            if (rc) return rc;
-        }
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_pair_pose_batch_arrsac_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-    return MLPL_OK;
+    return pair_pose_batch_arrsac_entry(ctx, n_pairs, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, refine, rng_states, dist, out,
+                                        d_matches_out, stream, "mlpl_pair_pose_batch_arrsac_dev");
+}
+
+int mlpl_pair_pose_batch_arrsac_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
+                                        const float *d_kp2, const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states,
+                                        double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+    return pair_pose_batch_arrsac_entry(ctx, n_pairs, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, refine, rng_states, dist, out,
+                                        d_matches_out, stream, "mlpl_pair_pose_batch_arrsac_f32_dev");
 }
 
 int mlpl_ransac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double thresh,
@@ -4410,7 +4454,7 @@ int mlpl_ransac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double 
     const double K1_[4] = {1, 1, 0, 0};
     for (int at = 0; at < n_problems; at += per) {
         const int B = std::min(per, n_problems - at);
-        const int rc = pair_pose_batch_dev(ctx, B, nullptr, stride, nullptr, stride, 0, nullptr, nullptr, K1_, K1_, thresh, max_iters, confidence, seeds + at, dist,
+        const int rc = pair_pose_batch_dev(ctx, B, DescView{nullptr, nullptr, 0, 0}, stride, stride, nullptr, nullptr, K1_, K1_, thresh, max_iters, confidence, seeds + at, dist,
                                            out + at, nullptr, s, d_p1 + (size_t)at * stride * 2, d_p2 + (size_t)at * stride * 2, counts + at, recover_pose ? 1 : 0,
                                            d_masks ? d_masks + (size_t)at * stride : nullptr);
         if (rc) return rc;

@@ -187,3 +187,41 @@ def match_hamming_device(q, t, ratio_test: bool = True, ratio: float = 0.75, ctx
         out["count"].data_ptr(), torch.cuda.current_stream(q.device).cuda_stream if stream is None else stream)
     check(rc, "mlpl_match_hamming_dev")
     return out
+
+
+def match_l2_device(q, t, ratio_test: bool = True, ratio: float = 0.75, ctx: Optional[Context] = None, out=None,
+                    stream: Optional[int] = None):
+    """match_hamming_device for float descriptors (mlpl_match_l2_dev): squared-L2 knn + ratio + compaction on CUDA/HIP torch tensors.
+
+    q: float32 [B, nq, dim] (or [nq, dim]), t: float32 [B, nt, dim]; rows may be padded (strides are passed in elements).  Returns dict
+    of torch tensors idx [B,nq,k] int32, dist [B,nq,k] float32, matches [B,nq,4] int32 (DMatch rows, .distance bit-cast), count [B]
+    int32.  Enqueues on `stream` (a hipStream_t handle; None = torch's current stream) without synchronising.
+    """
+    import torch
+
+    if q.dim() == 2:
+        q = q.unsqueeze(0)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    assert q.is_cuda and t.is_cuda and q.dtype == torch.float32 and t.dtype == torch.float32
+    assert q.stride(2) == 1 and t.stride(2) == 1 and q.shape[0] == t.shape[0] and q.shape[2] == t.shape[2]
+    B, nq, dim = q.shape
+    nt = t.shape[1]
+    ctx = ctx or default_context(q.device.index or 0)
+    k = 2 if ratio_test else 1
+    if out is None:
+        rows = max(nq, 1)   # (nq = 0 is a valid call, and an empty tensor has no address: the library gets the blocks, the caller the views)
+        out = {
+            "idx": torch.empty((B, rows, k), dtype=torch.int32, device=q.device),
+            "dist": torch.empty((B, rows, k), dtype=torch.float32, device=q.device),
+            "matches": torch.empty((B, rows, 4), dtype=torch.int32, device=q.device),
+            "count": torch.empty((B,), dtype=torch.int32, device=q.device),
+        }
+    rc = ctx.lib.mlpl_match_l2_dev(
+        ctx.handle, q.data_ptr() or t.data_ptr(), nq, q.stride(1), q.stride(0), t.data_ptr(), nt, t.stride(1), t.stride(0), dim,
+        1 if ratio_test else 0, ratio, B, out["idx"].data_ptr(), out["dist"].data_ptr(), out["matches"].data_ptr(),
+        out["count"].data_ptr(), torch.cuda.current_stream(q.device).cuda_stream if stream is None else stream)
+    check(rc, "mlpl_match_l2_dev")
+    if nq == 0:
+        out = {k_: (v[:, :0] if k_ != "count" else v) for k_, v in out.items()}
+    return out

@@ -103,3 +103,37 @@ def stereo_pair(n: int = 2000, seed: int = 20260200, inlier_frac: float = 0.5, f
         d1[lost] = rng.integers(0, 256, size=(int(lost.sum()), nbytes), dtype=np.uint8)
     K = np.array([f, f, cx, cy], np.float64)
     return dict(desc1=d1, desc2=d2, kp1=kp1, kp2=kp2, K=K, R=R, t=t, train_of_query=perm.astype(np.int32))
+
+
+def _sift_rows(rng, n: int, dim: int):
+    """sift_pair's make(): gamma-distributed rows, L2-normalised to 512, clipped at 255, rounded."""
+    x = rng.gamma(0.6, 1.0, size=(n, dim))
+    x = x / np.linalg.norm(x, axis=1, keepdims=True) * 512.0
+    return np.clip(np.rint(x), 0, 255)
+
+
+def stereo_pair_f32(n: int = 2000, seed: int = 20260400, dim: int = 128, sigma: float = 6.0, unmatched_frac: float = 0.0,
+                    rootsift: bool = False, f: float = 800.0, cx: float = 320.0, cy: float = 240.0):
+    """stereo_pair with float descriptors (the C5 unit for SIFT-like data): pose_scene geometry, keypoints in pixels, train side
+    shuffled; desc2 = sift_pair's rows (integer-valued 0..255, OpenCV-SIFT layout), desc1 = clip(rint(desc2[perm] + N(0, sigma))), so
+    the nearest neighbours are the true correspondences; `unmatched_frac` of the queries are fresh rows without a true neighbour (they
+    fail the ratio test).  rootsift: both sides become sqrt(x / sum(x)) (RootSIFT) -- non-integer data, which the exact and the fp16
+    L2 paths serve instead of the int8 one.  Returns the same dict keys as stereo_pair, descriptors float32."""
+    p1, p2, R, t, mask, th = pose_scene(n, inlier_frac=0.5, seed=seed)
+    rng = np.random.default_rng(seed + 7)
+    perm = rng.permutation(n)                      # train row perm[i] belongs to query i
+    kp1 = (p1 * f + np.array([cx, cy])).astype(np.float32)
+    kp2_q = (p2 * f + np.array([cx, cy])).astype(np.float32)
+    kp2 = np.empty_like(kp2_q)
+    kp2[perm] = kp2_q
+    d2 = _sift_rows(rng, n, dim)
+    d1 = np.clip(np.rint(d2[perm] + rng.normal(0, sigma, size=(n, dim))), 0, 255)
+    if unmatched_frac > 0:
+        lost = rng.random(n) < unmatched_frac
+        d1[lost] = _sift_rows(rng, int(lost.sum()), dim)
+    if rootsift:
+        d1 = np.sqrt(d1 / np.maximum(d1.sum(axis=1, keepdims=True), 1e-12))
+        d2 = np.sqrt(d2 / np.maximum(d2.sum(axis=1, keepdims=True), 1e-12))
+    K = np.array([f, f, cx, cy], np.float64)
+    return dict(desc1=np.ascontiguousarray(d1, np.float32), desc2=np.ascontiguousarray(d2, np.float32), kp1=kp1, kp2=kp2, K=K, R=R, t=t,
+                train_of_query=perm.astype(np.int32))

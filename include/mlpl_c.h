@@ -77,6 +77,8 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *       "hamming_mfma_prefetch" 0 | 2 | 4 | 6 tiles of prefetch distance in the LDS-ring kernel.  They do not combine: waves 16 beats a
  *       prefetch of 4 or 6, which beats "hamming_mfma_prio"; prefetch and prio 3 exist with 8-wave workgroups only and are ignored elsewhere.
  *       "hamming_expand_fine" (default 1) = small launches expand the train set with one thread per (tile, K-step, lane).
+ *       "hamming_expand_inkernel" 1 = the eight-wave LDS-ring kernel reads the raw 32-byte train rows and expands each tile in its own
+ *       workgroup (no expansion launch, no expanded copy of the train set in the workspace); 0 = the separate expansion kernel.
  *   L2: "l2_mfma_waves" 0|4|8 and "l2_mfma_blocks_per_cu" shape the int8 matrix-core kernel of the forced mode (see mlpl_set_l2_path);
  *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0);
  *     "l2_fold_counts" (default 1) = mlpl_match_l2_dev's fold over the train splits evaluates the ratio predicate and writes the pass

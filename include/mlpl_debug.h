@@ -73,8 +73,8 @@ int mlpl_debug_hamming_clock(mlpl_ctx *ctx, unsigned long long *out, int max_ite
  * of entries written (<= max_items). */
 int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, long long *ws_grows);
 
-/* Diagnostics: the kernel instances the last launches chose (tests check that an option reached the instance it names).  Writes 12 ints
- * and returns 12:
+/* Diagnostics: the kernel instances the last launches chose (tests check that an option reached the instance it names).  Writes 13 ints
+ * and returns 13:
  *   out[0]  instance of the last inlier-count pass (RANSAC pass, pair batch, mlpl_count_models, mlpl_debug_count_pass; 0 = none yet):
  *           1 score_models_block_kernel<count> (one workgroup per model), 2 score_models_kernel<fp64, 512 threads>,
  *           3 score_models_kernel<fp64, 128 threads, 256-point tiles> (passes of <= 24576 models), 4 count_models_f32_kernel<128, 256>
@@ -88,8 +88,9 @@ int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, lo
  *   out[5]  waves per workgroup of the static ring kernel (4, 8, 16; 4 for the other matrix-core kernels, 0 VALU);
  *   out[6]  its prefetch distance in tiles (2, 4, 6; 0 otherwise);  out[7] 1 = the kernel merged its splits itself (no merge launch);
  *   out[8]  1 = the age-aware split table was used;  out[9] 1 = the train set was expanded one thread per (tile, K-step, lane);
- *   out[10] train splits;  out[11] 64-bit K-steps of the matrix-core kernels (0 VALU). */
-int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[12]);
+ *   out[10] train splits;  out[11] 64-bit K-steps of the matrix-core kernels (0 VALU);
+ *   out[12] 1 = the static ring kernel expanded the raw train tiles itself (option "hamming_expand_inkernel"; no expansion launch). */
+int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]);
 
 /* Diagnostics: what the last float knn / match call of this context (mlpl_knn2_l2sq_f32*, mlpl_match_l2_dev, the float pair entries)
  * chose.  Writes 4 ints and returns 4: out[0] path -- 1 exact fp32 kernel, 2 int8 matrix-core path (forced), 3 the auto path's fused

@@ -263,7 +263,7 @@ class Context:
 
     def last_kernels(self) -> list:
         """mlpl_debug_last_kernels (include/mlpl_debug.h): the counting and Hamming kernel instances the last launches chose."""
-        out = (C.c_int * 12)()
+        out = (C.c_int * 13)()
         n = self._lib.mlpl_debug_last_kernels(self._h, out)
         if n < 0:
             raise MlplError(n, "mlpl_debug_last_kernels", last_error())

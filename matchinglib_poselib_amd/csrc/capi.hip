@@ -138,6 +138,7 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
     ctx->opt_hamming_mfma_prio = 0;
     ctx->opt_hamming_fused_merge = 1;
     ctx->opt_hamming_expand_fine = 1;
+    ctx->opt_hamming_expand_inkernel = 1;  // measured (tools/hamming_opt_ab.py, profiles/README.md): the step loses the expansion pass, the ring kernel gains less
     ctx->opt_hamming_merge_emit = 0;  // measured (tools/single_pair_probe.py): the launch it saves is what the chained look-back costs -- 21.2-22.2 against 20.8-21.4 us
     ctx->opt_ransac_lazy_sums = 1;
     ctx->opt_ransac_overlap = 1;
@@ -220,6 +221,7 @@ static const struct {
     int lo, hi;
 } kRangeOptions[] = {
     {"l2_fold_counts", &mlpl_ctx::opt_l2_fold_counts, 0, 1},
+    {"hamming_expand_inkernel", &mlpl_ctx::opt_hamming_expand_inkernel, 0, 1},
 };
 
 int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
@@ -357,11 +359,11 @@ int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value) {
     return MLPL_OK;
 }
 
-int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[12]) {
+int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]) {
     if (!ctx || !out) return MLPL_E_BAD_INPUT;
     out[0] = ctx->dbg_count_kernel[0], out[1] = ctx->dbg_count_kernel[1];
-    for (int i = 0; i < 10; ++i) out[2 + i] = ctx->dbg_hamming_kernel[i];
-    return 12;
+    for (int i = 0; i < 11; ++i) out[2 + i] = ctx->dbg_hamming_kernel[i];
+    return 13;
 }
 
 int mlpl_debug_last_l2_match(mlpl_ctx *ctx, int out[4]) {

@@ -78,6 +78,26 @@ __device__ __forceinline__ uint32_t expand_byte01(uint32_t x) {
     return t << 1;
 }
 
+// The BIT-PLANE rule of the in-kernel expansion (option hamming_expand_inkernel): every output dword of a 16-byte fragment is one plane of ONE
+// raw 32-bit word -- nibble j of plane p carries bit 4 j + p -- and a nibble is 0x2 | bit << 3, i.e. bit 0 -> +1.0, bit 1 -> -1.0.  One mask and
+// one v_lshl_or_b32 per output dword against the ~9 operations of expand_byte.  Which bit goes to which K position is free as long as both
+// operands follow the same rule, and so is the sign convention: both operands flip together and every product is unchanged.  The four dwords
+// of a fragment carry the planes 0, 2, 1, 3 in this order: the thread that forms dwords 2 i and 2 i + 1 needs planes i and i + 2, which are planes
+// 0 and 2 of the word shifted right by i (kernel below).
+__device__ __forceinline__ uint32_t expand_plane(uint32_t x, int p) { return ((x & (0x11111111u << p)) << (3 - p)) | 0x22222222u; }
+// the same for planes 0 and 2 in the two instructions named above (left to itself the compiler shifts first and takes three; `twos` =
+// 0x22222222 in a scalar register)
+__device__ __forceinline__ uint32_t expand_plane0(uint32_t x, uint32_t twos) {
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, 3, %2" : "=v"(r) : "v"(x & 0x11111111u), "s"(twos));
+    return r;
+}
+__device__ __forceinline__ uint32_t expand_plane2(uint32_t x, uint32_t twos) {
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(r) : "v"(x & 0x44444444u), "s"(twos));
+    return r;
+}
+
 // Rows of `nw` 32-bit words (word rows as the VALU path uses them) -> fragment order.  Lane (r = l & 31, h = l >> 5) of
 // K-step s holds word h * KS + s of row 32 * tile + r, i.e. each lane owns KS CONSECUTIVE words of its row (one 16-byte
 // load at KS = 4, and the wave reads one contiguous KiB); which 32 bits go to which K position is free as long as both
@@ -353,14 +373,34 @@ struct HammingFuse {
 // fetched and a barrier passed once per eight units' worth of query tiles instead of four (tools/hamming_unit_probe3.hip `ringnw`: 167.9 ->
 // 159.1 cycles per unit per SIMD).  A workgroup then serves NW * QT query tiles of one (image pair, train split).
 // PD (round 5) = prefetch distance in tiles (2, 4 or 6): the copy of tile it + PD is issued in iteration it; the ring has NB >= PD + 2 slots.
-template <int QT, int PRIO, int NW = 4, int PD = 2>
+//
+// XP (option hamming_expand_inkernel, NW = 8 and PD = 2 only) = the workgroup expands the train tiles it consumes ITSELF: `tsrc` is the raw
+// train set (rows of 8 words, `t_batch` words per image pair) instead of the fragment buffer, hamming_expand_kernel does not run and the
+// 4x expanded copy of the train set is neither written to memory nor read back.
+//   * Raw ring, NR = 4 slots of 1 KiB: waves 0..3 copy a quarter each of the raw tile (32 rows x 8 words, contiguous in memory) with 4-byte
+//     LDS-DMA, a scalar base plus a 32-bit lane offset that is clamped to the last word of the image pair's train set (the rows of a ragged last
+//     tile behind it start at -inf through its C and never count; nothing past the pair's rows is read).
+//   * Fragment ring, 2 slots of 4 KiB in the fragment order the tile body reads: lane (r, h) of K-step s holds the four planes of raw word
+//     4 h + s of row r.  Wave w expands word w of all 32 rows: lane l reads the word of row l >> 1 and writes dwords 2 (l & 1), 2 (l & 1) + 1,
+//     so a wave writes 512 CONTIGUOUS bytes with ds_write_b64 (no bank conflict; the read is a 4-way conflict of one ds_read_b32).
+//   * Protocol, one s_barrier per tile plus one in the prologue: in iteration `it` a copying wave issues the copy of raw tile it + 2 and waits
+//     for its own piece of raw tile it + 1 (vmcnt(1)); behind the barrier every wave reads its word of raw tile it + 1 together with the
+//     fragments of tile `it`, expands it into fragment slot (it + 1) & 1 and runs the body of tile `it`.  The prologue does the same for tile 0.
+//     Slot reuse: a wave past the barrier of iteration `it` knows that every wave has finished the body of it - 1 (its MFMAs consumed those
+//     reads), so fragment slot (it + 1) & 1 is free, and that every wave's writes of tile `it` have completed (lgkmcnt(0) before the barrier).
+//     Raw slot (it + 2) & 3 last held tile it - 2, read behind the barrier of iteration it - 3 and complete before that of it - 2; the copy
+//     is issued behind the barrier of it - 1.  The tile after the last one does not exist: the last iteration expands a stale raw slot into the
+//     free fragment slot, which nobody reads -- cheaper than a branch around the hand-scheduled LDS sequence.
+template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false>
 __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
-    const uint32_t *__restrict__ qw, size_t q_batch_words, const uint4 *__restrict__ tfrag, size_t t_batch_u4, int nq, int nt,
+    const uint32_t *__restrict__ qw, size_t q_batch_words, const void *__restrict__ tsrc, size_t t_batch, int nq, int nt,
     int rows_per_split, int nsplit, int dshift, int qblocks, int n_items, uint2 *__restrict__ part,
     unsigned long long *__restrict__ stamps, const int32_t *__restrict__ split_tile0, HammingFuse fuse) {
-    constexpr int KS = 4, NB = PD == 2 ? 4 : 8;
+    constexpr int KS = 4, NB = XP ? 2 : PD == 2 ? 4 : 8, NR = 4;
     static_assert(PD == 2 || PD == 4 || PD == 6, "prefetch distance");
+    static_assert(!XP || (NW == 8 && PD == 2), "the in-kernel expansion exists for eight waves and a prefetch distance of 2");
     __shared__ __attribute__((aligned(16))) uint4 ring[NB][KS * 64];
+    __shared__ __attribute__((aligned(16))) uint32_t raw_ring[XP ? NR * 256 : 1];   // (unused, hence not allocated, without XP)
     const int l = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     unsigned long long st_c = 0, st_r = 0;
@@ -398,20 +438,61 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     for (int t = 0; t < QT; ++t) m1[t] = m2[t] = -INFINITY;
 
     // my piece (K-step w) of the split's first tile; a tile is KS * 64 uint4 = 4 KiB, contiguous
-    const uint4 *tbase = tfrag + (size_t)b * t_batch_u4 + (size_t)tile0 * KS * 64 + (size_t)w * 64;  // wave-uniform
+    // (XP: my quarter of the raw tile instead; a raw tile is 32 rows x 8 words = 1 KiB, contiguous)
+    const uint4 *tbase = (const uint4 *)tsrc + (size_t)b * t_batch + (size_t)tile0 * KS * 64 + (size_t)w * 64;  // wave-uniform
+    const char *rbase = (const char *)tsrc + ((size_t)b * t_batch + (size_t)tile0 * 32 * (2 * KS)) * 4;         // wave-uniform
+    const uint32_t raw_last = (uint32_t)(nt - row0) * (8u * KS) - 4u;   // byte offset of the pair's last train word behind rbase
     auto copy_tile = [&](int t_rel) {
         if (NW > KS && w >= KS) return;  // (wave-uniform: the K-steps are copied by the first KS waves)
-        __builtin_amdgcn_global_load_lds((const void *)(tbase + (size_t)t_rel * KS * 64 + l),
-                                         (__attribute__((address_space(3))) void *)&ring[t_rel & (NB - 1)][w * 64], 16, 0, 0);
+        if constexpr (XP) {
+            const uint32_t lx = (uint32_t)l;
+            const uint32_t off = min((uint32_t)t_rel * 1024u + (uint32_t)w * 256u + lx * 4u, raw_last);
+            __builtin_amdgcn_global_load_lds((const void *)(rbase + off),
+                                             (__attribute__((address_space(3))) void *)&raw_ring[(t_rel & (NR - 1)) * 256 + w * 64], 4, 0, 0);
+        } else {
+            __builtin_amdgcn_global_load_lds((const void *)(tbase + (size_t)t_rel * KS * 64 + l),
+                                             (__attribute__((address_space(3))) void *)&ring[t_rel & (NB - 1)][w * 64], 16, 0, 0);
+        }
     };
     // The tile is read back with hand-written ds_read_b128: for a compiler-visible LDS load the waitcnt pass would first drain EVERY
     // outstanding LDS-DMA (vmcnt(0): it cannot know that the copies in flight target other ring slots), which serialises the prefetch.
     // The reads return in order, so K-step s is complete once at most 3 - s of them are outstanding.
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0] + (uint32_t)l * 16u;
-    auto tile_body = [&](int slot, const v16f &c0) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const uint32_t raw_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&raw_ring[0];
+    const uint32_t frag_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0];
+    // XP: where this lane reads its raw word of tile `t_rel` and where it writes the two planes it forms (see the protocol above)
+    auto raw_addr = [&](int t_rel, uint32_t lx) { return raw_lds + (uint32_t)(t_rel & (NR - 1)) * 1024u + (uint32_t)w * 4u + (lx >> 1) * 32u; };
+    auto plane_addr = [&](int t_rel, uint32_t lx) {
+        const uint32_t base = frag_lds + (uint32_t)(t_rel & 1) * (KS * 1024u) + (uint32_t)(w & 3) * 1024u + (uint32_t)(w >> 2) * 512u;   // scalar
+        return base + lx * 8u;
+    };
+    auto expand_pair = [&](uint32_t x, uint32_t lx) {
+        const uint32_t y = x >> (lx & 1u);   // dwords 0, 1 = planes 0, 2; dwords 2, 3 = planes 1, 3
+        return u32x2{expand_plane0(y, 0x22222222u), expand_plane2(y, 0x22222222u)};
+    };
+    auto tile_body = [&](int it, const v16f &c0) {
         u32x4 r[KS];
-        const uint32_t addr = ring_lds + (uint32_t)slot * (KS * 1024u);
+        const uint32_t addr = ring_lds + (uint32_t)(it & (NB - 1)) * (KS * 1024u);
+        if constexpr (XP) {
+            uint32_t lx = (uint32_t)l, x;
+            const uint32_t ra = raw_addr(it + 1, lx), wa = plane_addr(it + 1, lx);
+            asm volatile(
+                "ds_read_b32 %4, %6\n\tds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:1024\n\tds_read_b128 %2, %5 offset:2048\n\t"
+                "ds_read_b128 %3, %5 offset:3072"
+                : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(x)
+                : "v"(addr), "v"(ra)
+                : "memory");
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x));
+            const u32x2 o = expand_pair(x, lx);
+            asm volatile("ds_write_b64 %0, %1" ::"v"(wa), "v"(o) : "memory");
+            // (in order behind the four fragment reads: K-step s is complete once at most 4 - s operations are outstanding)
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r[0]));
+            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
+            asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
+        } else {
         asm volatile(
             "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
             : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
@@ -421,6 +502,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[1]));
         asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[2]));
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[3]));
+        }
         uint4 a[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) a[s] = make_uint4(r[s].x, r[s].y, r[s].z, r[s].w);
@@ -469,8 +551,22 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         const uint32_t vs[KS] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int s = 0; s < KS; ++s)
-            bq[t][s] = make_uint4(expand_byte(vs[s] & 255u), expand_byte((vs[s] >> 8) & 255u), expand_byte((vs[s] >> 16) & 255u),
-                                  expand_byte(vs[s] >> 24));
+            if constexpr (XP)   // (the rule of the train operand)
+                bq[t][s] = make_uint4(expand_plane(vs[s], 0), expand_plane(vs[s], 2), expand_plane(vs[s], 1), expand_plane(vs[s], 3));
+            else
+                bq[t][s] = make_uint4(expand_byte(vs[s] & 255u), expand_byte((vs[s] >> 8) & 255u), expand_byte((vs[s] >> 16) & 255u),
+                                      expand_byte(vs[s] >> 24));
+    }
+    if constexpr (XP) {
+        // tile 0: the query loads' wait has covered the first copies (see above); one barrier makes the four quarters visible, then every
+        // wave expands its word of the tile into fragment slot 0
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        uint32_t lx = (uint32_t)l, x;
+        asm volatile("" : "+v"(lx));
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(x) : "v"(raw_addr(0, lx)) : "memory");
+        const u32x2 o = expand_pair(x, lx);
+        asm volatile("ds_write_b64 %0, %1" ::"v"(plane_addr(0, lx)), "v"(o) : "memory");
     }
 
     // only the last tile of the train set can be ragged; it runs after the loop with its own C (rows >= nt start at -inf and stay there)
@@ -480,6 +576,17 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     // (slot (it + PD) % NB was last read in iteration it + PD - NB <= it - 2, and a wave that has passed the barrier of iteration it - 1 knows
     // that every wave has finished iteration it - 2)
     auto arrive = [&](int it) {
+        if constexpr (XP) {
+            // own quarter of raw tile it + 1 landed; own planes of tile `it` (written in the previous iteration, or the prologue) complete
+            if (it + PD < ntiles) {
+                copy_tile(it + PD);
+                asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();
+            return;
+        }
         if (it + PD < ntiles) {
             copy_tile(it + PD);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PD) : "memory");
@@ -517,7 +624,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         rotate_prio();
         arrive(it);
         if (stamps && l == 0 && it < 48) stamps[(size_t)n_items * NW * 4 + ((size_t)item * NW + w) * 48 + it] = __builtin_amdgcn_s_memtime();
-        tile_body(it & (NB - 1), cinit);
+        tile_body(it, cinit);
     }
     if (ragged) {
         arrive(nfull);
@@ -527,7 +634,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
             const int lr = (reg & 3) + 8 * (reg >> 2) + 4 * h;
             cinit[reg] = (tile_row0 + lr < nt) ? -(float)lr * kEps : -INFINITY;
         }
-        tile_body(nfull & (NB - 1), cinit);
+        tile_body(nfull, cinit);
     }
 
     // (the epilogue's addresses are formed from copies of the lane and tile indices the compiler cannot see through: formed in the prologue
@@ -960,11 +1067,23 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
         return MLPL_E_BAD_INPUT;
     }
 
+    // Instance of the static LDS-ring kernel.  Precedence (the options do not combine): waves 16 (qt 4 only; the plain <4, 0, 16>) beats a
+    // prefetch distance of 4 or 6, which beats prio; prefetch and prio 3 exist at qt 4 with 8 waves only, prio 1 at every shape.  An option
+    // the shape has no instance for is ignored: prefetch with 4 waves, prio 3 below 8 waves (prio 0 is run).
+    const int pd = (nwv == 8 && (ctx->opt_hamming_mfma_prefetch == 4 || ctx->opt_hamming_mfma_prefetch == 6)) ? ctx->opt_hamming_mfma_prefetch : 2;
+    const int prio = (nwv == 16 || pd != 2) ? 0 : ctx->opt_hamming_mfma_prio == 1 ? 1 : (ctx->opt_hamming_mfma_prio == 3 && nwv == 8) ? 3 : 0;
+    const int train01 = (lds_ring && !dyn && ctx->opt_hamming_train01) ? 1 : 0;  // {0, +1} train fragments: that kernel only (it has the raw query words)
+    // In-kernel expansion of the train tiles (option hamming_expand_inkernel): the throughput instance <4, 0, 8, 2> of the static ring kernel on
+    // whole 32-byte rows (a raw tile is then one contiguous KiB) with the +-1 train operand; every other call expands into WS_FRAG_T as before.
+    // (The 4-byte LDS-DMA needs word alignment, which a row of uint32_t has.)
+    const bool inkernel = ctx->opt_hamming_expand_inkernel && lds_ring && !dyn && nwv == 8 && pd == 2 && prio == 0 && nw == 8 && !train01 &&
+                          ((uintptr_t)tw & 3u) == 0;
+
     void *qf = nullptr, *tf = nullptr, *part = nullptr;
     int rc;
     const size_t q_u4 = (size_t)q_tiles_padded * ks * 64, t_u4 = (size_t)t_tiles * ks * 64;
     if ((rc = ws_get(ctx, WS_FRAG_Q, (size_t)batch * q_u4 * 16, &qf))) return rc;
-    if ((rc = ws_get(ctx, WS_FRAG_T, ((size_t)batch * t_u4 + (size_t)ks * 64) * 16, &tf))) return rc;  // + one spare tile (register prefetch)
+    if (!inkernel && (rc = ws_get(ctx, WS_FRAG_T, ((size_t)batch * t_u4 + (size_t)ks * 64) * 16, &tf))) return rc;  // + one spare tile (register prefetch)
     if ((rc = ws_get(ctx, WS_PARTIAL, (size_t)batch * nsplit * nq * sizeof(uint2), &part))) return rc;
     int *counters = nullptr;
     const int counters_per_batch = dyn ? qblocks * nspan : 0;
@@ -975,13 +1094,14 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     }
     // the static LDS-ring kernel expands its query operand itself (in registers): only the train set goes through the expansion kernel
     const bool expand_q = !(lds_ring && !dyn);
-    const int train01 = (lds_ring && !dyn && ctx->opt_hamming_train01) ? 1 : 0;  // {0, +1} train fragments: that kernel only (it has the raw query words)
     const ExpandArgs ta{tw, t_batch_words, nt, t_tiles, (uint4 *)tf};
     const ExpandArgs qa = expand_q ? ExpandArgs{qw, q_batch_words, nq, q_tiles_padded, (uint4 *)qf} : ta;  // blockIdx.z == 0
     const dim3 egrid((unsigned)(((expand_q ? std::max(q_tiles_padded, t_tiles) : t_tiles) * 64 + 255) / 256), batch, expand_q ? 2 : 1);
     // (one thread per K-step when the launch is small: the single-pair latency shape)
-    const bool expand_fine = !expand_q && ks == 4 && nw == 8 && !counters && (long long)t_tiles * batch <= 4LL * ctx->num_cus && ctx->opt_hamming_expand_fine;
-    if (expand_fine) {
+    const bool expand_fine = !inkernel && !expand_q && ks == 4 && nw == 8 && !counters && (long long)t_tiles * batch <= 4LL * ctx->num_cus && ctx->opt_hamming_expand_fine;
+    if (inkernel) {
+        // nothing to expand here: the ring kernel reads the raw train rows
+    } else if (expand_fine) {
         hipLaunchKernelGGL(hamming_expand_fine_kernel, dim3((unsigned)t_tiles, batch), dim3(256), 0, s, ta, train01);
     } else
     switch (ks) {
@@ -1086,16 +1206,11 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
         }
         *fused_out = 1;
     }
-    // Instance of the static LDS-ring kernel.  Precedence (the options do not combine): waves 16 (qt 4 only; the plain <4, 0, 16>) beats a
-    // prefetch distance of 4 or 6, which beats prio; prefetch and prio 3 exist at qt 4 with 8 waves only, prio 1 at every shape.  An option
-    // the shape has no instance for is ignored: prefetch with 4 waves, prio 3 below 8 waves (prio 0 is run).
-    const int pd = (nwv == 8 && (ctx->opt_hamming_mfma_prefetch == 4 || ctx->opt_hamming_mfma_prefetch == 6)) ? ctx->opt_hamming_mfma_prefetch : 2;
-    const int prio = (nwv == 16 || pd != 2) ? 0 : ctx->opt_hamming_mfma_prio == 1 ? 1 : (ctx->opt_hamming_mfma_prio == 3 && nwv == 8) ? 3 : 0;
     {
         int *rec = ctx->dbg_hamming_kernel;
         rec[0] = dyn ? 5 : lds_ring ? 4 : 3, rec[1] = (dyn || !lds_ring) ? (ks <= 4 && qt == 4 ? 4 : qt >= 2 ? 2 : 1) : qt;
         rec[2] = (lds_ring && !dyn) ? prio : 0, rec[3] = lds_ring && !dyn ? nwv : 4, rec[4] = lds_ring && !dyn ? pd : 0;
-        rec[5] = *fused_out, rec[6] = split_tab != nullptr, rec[7] = expand_fine, rec[8] = nsplit, rec[9] = ks;
+        rec[5] = *fused_out, rec[6] = split_tab != nullptr, rec[7] = expand_fine, rec[8] = nsplit, rec[9] = ks, rec[10] = inkernel;
     }
     prof_mark(ctx, MLPL_PROF_KNN_HAMMING, 0, s);
     if (dyn) {
@@ -1110,29 +1225,32 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
 #define MLPL_RING_LAUNCH(QT_)                                                                                                          \
     do {                                                                                                                               \
         if (prio == 1)                                                                                                                 \
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 1>), grid, dim3(256), 0, s, qw, q_batch_words, (const uint4 *)tf, \
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 1>), grid, dim3(256), 0, s, qw, q_batch_words, (const void *)tf,  \
                                t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
         else                                                                                                                           \
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 0>), grid, dim3(256), 0, s, qw, q_batch_words, (const uint4 *)tf, \
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 0>), grid, dim3(256), 0, s, qw, q_batch_words, (const void *)tf,  \
                                t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
     } while (0)
-        if (nwv == 16)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 16>), grid, dim3(1024), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
+        if (inkernel)
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 2, true>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tw, t_batch_words, nq, nt,
+                               rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
+        else if (nwv == 16)
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 16>), grid, dim3(1024), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (nwv == 8 && pd == 4)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 4>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 4>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (nwv == 8 && pd == 6)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 6>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 6>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (nwv == 8 && prio == 3)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 3, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 3, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (nwv == 8 && prio == 1)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 1, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 1, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (nwv == 8)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit,
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
                                dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (qt == 4) MLPL_RING_LAUNCH(4);
         else if (qt == 2) MLPL_RING_LAUNCH(2);

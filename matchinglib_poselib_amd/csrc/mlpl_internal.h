@@ -129,11 +129,12 @@ struct mlpl_ctx {
     size_t hamming_scan_bytes;      // ... and its size when it was zeroed (a regrown block may return at the same address, never at the same size)
     uint32_t hamming_scan_gen;
     int opt_hamming_train01;        // 1 = {0, +1} train fragments in the static LDS-ring kernel (accumulator = pop(query) - distance), 0 = +-1
+    int opt_hamming_expand_inkernel;   // 1 = the static LDS-ring kernel's throughput instance expands the raw train tiles itself (no expansion launch, no WS_FRAG_T)
     int dbg_stamp_items;
     // diagnostics (mlpl_debug_last_kernels): what the last launches chose -- {count instance code, its point splits} of the last
     // inlier-count pass, and the Hamming instance of the last knn_hamming call (layout: include/mlpl_debug.h)
     int dbg_count_kernel[2];
-    int dbg_hamming_kernel[10];
+    int dbg_hamming_kernel[11];
     int opt_ransac_chunk;           // hypotheses per device pass (0 = 32768)
     int opt_ransac_event_cap;       // tests: capacity of the record-event list of candidate / replay kernels (0 = 1024); forces their serial fallback
     int opt_ransac_count_mpl;       // models per lane of the packed-fp32 counting kernel: 2 (default) or 1

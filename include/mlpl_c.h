@@ -83,6 +83,8 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0);
  *     "l2_fold_counts" (default 1) = mlpl_match_l2_dev's fold over the train splits evaluates the ratio predicate and writes the pass
  *     counts itself (four launches), 0 = separate merge and counting launches (five; A/B and tests; same results).
+ *   VFC: "vfc_store_u" 1 = the filter's kernel keeps the m x n kernel matrix U (128 bytes per match) in the workspace, 0 (default) = it
+ *     recomputes U in both passes of an EM iteration.  Same bits either way; the default is not backed by a measurement yet.
  *   RANSAC: "ransac_device_draw" (default 1) = large passes draw their samples on the device (mlpl_debug_ransac_draw); "ransac_chunk" hypotheses per device pass (0 = 32768 = the maximum; the sequential best/niters rule is replayed across
  *     passes); "ransac_lazy_sums" (default 1) = the passes count inliers without the division and compute error sums only for the
  *     models that can still win, 0 = sums for every model; "ransac_f32_filter" (default 1) = the counting kernels decide in packed single
@@ -218,6 +220,34 @@ int mlpl_match_l2_dev(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, 
                       const float *d_t, int nt, size_t t_stride, size_t t_batch_stride, int dim,
                       int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
                       mlpl_dmatch *d_out, int32_t *d_n_out, void *stream);
+
+/* ---- VFC match filter: getMatches' VFCrefine ----------------------------------------------------------------
+ * matchinglib::filterWithVFC (M/source/vfcMatches.cpp:63-100) with VFC's default method, SparseVFC (M/source/vfc.cpp; the other two
+ * methods are unreachable in the reference and not built), on the matched points x1[i] -> x2[i] (n x 2 floats, pixels, host).
+ * normalize() is reproduced bit for bit; the control points are drawn from the first 48 values of glibc's srand(seed) / rand() (the
+ * reference draws from wherever the process-wide stream stands; an unseeded process starts at seed 1); everything from the kernel matrices on
+ * -- posteriors, the m x m system (LU, partial pivoting; a pivot below 100 DBL_EPSILON gives C = 0, cv::solve's rule for doubles), exp and
+ * log -- is float64 with the reference's float constants widened, because the system is numerically singular (condition 1e15 - 1e16) and
+ * the reference's own float rounding decides nothing reproducible.  The contract is the KEPT SET: equal to the reference's on separable
+ * data, equal to the float64 restatement (tests/vfc_oracle.py) otherwise.  One workgroup, all (at most 50) EM iterations in one launch.
+ * keep: n bytes (1 = kept), *n_keep their number; P: NULL or n doubles, the inlier posteriors of the last iteration (diagnostic);
+ * info (optional) = {control points, iterations run, 1 if normalize() refused (a scale below 0.1: everything is kept), solves that hit the
+ * singular rule}.  Returns filterWithVFC's value: 0; -1 (n < 5: nothing ran, keep all 1 and *n_keep = n); -2 (fewer than 10 % kept; keep
+ * and *n_keep are still written).  Errors: MLPL_E_INTERNAL and below (never -1 / -2).  n <= 65535. */
+int mlpl_vfc_filter(mlpl_ctx *ctx, const float *x1, const float *x2, int n, uint32_t seed, uint8_t *keep, int *n_keep, double *P /* NULL or n */,
+                    int info[4]);
+/* The same for a batch of match lists, device-resident and non-synchronising (one launch and a 192-byte-per-problem upload on `stream`):
+ * problem b filters d_matches + b * match_stride (d_n_matches[b] <= match_stride entries: the output of mlpl_match_hamming_dev /
+ * mlpl_match_l2_dev) on x1 = d_kp1[b][queryIdx], x2 = d_kp2[b][trainIdx] ([batch][nq][2] / [batch][nt][2] floats, as
+ * mlpl_gather_match_points_dev reads them; indices outside are clamped).  seeds: HOST, one per problem, or NULL (all 1).  The kept matches
+ * are compacted in order into d_out + b * match_stride (the layout of the pair entries' d_matches_out; d_out must not be d_matches),
+ * d_n_out[b] their number, d_status[b] = 0 / -1 / -2 as above.  status -1 (0 <= n < 5) passes the list through.  getmatches_rule != 0
+ * applies M/source/matchers.cpp:726-731: the list is passed through unchanged unless status is 0 and (kept > 8 or n < 24).
+ * Every problem's list, count and status are bit-identical to what mlpl_vfc_filter yields for it with the same seed (the same kernel,
+ * every sum in an order that depends on the problem alone).  Option "vfc_store_u": see mlpl_set_option. */
+int mlpl_vfc_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                                const float *d_kp1, int nq, const float *d_kp2, int nt, const uint32_t *seeds /* host */, int getmatches_rule,
+                                mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, void *stream);
 
 /* ---- correspondence gather (pre-step of the pose path) -------------------------------------------------------
  * Replaces the gather + ImgToCamCoordTrans of StereoRefine::addNewCorrespondences (P/source/stereo_pose_refinement.cpp:

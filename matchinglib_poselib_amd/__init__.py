@@ -6,7 +6,7 @@ declared in include/mlpl_c.h (libmlpl_hip.so).  This package is the thin host-si
 reference's operator interface; all arithmetic runs in the HIP library and there is no CPU fallback.
 """
 from ._lib import MlplError, Context, load_library, library_path  # noqa: F401
-from .matching import DMATCH_DTYPE, getMatches, knn_hamming, knn_l2sq, ratio_compact  # noqa: F401
+from .matching import DMATCH_DTYPE, filter_with_vfc, getMatches, knn_hamming, knn_l2sq, ratio_compact  # noqa: F401
 
 __all__ = [
     "MlplError",
@@ -15,6 +15,7 @@ __all__ = [
     "library_path",
     "DMATCH_DTYPE",
     "getMatches",
+    "filter_with_vfc",
     "knn_hamming",
     "knn_l2sq",
     "ratio_compact",

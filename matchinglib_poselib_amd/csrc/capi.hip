@@ -160,6 +160,7 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
     ctx->opt_usac_sprt_fast = 1;
     ctx->opt_l2_float_mfma = 1;
     ctx->opt_l2_fold_counts = 1;
+    ctx->opt_vfc_store_u = 0;   // not measured yet (tools/vfc_timing.py measures both settings)
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -222,6 +223,7 @@ static const struct {
 } kRangeOptions[] = {
     {"l2_fold_counts", &mlpl_ctx::opt_l2_fold_counts, 0, 1},
     {"hamming_expand_inkernel", &mlpl_ctx::opt_hamming_expand_inkernel, 0, 1},
+    {"vfc_store_u", &mlpl_ctx::opt_vfc_store_u, 0, 1},
 };
 
 int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
@@ -510,6 +512,49 @@ int mlpl_gather_match_points_dev(mlpl_ctx *ctx, const mlpl_dmatch *d_matches, in
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_gather_match_points(d_matches, n, d_kp1, d_kp2, K0, K1, d_p1, d_p2, pick_stream(ctx, stream));
+}
+
+int mlpl_vfc_filter(mlpl_ctx *ctx, const float *x1, const float *x2, int n, uint32_t seed, uint8_t *keep, int *n_keep, double *P, int info[4]) {
+    if (!ctx || n < 0 || n > 65535 || (n > 0 && (!x1 || !x2 || !keep))) {
+        set_error("mlpl_vfc_filter: bad arguments (n in [0, 65535])");
+        return MLPL_E_INTERNAL;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nn = (size_t)std::max(n, 1);
+    void *d1, *d2;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, nn * 8, &d1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, nn * 8, &d2))) return rc;
+    if (n > 0) {
+        MLPL_HIP_TRY(hipMemcpyAsync(d1, x1, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        MLPL_HIP_TRY(hipMemcpyAsync(d2, x2, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    }
+    VfcWork work{};
+    if ((rc = launch_vfc(ctx, 1, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, (const float *)d1, (const float *)d2, n, &seed, 0, nullptr, nullptr,
+                         nullptr, &work, s)))
+        return rc;
+    int32_t res[8];
+    MLPL_HIP_TRY(hipMemcpyAsync(res, work.res, sizeof(res), hipMemcpyDeviceToHost, s));
+    if (n > 0) MLPL_HIP_TRY(hipMemcpyAsync(keep, work.keep, (size_t)n, hipMemcpyDeviceToHost, s));
+    if (n > 0 && P) MLPL_HIP_TRY(hipMemcpyAsync(P, work.P, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipStreamSynchronize(s));
+    if (n_keep) *n_keep = res[1];
+    if (info) info[0] = res[2], info[1] = res[3], info[2] = res[4], info[3] = res[5];
+    return res[0];
+}
+
+int mlpl_vfc_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                                const float *d_kp1, int nq, const float *d_kp2, int nt, const uint32_t *seeds, int getmatches_rule,
+                                mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, void *stream) {
+    if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
+        nq < 1 || nt < 1 || !d_out || d_out == d_matches || !d_n_out || !d_status) {
+        set_error("mlpl_vfc_filter_matches_dev: bad arguments (batch, match_stride in [1, 65535]; d_out apart from d_matches)");
+        return MLPL_E_INTERNAL;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_vfc(ctx, batch, d_matches, match_stride, d_n_matches, d_kp1, nq, d_kp2, nt, nullptr, nullptr, 0, seeds, getmatches_rule, d_out,
+                      d_n_out, d_status, nullptr, pick_stream(ctx, stream));
 }
 
 int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_stride, size_t q_batch_stride,

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "matchinglib_poselib/matchinglib_matchers.h"
+#include "matchinglib_poselib/vfcMatches.h"
 #include "matchinglib_poselib/pose_estim.h"
 #include "matchinglib_poselib/stereo_pose_refinement.h"
 #include "facade_internal.h"
@@ -52,6 +53,7 @@ mlpl_ctx *default_ctx() {
 
 thread_local bool g_seed_fixed = false;
 thread_local unsigned g_seed = 0;
+thread_local unsigned g_vfc_seed = 1;  // glibc's rand() state when srand was never called
 
 // contiguous n x 2 CV_64F copy of a point matrix (the reference converts with convertTo(CV_64F))
 std::vector<double> points64(cv::InputArray pa, int &n) {
@@ -97,10 +99,6 @@ int getMatches(const std::vector<cv::KeyPoint> &keypoints1, const std::vector<cv
         return -1;
     }
     if (descriptors1.cols != descriptors2.cols) return -1;
-    if (VFCrefine) {
-        std::cout << "VFC refinement is not part of the MI355X hot path." << std::endl;
-        return -2;
-    }
     std::vector<mlpl_dmatch> out((size_t)descriptors1.rows);
     int n_out = 0;
     // cv::Mat::step is honoured, so non-continuous Mats (ROIs) are handled (the reference silently mis-reads them,
@@ -117,6 +115,40 @@ int getMatches(const std::vector<cv::KeyPoint> &keypoints1, const std::vector<cv
     static_assert(sizeof(cv::DMatch) == sizeof(mlpl_dmatch), "DMatch layout");
     if (n_out) std::memcpy((void *)finalMatches.data(), out.data(), (size_t)n_out * sizeof(mlpl_dmatch));
     if (rc == -3) std::cout << "Too less remaining matches using the " << matcher_name << " matcher." << std::endl;
+    if (rc == 0 && VFCrefine) {
+        // matchers.cpp:722-733: the filtered list replaces finalMatches only when the filter returned 0 and (kept > 8 or n < 24)
+        std::vector<cv::DMatch> filtered;
+        if (!filterWithVFC(keypoints1, keypoints2, finalMatches, filtered)) {
+            if (filtered.size() > 8 || finalMatches.size() < 24) finalMatches = filtered;
+        }
+    }
+    return rc;
+}
+
+void setVfcSeed(unsigned seed) { g_vfc_seed = seed; }
+void clearVfcSeed() { g_vfc_seed = 1; }
+
+int filterWithVFC(std::vector<cv::KeyPoint> const &keypL, std::vector<cv::KeyPoint> const &keypR, std::vector<cv::DMatch> const &matches_in,
+                  std::vector<cv::DMatch> &matches_out) {
+    matches_out.clear();
+    const size_t n = matches_in.size();
+    if (n < 5) {  // VFC::setData, MIN_POINT_NUMBER
+        std::cout << "Too less matches for refinement with VFC!" << std::endl;
+        return -1;
+    }
+    if (n > 65535) throw cv::Exception("filterWithVFC: more than 65535 matches");
+    std::vector<float> x1(2 * n), x2(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const cv::Point2f &a = keypL.at((size_t)matches_in[i].queryIdx).pt, &b = keypR.at((size_t)matches_in[i].trainIdx).pt;
+        x1[2 * i] = a.x, x1[2 * i + 1] = a.y, x2[2 * i] = b.x, x2[2 * i + 1] = b.y;
+    }
+    std::vector<uint8_t> keep(n);
+    int n_keep = 0;
+    const int rc = mlpl_vfc_filter(default_ctx(), x1.data(), x2.data(), (int)n, g_vfc_seed, keep.data(), &n_keep, nullptr, nullptr);
+    if (rc != 0 && rc != -2) throw cv::Exception(std::string("filterWithVFC: ") + mlpl_last_error());
+    matches_out.reserve((size_t)n_keep);
+    for (size_t i = 0; i < n; ++i)
+        if (keep[i]) matches_out.push_back(matches_in[i]);
     return rc;
 }
 

@@ -62,6 +62,7 @@ enum WsSlot {
     WS_CLOCK,     // clock ring of the Hamming kernel (option hamming_stamps = 2): kClockRing records of 4 x u64
     WS_SCAN,      // pass counts of the merge workgroups when the merge kernel emits the matches itself (knn_hamming.hip MergeEmit)
     WS_TICKETS,   // ticket counters of the fused Hamming epilogue (zero between launches; knn_hamming_mfma.hip)
+    WS_VFC,       // VFC match filter (vfc.hip): per-point state, per-problem results, the raw rand() values of the control-point draws
     WS_NUM_SLOTS
 };
 
@@ -129,6 +130,7 @@ struct mlpl_ctx {
     size_t hamming_scan_bytes;      // ... and its size when it was zeroed (a regrown block may return at the same address, never at the same size)
     uint32_t hamming_scan_gen;
     int opt_hamming_train01;        // 1 = {0, +1} train fragments in the static LDS-ring kernel (accumulator = pop(query) - distance), 0 = +-1
+    int opt_vfc_store_u;            // 1 = the VFC kernel keeps the m x n kernel matrix U in the workspace; 0 (default, unmeasured: DESIGN section 8) = it recomputes U in both passes of an iteration
     int opt_hamming_expand_inkernel;   // 1 = the static LDS-ring kernel's throughput instance expands the raw train tiles itself (no expansion launch, no WS_FRAG_T)
     int dbg_stamp_items;
     // diagnostics (mlpl_debug_last_kernels): what the last launches chose -- {count instance code, its point splits} of the last
@@ -285,5 +287,60 @@ int launch_recover_pose_batch(const char *d_E_base, size_t E_stride, const doubl
 int launch_gather_match_points_batch(const mlpl_dmatch *d_matches, const int32_t *d_counts, int B, int pair_stride, const float *d_kp1,
                                      size_t kp1_stride, const float *d_kp2, size_t kp2_stride, const double K0[4], const double K1[4],
                                      double *d_p1, double *d_p2, hipStream_t s);
+
+
+// VFC match filter (vfc.hip).  Points either through a match list and keypoints (d_matches [batch][match_stride], d_n_matches [batch],
+// d_kp1 [batch][nq][2], d_kp2 [batch][nt][2]) or directly (d_matches == nullptr, batch = 1: d_x1 / d_x2 [n_direct][2]); seeds: host,
+// [batch] or nullptr (= 1).  One launch and one small upload on s, no synchronisation.  *work (optional) receives the workspace views of the
+// launch: keep [batch][stride] bytes, P [batch][stride], res [batch][8] = {status, kept, control points, iterations, normalisation
+// refused, singular solves, n_out, 0}.
+struct VfcWork {
+    const uint8_t *keep;
+    const double *P;
+    const int32_t *res;
+    size_t stride;
+};
+int launch_vfc(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches, const float *d_kp1, int nq,
+               const float *d_kp2, int nt, const float *d_x1, const float *d_x2, int n_direct, const uint32_t *seeds, int rule, mlpl_dmatch *d_out,
+               int32_t *d_n_out, int32_t *d_status, VfcWork *work, hipStream_t s);
+
+// glibc srand()/rand() (TYPE_3 additive feedback generator: r[k+3] += r[k] over a ring of 31 words, output r >> 1, the first 310
+// outputs discarded), produced 31 values at a time: one unrolled pass over the ring has no index wrap-around and three independent
+// dependency chains.  After seeding the generator is block-aligned (310 = 10 * 31), so block k holds outputs 31 k .. 31 k + 30.
+struct GlibcRand {
+    uint32_t r[31];
+    int32_t out[31];
+    int pos;
+    void refill() {
+#pragma unroll
+        for (int k = 0; k < 28; ++k) {
+            r[k + 3] += r[k];
+            out[k] = (int32_t)(r[k + 3] >> 1);
+        }
+        for (int k = 28; k < 31; ++k) {
+            r[k - 28] += r[k];
+            out[k] = (int32_t)(r[k - 28] >> 1);
+        }
+        pos = 0;
+    }
+    void seed(unsigned s) {
+        if (s == 0) s = 1;
+        int32_t t[31];
+        t[0] = (int32_t)s;
+        for (int i = 1; i < 31; ++i) {
+            const long hi = t[i - 1] / 127773, lo = t[i - 1] % 127773;
+            long w = 16807 * lo - 2836 * hi;
+            if (w < 0) w += 2147483647;
+            t[i] = (int32_t)w;
+        }
+        for (int i = 0; i < 31; ++i) r[i] = (uint32_t)t[i];
+        for (int i = 0; i < 10; ++i) refill();
+        pos = 31;
+    }
+    int next() {
+        if (pos == 31) refill();
+        return out[pos++];
+    }
+};
 
 }  // namespace mlpl

@@ -2795,45 +2795,7 @@ __global__ void refit_decide_kernel(const int32_t *__restrict__ n_models, const 
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 
-// glibc srand()/rand() (TYPE_3 additive feedback), so that a seed reproduces the reference's sample stream
-// glibc srand()/rand() (TYPE_3 additive feedback generator: r[k+3] += r[k] over a ring of 31 words, output r >> 1, the first 310
-// outputs discarded), produced 31 values at a time: one unrolled pass over the ring has no index wrap-around and three independent
-// dependency chains.  After seeding the generator is block-aligned (310 = 10 * 31), so block k holds outputs 31 k .. 31 k + 30.
-struct GlibcRand {
-    uint32_t r[31];
-    int32_t out[31];
-    int pos;
-    void refill() {
-#pragma unroll
-        for (int k = 0; k < 28; ++k) {
-            r[k + 3] += r[k];
-            out[k] = (int32_t)(r[k + 3] >> 1);
-        }
-        for (int k = 28; k < 31; ++k) {
-            r[k - 28] += r[k];
-            out[k] = (int32_t)(r[k - 28] >> 1);
-        }
-        pos = 0;
-    }
-    void seed(unsigned s) {
-        if (s == 0) s = 1;
-        int32_t t[31];
-        t[0] = (int32_t)s;
-        for (int i = 1; i < 31; ++i) {
-            const long hi = t[i - 1] / 127773, lo = t[i - 1] % 127773;
-            long w = 16807 * lo - 2836 * hi;
-            if (w < 0) w += 2147483647;
-            t[i] = (int32_t)w;
-        }
-        for (int i = 0; i < 31; ++i) r[i] = (uint32_t)t[i];
-        for (int i = 0; i < 10; ++i) refill();
-        pos = 31;
-    }
-    int next() {
-        if (pos == 31) refill();
-        return out[pos++];
-    }
-};
+// glibc srand()/rand(): GlibcRand (mlpl_internal.h), so that a seed reproduces the reference's sample stream
 
 // getSubset (modelest.cpp:567-610): 5 distinct indices, duplicates redrawn.  checkSubset (:613-650) returns
 // `i >= i1` with i0 == i1, i.e. true for every input, so no geometric rejection ever happens in the reference.

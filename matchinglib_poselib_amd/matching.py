@@ -104,6 +104,7 @@ def getMatches(
     queryPars_NMSLIB: str = "",
     nr_threads: int = 0,
     ctx: Optional[Context] = None,
+    vfc_seed: int = 1,
 ) -> Tuple[int, np.ndarray]:
     """matchinglib::getMatches (matchinglib_matchers.h:61-64).  Returns (err, finalMatches).
 
@@ -112,6 +113,8 @@ def getMatches(
     "BRUTEFORCENMS" (NMSLIB seq_search, matchers.cpp:476-519, with its 240-bit / sqrt-L2 semantics) are built in this
     library; every other name -- including the reference's default "GMBSOF" -- yields -2.
     A dtype mismatch raises ValueError where the reference's CV_Assert throws cv::Exception (matchers.cpp:119).
+    VFCrefine (matchers.cpp:722-733): the matches are filtered with filter_with_vfc(seed = vfc_seed) and the filtered list replaces them
+    when the filter returned 0 and (kept > 8 or n < 24); keypoints1 / keypoints2 must then carry coordinates ((x, y) rows or .pt).
     """
     d1 = np.asarray(descriptors1)
     d2 = np.asarray(descriptors2)
@@ -125,8 +128,6 @@ def getMatches(
         return -1, empty
     if matcher_name not in ("LINEAR", "BRUTEFORCENMS"):
         return -2, empty
-    if VFCrefine:
-        raise NotImplementedError("VFC refinement (matchers.cpp:722-733) is outside the hot path built here")
     if d1.dtype == np.uint8:
         desc_type = CV_8U
     elif d1.dtype == np.float32:
@@ -145,10 +146,51 @@ def getMatches(
         ctx.handle, n1, n2, d1.ctypes.data, d1.shape[0], d1.strides[0], d2.ctypes.data, d2.shape[0], d2.strides[0],
         d1.shape[1], desc_type, 1 if ratioTest else 0, out.ctypes.data, C.byref(n))
     if rc in (0, -3):
-        return rc, out[: n.value].copy()
+        matches = out[: n.value].copy()
+        if rc == 0 and VFCrefine:
+            vrc, filtered = filter_with_vfc(keypoints1, keypoints2, matches, seed=vfc_seed, ctx=ctx)
+            if vrc == 0 and (len(filtered) > 8 or len(matches) < 24):
+                matches = filtered
+        return rc, matches
     if rc in (-1, -4):
         return rc, empty
     raise MlplError(rc, "mlpl_get_matches_linear", _lib.last_error())
+
+
+def _keypoint_xy(kps) -> np.ndarray:
+    """(x, y) float32 rows of a keypoint sequence: an [n, 2] array, (x, y) pairs, or objects with .pt (cv2.KeyPoint)."""
+    if isinstance(kps, np.ndarray):
+        return np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
+    return np.ascontiguousarray([k.pt if hasattr(k, "pt") else k for k in kps], np.float32).reshape(-1, 2)
+
+
+def vfc_filter_points(x1, x2, seed: int = 1, ctx: Optional[Context] = None) -> dict:
+    """mlpl_vfc_filter on matched points x1[i] -> x2[i] (float32 [n, 2]) -> dict(rc, keep bool [n], n_keep, P float64 [n], m, iterations,
+    refused, singular).  rc = 0, -1 (n < 5: everything kept) or -2 (fewer than 10 % kept)."""
+    ctx = ctx or default_context()
+    x1 = np.ascontiguousarray(x1, np.float32).reshape(-1, 2)
+    x2 = np.ascontiguousarray(x2, np.float32).reshape(-1, 2)
+    n = x1.shape[0]
+    if x2.shape[0] != n:
+        raise ValueError("x1 and x2 differ in length")
+    keep, P, info, nk = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float64), np.zeros(4, np.int32), C.c_int(0)
+    rc = ctx.lib.mlpl_vfc_filter(ctx.handle, x1.ctypes.data, x2.ctypes.data, n, int(seed) & 0xFFFFFFFF, keep.ctypes.data, C.byref(nk),
+                                 P.ctypes.data, info.ctypes.data)
+    if rc not in (0, -1, -2):
+        raise MlplError(rc, "mlpl_vfc_filter", _lib.last_error())
+    return dict(rc=rc, keep=keep[:n].astype(bool), n_keep=nk.value, P=P[:n], m=int(info[0]), iterations=int(info[1]), refused=bool(info[2]),
+                singular=int(info[3]))
+
+
+def filter_with_vfc(kp1, kp2, matches: np.ndarray, seed: int = 1, ctx: Optional[Context] = None) -> Tuple[int, np.ndarray]:
+    """matchinglib::filterWithVFC (vfcMatches.cpp:63-100) -> (rc, matches_out): 0 ok, -1 fewer than 5 matches (matches_out empty), -2
+    fewer than 10 % kept.  kp1 / kp2: keypoint coordinates (see getMatches); matches: DMATCH_DTYPE rows."""
+    matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
+    if len(matches) < 5:
+        return -1, np.empty(0, DMATCH_DTYPE)
+    a, b = _keypoint_xy(kp1), _keypoint_xy(kp2)
+    r = vfc_filter_points(a[matches["queryIdx"]], b[matches["trainIdx"]], seed, ctx)
+    return r["rc"], matches[r["keep"]].copy()
 
 
 # ---- device-resident (torch) entry: nothing leaves HBM -------------------------------------------------------
@@ -224,4 +266,37 @@ def match_l2_device(q, t, ratio_test: bool = True, ratio: float = 0.75, ctx: Opt
     check(rc, "mlpl_match_l2_dev")
     if nq == 0:
         out = {k_: (v[:, :0] if k_ != "count" else v) for k_, v in out.items()}
+    return out
+
+
+def vfc_filter_matches_device(matches, count, kp1, kp2, seeds=None, getmatches_rule: bool = False, ctx: Optional[Context] = None, out=None,
+                              stream: Optional[int] = None):
+    """Batched VFC filter on device-resident match lists (mlpl_vfc_filter_matches_dev), the step between match_hamming_device /
+    match_l2_device and the gather.  matches: int32 [B, stride, 4] (DMatch rows), count: int32 [B], kp1: float32 [B, nq, 2], kp2:
+    float32 [B, nt, 2] CUDA/HIP tensors; seeds: one per problem (host) or None (all 1).  Returns dict of torch tensors matches
+    [B, stride, 4] (the kept matches, compacted in order), count [B], status [B] (0, -1: fewer than 5, passed through, -2: fewer than
+    10 % kept).  getmatches_rule: pass a list through unless status is 0 and (kept > 8 or n < 24).  Enqueues on `stream` (None = torch's
+    current stream) without synchronising."""
+    import torch
+
+    if matches.dim() == 2:
+        matches, count, kp1, kp2 = matches.unsqueeze(0), count.reshape(1), kp1.unsqueeze(0), kp2.unsqueeze(0)
+    assert matches.is_cuda and matches.dtype == torch.int32 and matches.is_contiguous() and matches.shape[2] == 4
+    assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()
+    assert kp1.is_cuda and kp2.is_cuda and kp1.dtype == torch.float32 and kp2.dtype == torch.float32 and kp1.is_contiguous() and kp2.is_contiguous()
+    B, stride = matches.shape[0], matches.shape[1]
+    assert count.shape == (B,) and kp1.shape[0] == B and kp2.shape[0] == B and kp1.shape[2] == 2 and kp2.shape[2] == 2
+    ctx = ctx or default_context(matches.device.index or 0)
+    sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint32), (B,)))
+    if out is None:
+        out = {
+            "matches": torch.empty_like(matches),
+            "count": torch.empty((B,), dtype=torch.int32, device=matches.device),
+            "status": torch.empty((B,), dtype=torch.int32, device=matches.device),
+        }
+    rc = ctx.lib.mlpl_vfc_filter_matches_dev(
+        ctx.handle, B, matches.data_ptr(), stride, count.data_ptr(), kp1.data_ptr(), kp1.shape[1], kp2.data_ptr(), kp2.shape[1],
+        None if sd is None else sd.ctypes.data, 1 if getmatches_rule else 0, out["matches"].data_ptr(), out["count"].data_ptr(),
+        out["status"].data_ptr(), torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
+    check(rc, "mlpl_vfc_filter_matches_dev")
     return out

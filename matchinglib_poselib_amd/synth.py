@@ -137,3 +137,34 @@ def stereo_pair_f32(n: int = 2000, seed: int = 20260400, dim: int = 128, sigma: 
     K = np.array([f, f, cx, cy], np.float64)
     return dict(desc1=np.ascontiguousarray(d1, np.float32), desc2=np.ascontiguousarray(d2, np.float32), kp1=kp1, kp2=kp2, K=K, R=R, t=t,
                 train_of_query=perm.astype(np.int32))
+
+
+def vfc_scene(kind: str, n: int, seed: int = 0, width: float = 1280.0, height: float = 720.0):
+    """Matched points for the VFC match filter (matchinglib::filterWithVFC): x1 uniform over a width x height image, x2 = H(x1) under a
+    mild homography (2 degrees of rotation, 3 % of scale, a shift, a little perspective).
+    kind "clean":  0.7 px of Gaussian noise on x2, and 20-50 % of the matches (the fraction is drawn per scene) replaced by uniform
+                   outliers -- separable data: the inlier posterior is bimodal.
+    kind "graded": no outliers, but a per-match noise sigma that is log-uniform in [0.5, 120] px -- a continuum between inlier and
+                   outlier, on which the posterior comes arbitrarily close to the filter's threshold.
+    Returns dict(x1, x2: float32 [n, 2], inlier: bool [n] ("clean": not replaced; "graded": sigma < 3 px), sigma [n])."""
+    if kind not in ("clean", "graded"):
+        raise ValueError("kind is 'clean' or 'graded'")
+    rng = np.random.default_rng(20261719 + 7919 * seed + (0 if kind == "clean" else 1))
+    x1 = rng.random((n, 2)) * np.array([width, height])
+    a = np.deg2rad(2.0)
+    H = np.array([[1.03 * np.cos(a), -1.03 * np.sin(a), 24.0], [1.03 * np.sin(a), 1.03 * np.cos(a), -15.0], [2e-5, -1e-5, 1.0]])
+    h = np.concatenate([x1, np.ones((n, 1))], axis=1) @ H.T
+    x2 = h[:, :2] / h[:, 2:3]
+    if kind == "clean":
+        sigma = np.full(n, 0.7)
+        x2 = x2 + rng.normal(0.0, 1.0, (n, 2)) * 0.7
+        frac = rng.uniform(0.2, 0.5)
+        out = np.zeros(n, bool)
+        out[rng.permutation(n)[: int(round(frac * n))]] = True
+        x2[out] = rng.random((int(out.sum()), 2)) * np.array([width, height])
+        inlier = ~out
+    else:
+        sigma = np.exp(rng.uniform(np.log(0.5), np.log(120.0), n))
+        x2 = x2 + rng.normal(0.0, 1.0, (n, 2)) * sigma[:, None]
+        inlier = sigma < 3.0
+    return dict(x1=np.ascontiguousarray(x1, np.float32), x2=np.ascontiguousarray(x2, np.float32), inlier=inlier, sigma=sigma)

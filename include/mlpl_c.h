@@ -249,6 +249,37 @@ int mlpl_vfc_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_m
                                 const float *d_kp1, int nq, const float *d_kp2, int nt, const uint32_t *seeds /* host */, int getmatches_rule,
                                 mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, void *stream);
 
+/* ---- GMS match filter: matchinglib::filterMatchesGMS --------------------------------------------------------
+ * Grid-based motion statistics (M/source/gms.cpp over M/thirdparty/gms-1.0/src/MatchGMS.cpp), the filter getCorrespondences runs behind
+ * getMatches (M/source/correspondences.cpp:378-397).  Integer voting on a 20 x 20 left grid and a right grid of 20, 10, 14, 28 or 40 cells a
+ * side (scale levels 0-4; only level 0 without use_scale), four half-cell-shifted grid types per run, eight rotation types of the 3 x 3
+ * neighbourhood with use_rotation (only type 0 without); the first run with the most inliers wins (scale level outer, rotation type inner,
+ * strict >).  Reproduced bit for bit, the reference's quirks included: coordinates are normalised with a float reciprocal and one float
+ * multiply, the cell is floorf of a separately rounded multiply (and + 0.5f); a negative left x is not checked and may alias into the
+ * row before; the right cell is computed at grid type 1 only and not bounds-checked (x = Wr aliases into the next row); a match whose left
+ * or right index is negative at a grid type is dropped for the REST of the run (it keeps an inlier flag it earned before); the cell test
+ * score < 6 sqrt(thresh / numPair) is evaluated in double.
+ * Deviations: where the reference reads or writes out of bounds or converts an unrepresentable float to int, the match is dropped like a
+ * negative index and counted: a right index at or above Wr * Hr, a coordinate that is not finite or whose floor does not fit an int.  Cell
+ * indices are formed in 64 bits (the reference's int sum can overflow).  A non-positive image size is MLPL_E_BAD_INPUT.
+ * kp1 / kp2: n1 / n2 rows of (x, y) floats; matches: n DMatch rows; all HOST pointers.  keep: n bytes of 0 / 1, *n_keep the best run's count
+ * (0 = "nothing assigned": keep is all 0).  info (optional) = {winning scale level or -1, winning rotation type or -1, matches dropped by
+ * the out-of-bounds rule in the winning run, 0}.  Returns 0, or MLPL_E_BAD_INPUT (n > 65535, a non-positive size, a queryIdx / trainIdx
+ * outside the keypoint arrays) or another MLPL_E_* code.  n = 0 returns 0 with *n_keep = 0. */
+int mlpl_gms_filter(mlpl_ctx *ctx, const float *kp1, int n1, int width1, int height1, const float *kp2, int n2, int width2, int height2,
+                    const mlpl_dmatch *matches, int n, int use_scale, int use_rotation, uint8_t *keep, int *n_keep, int info[4]);
+/* The same for a batch of match lists, device-resident and non-synchronising (one launch on `stream`, no upload): the layouts of
+ * mlpl_vfc_filter_matches_dev -- problem b filters d_matches + b * match_stride (d_n_matches[b] <= match_stride entries: the output of
+ * mlpl_match_hamming_dev / mlpl_match_l2_dev) on d_kp1[b][queryIdx], d_kp2[b][trainIdx] ([batch][nq][2] / [batch][nt][2] floats; indices
+ * outside are clamped).  The kept matches are compacted in order into d_out + b * match_stride (d_out must not be d_matches), d_n_out[b]
+ * their number, d_n_inliers[b] the filter's count.  min_final_rule != 0 applies correspondences.cpp:388-397: the list passes through
+ * unchanged unless the count is at least MIN_FINAL_MATCHES (2).  Every list, count and flag is bit-identical to mlpl_gms_filter on the same
+ * problem (the same kernel).  batch, match_stride in [1, 65535]. */
+int mlpl_gms_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                                const float *d_kp1, int nq, const float *d_kp2, int nt, int width1, int height1, int width2, int height2,
+                                int use_scale, int use_rotation, int min_final_rule, mlpl_dmatch *d_out, int32_t *d_n_out,
+                                int32_t *d_n_inliers, void *stream);
+
 /* ---- correspondence gather (pre-step of the pose path) -------------------------------------------------------
  * Replaces the gather + ImgToCamCoordTrans of StereoRefine::addNewCorrespondences (P/source/stereo_pose_refinement.cpp:
  * 428-455, P/source/pose_helper.cpp:1100-1109): p1[i] = ((double)kp1[m.queryIdx] - c0) / f0 rounded to float and widened

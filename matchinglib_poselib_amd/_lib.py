@@ -162,6 +162,10 @@ _SIGNATURES = {
     "mlpl_vfc_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mlpl_vfc_filter_matches_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_gms_filter": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                c_void_p, c_void_p, c_void_p]),
+    "mlpl_gms_filter_matches_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mlpl_recover_pose_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
     "mlpl_recover_pose_translation": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,

@@ -557,6 +557,59 @@ int mlpl_vfc_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_m
                       d_n_out, d_status, nullptr, pick_stream(ctx, stream));
 }
 
+int mlpl_gms_filter(mlpl_ctx *ctx, const float *kp1, int n1, int width1, int height1, const float *kp2, int n2, int width2, int height2,
+                    const mlpl_dmatch *matches, int n, int use_scale, int use_rotation, uint8_t *keep, int *n_keep, int info[4]) {
+    if (!ctx || n < 0 || n > 65535 || n1 < 0 || n2 < 0 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 ||
+        (n > 0 && (!kp1 || !kp2 || !matches || !keep))) {
+        set_error("mlpl_gms_filter: bad arguments (n in [0, 65535], positive image sizes)");
+        return MLPL_E_BAD_INPUT;
+    }
+    for (int i = 0; i < n; ++i)
+        if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n1 || matches[i].trainIdx < 0 || matches[i].trainIdx >= n2) {
+            set_error("mlpl_gms_filter: match %d points outside the keypoint arrays", i);
+            return MLPL_E_BAD_INPUT;
+        }
+    if (n_keep) *n_keep = 0;
+    if (info) info[0] = -1, info[1] = -1, info[2] = 0, info[3] = 0;
+    if (n == 0) return MLPL_OK;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    void *d1, *d2, *dm;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n1 * 8, &d1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n2 * 8, &d2))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX2, (size_t)n * sizeof(mlpl_dmatch), &dm))) return rc;
+    MLPL_HIP_TRY(hipMemcpyAsync(d1, kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(d2, kp2, (size_t)n2 * 8, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(dm, matches, (size_t)n * sizeof(mlpl_dmatch), hipMemcpyHostToDevice, s));
+    GmsWork work{};
+    if ((rc = launch_gms(ctx, 1, (const mlpl_dmatch *)dm, n, nullptr, n, (const float *)d1, n1, (const float *)d2, n2, width1, height1, width2,
+                         height2, use_scale, use_rotation, 0, nullptr, nullptr, nullptr, &work, s)))
+        return rc;
+    int32_t res[8];
+    MLPL_HIP_TRY(hipMemcpyAsync(res, work.res, sizeof(res), hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(keep, work.keep, (size_t)n, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipStreamSynchronize(s));
+    if (n_keep) *n_keep = res[0];
+    if (info) info[0] = res[1], info[1] = res[2], info[2] = res[3], info[3] = 0;
+    return MLPL_OK;
+}
+
+int mlpl_gms_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                                const float *d_kp1, int nq, const float *d_kp2, int nt, int width1, int height1, int width2, int height2,
+                                int use_scale, int use_rotation, int min_final_rule, mlpl_dmatch *d_out, int32_t *d_n_out,
+                                int32_t *d_n_inliers, void *stream) {
+    if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
+        nq < 1 || nt < 1 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 || !d_out || d_out == d_matches || !d_n_out ||
+        !d_n_inliers) {
+        set_error("mlpl_gms_filter_matches_dev: bad arguments (batch, match_stride in [1, 65535]; positive image sizes; d_out apart from d_matches)");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_gms(ctx, batch, d_matches, match_stride, d_n_matches, 0, d_kp1, nq, d_kp2, nt, width1, height1, width2, height2, use_scale,
+                      use_rotation, min_final_rule, d_out, d_n_out, d_n_inliers, nullptr, pick_stream(ctx, stream));
+}
+
 int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_stride, size_t q_batch_stride,
                            const uint8_t *d_t, int nt, size_t t_stride, size_t t_batch_stride, int nbytes,
                            int ratio_test, float ratio, int batch, int32_t *d_idx, int32_t *d_dist, mlpl_dmatch *d_out,

@@ -63,6 +63,7 @@ enum WsSlot {
     WS_SCAN,      // pass counts of the merge workgroups when the merge kernel emits the matches itself (knn_hamming.hip MergeEmit)
     WS_TICKETS,   // ticket counters of the fused Hamming epilogue (zero between launches; knn_hamming_mfma.hip)
     WS_VFC,       // VFC match filter (vfc.hip): per-point state, per-problem results, the raw rand() values of the control-point draws
+    WS_GMS,       // GMS match filter (gms.hip): per-match cell codes, buckets and flags, per-problem results
     WS_NUM_SLOTS
 };
 
@@ -303,6 +304,19 @@ struct VfcWork {
 int launch_vfc(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches, const float *d_kp1, int nq,
                const float *d_kp2, int nt, const float *d_x1, const float *d_x2, int n_direct, const uint32_t *seeds, int rule, mlpl_dmatch *d_out,
                int32_t *d_n_out, int32_t *d_status, VfcWork *work, hipStream_t s);
+
+// GMS match filter (gms.hip) on match lists and keypoints (d_matches [batch][match_stride], d_n_matches [batch] or nullptr = n_direct for
+// every problem, d_kp1 [batch][nq][2], d_kp2 [batch][nt][2]).  One launch on s, no upload, no synchronisation.  *work (optional) receives the
+// workspace views of the launch: keep [batch][stride] bytes, res [batch][8] = {count, winning scale level or -1, winning rotation type or
+// -1, matches dropped by the out-of-bounds rule in the winning run, n_out, 0, 0, 0}.
+struct GmsWork {
+    const uint8_t *keep;
+    const int32_t *res;
+    size_t stride;
+};
+int launch_gms(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches, int n_direct,
+               const float *d_kp1, int nq, const float *d_kp2, int nt, int width1, int height1, int width2, int height2, int use_scale,
+               int use_rotation, int rule, mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_n_inliers, GmsWork *work, hipStream_t s);
 
 // glibc srand()/rand() (TYPE_3 additive feedback generator: r[k+3] += r[k] over a ring of 31 words, output r >> 1, the first 310
 // outputs discarded), produced 31 values at a time: one unrolled pass over the ring has no index wrap-around and three independent

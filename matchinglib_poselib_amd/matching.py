@@ -300,3 +300,62 @@ def vfc_filter_matches_device(matches, count, kp1, kp2, seeds=None, getmatches_r
         out["status"].data_ptr(), torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
     check(rc, "mlpl_vfc_filter_matches_dev")
     return out
+
+
+# ---- GMS match filter ------------------------------------------------------------------------------------------
+
+def gms_filter(kp1, size1, kp2, size2, matches, use_scale: bool = False, use_rotation: bool = False, ctx: Optional[Context] = None) -> dict:
+    """mlpl_gms_filter (matchinglib::filterMatchesGMS, the inlier-mask overload) -> dict(keep bool [n], n_keep, scale, rotation, dropped).
+    kp1 / kp2: keypoint coordinates ([n, 2] arrays, (x, y) pairs or objects with .pt); size1 / size2: (width, height) of the images;
+    matches: DMATCH_DTYPE rows.  scale / rotation: the winning scale level / rotation type, -1 when no run found an inlier (n_keep 0);
+    dropped: matches the out-of-bounds rule dropped in the winning run (include/mlpl_c.h)."""
+    ctx = ctx or default_context()
+    a, b = _keypoint_xy(kp1), _keypoint_xy(kp2)
+    matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    keep, info, nk = np.zeros(max(n, 1), np.uint8), np.zeros(4, np.int32), C.c_int(0)
+    rc = ctx.lib.mlpl_gms_filter(ctx.handle, a.ctypes.data, a.shape[0], int(size1[0]), int(size1[1]), b.ctypes.data, b.shape[0], int(size2[0]),
+                                 int(size2[1]), matches.ctypes.data, n, 1 if use_scale else 0, 1 if use_rotation else 0, keep.ctypes.data,
+                                 C.byref(nk), info.ctypes.data)
+    check(rc, "mlpl_gms_filter")
+    return dict(keep=keep[:n].astype(bool), n_keep=nk.value, scale=int(info[0]), rotation=int(info[1]), dropped=int(info[2]))
+
+
+def filter_matches_gms(kp1, size1, kp2, size2, matches, use_scale: bool = False, use_rotation: bool = False,
+                       ctx: Optional[Context] = None) -> Tuple[int, np.ndarray]:
+    """matchinglib::filterMatchesGMS, the matches_filtered overload -> (n, matches_out): the kept matches in order (empty when n is 0)."""
+    matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
+    r = gms_filter(kp1, size1, kp2, size2, matches, use_scale, use_rotation, ctx)
+    return r["n_keep"], matches[r["keep"]].copy()
+
+
+def gms_filter_matches_device(matches, count, kp1, kp2, size1, size2, use_scale: bool = False, use_rotation: bool = False,
+                              min_final_rule: bool = False, ctx: Optional[Context] = None, out=None, stream: Optional[int] = None):
+    """Batched GMS filter on device-resident match lists (mlpl_gms_filter_matches_dev), the step between match_hamming_device /
+    match_l2_device and the gather.  matches: int32 [B, stride, 4] (DMatch rows), count: int32 [B], kp1: float32 [B, nq, 2], kp2:
+    float32 [B, nt, 2] CUDA/HIP tensors; size1 / size2: (width, height).  Returns dict of torch tensors matches [B, stride, 4] (the kept
+    matches, compacted in order), count [B], inliers [B] (the filter's count).  min_final_rule: a list passes through unchanged unless
+    the filter kept at least 2 matches.  Enqueues on `stream` (None = torch's current stream) without synchronising."""
+    import torch
+
+    if matches.dim() == 2:
+        matches, count, kp1, kp2 = matches.unsqueeze(0), count.reshape(1), kp1.unsqueeze(0), kp2.unsqueeze(0)
+    assert matches.is_cuda and matches.dtype == torch.int32 and matches.is_contiguous() and matches.shape[2] == 4
+    assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()
+    assert kp1.is_cuda and kp2.is_cuda and kp1.dtype == torch.float32 and kp2.dtype == torch.float32 and kp1.is_contiguous() and kp2.is_contiguous()
+    B, stride = matches.shape[0], matches.shape[1]
+    assert count.shape == (B,) and kp1.shape[0] == B and kp2.shape[0] == B and kp1.shape[2] == 2 and kp2.shape[2] == 2
+    ctx = ctx or default_context(matches.device.index or 0)
+    if out is None:
+        out = {
+            "matches": torch.empty_like(matches),
+            "count": torch.empty((B,), dtype=torch.int32, device=matches.device),
+            "inliers": torch.empty((B,), dtype=torch.int32, device=matches.device),
+        }
+    rc = ctx.lib.mlpl_gms_filter_matches_dev(
+        ctx.handle, B, matches.data_ptr(), stride, count.data_ptr(), kp1.data_ptr(), kp1.shape[1], kp2.data_ptr(), kp2.shape[1],
+        int(size1[0]), int(size1[1]), int(size2[0]), int(size2[1]), 1 if use_scale else 0, 1 if use_rotation else 0,
+        1 if min_final_rule else 0, out["matches"].data_ptr(), out["count"].data_ptr(), out["inliers"].data_ptr(),
+        torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
+    check(rc, "mlpl_gms_filter_matches_dev")
+    return out

@@ -168,3 +168,40 @@ def vfc_scene(kind: str, n: int, seed: int = 0, width: float = 1280.0, height: f
         x2 = x2 + rng.normal(0.0, 1.0, (n, 2)) * sigma[:, None]
         inlier = sigma < 3.0
     return dict(x1=np.ascontiguousarray(x1, np.float32), x2=np.ascontiguousarray(x2, np.float32), inlier=inlier, sigma=sigma)
+
+
+def gms_scene(kind: str, n: int, seed: int = 0, width: int = 1280, height: int = 720):
+    """Keypoints and matches for the GMS match filter (matchinglib::filterMatchesGMS).  Both images are width x height.
+    kind "smooth": a smooth motion field (3 % of shrink, a shift, a slow sine) with 1 px of noise; a quarter of the matches random.
+    kind "rot90":  the same with the field rotated by 90 degrees about the image centre (in normalised coordinates, so that the 20 x 20
+                   grid maps onto itself): the filter finds it with the rotation switch only, at rotation type 6.
+    kind "scale2": the first image's points lie in its central half and the second image's content is scaled by 2 about the centre: the
+                   filter finds it on the 10 x 10 right grid (scale level 1).
+    kind "sparse": the smooth field with 70 % random matches -- few consistent matches per cell.
+    Match i joins keypoint i of the first image and keypoint perm[i] of the second.
+    Returns dict(kp1, kp2: float32 [n, 2], matches: DMatch rows [n], size1, size2: (width, height), inlier: bool [n])."""
+    if kind not in ("smooth", "rot90", "scale2", "sparse"):
+        raise ValueError("kind is 'smooth', 'rot90', 'scale2' or 'sparse'")
+    rng = np.random.default_rng(20261811 + 104729 * seed + {"smooth": 0, "rot90": 1, "scale2": 2, "sparse": 3}[kind])
+    wh = np.array([width, height], np.float64)
+    u = rng.random((n, 2))
+    if kind == "scale2":
+        u = 0.25 + 0.5 * u
+        v = 0.5 + 2.0 * (u - 0.5)
+    else:
+        v = 0.015 + 0.97 * u + 0.01 * np.sin(3.0 * u[:, ::-1])
+        if kind == "rot90":
+            v = np.stack([1.0 - v[:, 1], v[:, 0]], axis=1)
+    x1 = u * wh
+    x2 = v * wh + rng.normal(0.0, 1.0, (n, 2))
+    out = np.zeros(n, bool)
+    out[rng.permutation(n)[: int(round((0.7 if kind == "sparse" else 0.25) * n))]] = True
+    x2[out] = rng.random((int(out.sum()), 2)) * wh
+    x2 = np.clip(x2, 0.0, wh - 0.01)
+    perm = rng.permutation(n)
+    kp2 = np.empty((n, 2), np.float32)
+    kp2[perm] = x2.astype(np.float32)
+    matches = np.zeros(n, np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")]))
+    matches["queryIdx"], matches["trainIdx"] = np.arange(n), perm
+    matches["distance"] = rng.integers(0, 64, n).astype(np.float32)
+    return dict(kp1=np.ascontiguousarray(x1, np.float32), kp2=kp2, matches=matches, size1=(width, height), size2=(width, height), inlier=~out)

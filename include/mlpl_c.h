@@ -581,7 +581,8 @@ int mlpl_ransac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double 
  * MLPL_E_FAILED (reference: false: fewer than 6 starting inliers, or the first step lost too many) with E and mask untouched.
  * As the reference: a solver nibble of 0 or above 4 ("not supported") and steps = 0 return 0 with E unchanged and the mask made 0 / 1;
  * with PR_NISTER / PR_STEWENIUS, weight bits other than 0x10 / 0x20 run the unweighted solver.
- * Deliberate deviations: PR_KNEIP (0x4) returns MLPL_E_UNSUPPORTED (OpenGV's eigensolver is not built); PR_8PT with weight bits other
+ * Deliberate deviations: PR_KNEIP (0x4) returns MLPL_E_UNSUPPORTED from this entry and its batch form, which carry no R / t (the solver
+ * is built: mlpl_refine_essential_linear_rt below); PR_8PT with weight bits other
  * than 0x10 / 0x20 / 0x30 returns MLPL_E_BAD_INPUT (the reference reads uninitialised weights there); a PR_8PT fit on fewer than 8
  * points counts as a failed refit (the reference's assert(n > 7) is compiled out and its null space is not unique).  The method is
  * checked before anything else.  R / t of the reference are the caller's business: with every solver built here a passed R is cleared.
@@ -596,6 +597,36 @@ int mlpl_refine_essential_linear(mlpl_ctx *ctx, const double *p1, const double *
 int mlpl_refine_essential_linear_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                                            const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
                                            uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, void *stream);
+/*
+ * refineEssentialLinear with R and t: the two entries above plus PR_KNEIP (0x4), OpenGV's eigensolver (Kneip & Lynen) on the current
+ * inliers in list order -- the only solver that returns the pose itself (csrc/kneip_refine_impl.h).  Added arguments: R[9] in / out (row
+ * major), t[3] out (unit length), *rt_valid in: R holds a start rotation (0 = the reference's empty R) / out: R and t were written -- the
+ * reference's rule (pose_linear_refinement.cpp:272-293): at least one step was accepted; otherwise the reference clears R, here R and t
+ * stay and *rt_valid is 0.  Without a usable start (rt_valid 0, or R not a rotation by isMatRoationMat) step 0 makes up to 12 attempts from
+ * the identity perturbed in Cayley space by (rand() / RAND_MAX - 0.5) * 0.2 per component, rand() being glibc's stream after srand(seed),
+ * attempt a using raw values 3 a .. 3 a + 2; an attempt is taken when its count at th^2 is at least (1 - max_loss) times the inliers.
+ * *attempts_used (may be NULL): attempts made, 0 when R was the start.  When all 12 fail the reference returns true with E unchanged, the
+ * mask made 0 / 1 and R cleared, and so does this (0, steps_done 0, rt_valid 0); the same when the solver rejects step 0 from a given R.
+ * Per step: kneip_sums_kernel (the 36 distinct summation terms, bit-identical to the host's dgm::eig_sums), the Levenberg-Marquardt solve
+ * on the host (csrc/usac_degen_math.h), kneip_eval_kernel (all candidates of the step in one launch).  The weight bits are accepted and
+ * change nothing (OpenGV's useWeights stays false in the reference).  Deviation: with weight bits other than 0x10 / 0x20 the reference sums
+ * its zero-padded inlier vector until the first accepted step (n - count copies of correspondence 0); here always the list itself.
+ * Solver nibbles other than 0x4 run the kernel of the entries above and clear *rt_valid.  Returns as mlpl_refine_essential_linear;
+ * MLPL_E_FAILED leaves every in / out argument untouched.
+ */
+int mlpl_refine_essential_linear_rt(mlpl_ctx *ctx, const double *p1, const double *p2, int n, int method, double th, int steps, double th_mult,
+                                    double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done, double R[9], double t[3],
+                                    int *rt_valid, uint32_t seed, int *attempts_used);
+/* The batch form, in the layout of mlpl_refine_essential_linear_batch_dev: R + 9 b, t + 3 b, rt_valid[b] (host, as above), seeds[b] (host;
+ * NULL = 1 for every problem), attempts_used[b] (host, may be NULL).  The batch moves in lockstep over the steps (two launches and two
+ * host hops per step); its problems are solved by a few host threads.  Every problem's result is bit-identical to the single entry's. */
+int mlpl_refine_essential_linear_rt_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                              const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
+                                              uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, double *R, double *t,
+                                              int32_t *rt_valid, const uint32_t *seeds, int32_t *attempts_used, void *stream);
+/* Where the last mlpl_refine_essential_linear_rt(_batch_dev) call with solver 0x4 spent its time, seconds: {kneip_sums_kernel,
+ * host solves, kneip_eval_kernel, uploads + downloads + synchronisation}.  Measured only while enabled (enable: 1 / 0 / -1 = leave). */
+int mlpl_kneip_refine_times(mlpl_ctx *ctx, int enable, double out[4]);
 /* mlpl_recover_pose_dev for a batch in the same layout (the batched cheirality step of the pair entries): E + 9 b (host), d_masks NULL (all
  * points) or [n_problems][stride] on the device (in / out: the chosen candidate's mask), n_good[b], R + 9 b, t + 3 b (host).  Every problem's
  * result equals what mlpl_recover_pose_dev returns for it. */

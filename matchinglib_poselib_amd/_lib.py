@@ -157,6 +157,12 @@ _SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "mlpl_refine_essential_linear_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double,
                                                        c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_refine_essential_linear_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_double, c_double, c_double,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u32, c_void_p]),
+    "mlpl_refine_essential_linear_rt_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double,
+                                                          c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_kneip_refine_times": (c_int, [c_void_p, c_int, c_void_p]),
     "mlpl_recover_pose_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
     "mlpl_vfc_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -69,6 +69,7 @@ std::vector<double> points64(cv::InputArray pa, int &n) {
 }  // namespace
 
 mlpl_ctx *mlpl_facade_default_ctx() { return default_ctx(); }
+unsigned mlpl_facade_draw_seed() { return g_seed_fixed ? g_seed : (unsigned)std::time(nullptr); }
 
 namespace matchinglib {
 

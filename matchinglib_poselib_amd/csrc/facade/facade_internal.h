@@ -5,3 +5,7 @@
 // The calling thread's library context (created on first use on device $MLPL_DEVICE or 0).  Throws cv::Exception when no gfx950 device
 // is usable: the drop-in has no CPU fallback.
 mlpl_ctx *mlpl_facade_default_ctx();
+
+// One draw from the stream poselib::setRansacSeed controls on the calling thread: the fixed seed, or the clock as the reference's estimators
+// take it.
+unsigned mlpl_facade_draw_seed();

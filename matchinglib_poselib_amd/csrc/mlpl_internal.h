@@ -105,6 +105,8 @@ struct mlpl_ctx {
                             // 0 = knn_l2_merge_kernel + ratio_count_kernel (A/B, tests)
     int dbg_l2_match[4];    // mlpl_debug_last_l2_match: {path, train splits, counts by the fold, launches} of the last float knn / match call
     void *l2_flag_ptr;  // the flag buffer l2_gen counts for
+    int kneip_times_on;     // mlpl_kneip_refine_times: measure the next PR_KNEIP refinements
+    double kneip_times[4];  // {sums kernel, host solves, eval kernel, hops} of the last one, seconds
     int num_cus;
     // tuning knobs (mlpl_set_option)
     int opt_hamming_variant;        // 3 = fp4 matrix-core kernel (default), 0 = LDS-tiled VALU, 1 = scalar-operand VALU, 2 = one wave per block

@@ -3319,6 +3319,7 @@ void hub_streams_free(void *p) {
 #include "pair_batch_impl.h"
 #include "pair_batch_usac.h"
 #include "linear_refine_impl.h"
+#include "kneip_refine_impl.h"
 
 void free_rand_cache(void *p) { delete static_cast<RandCache *>(p); }
 
@@ -4162,6 +4163,87 @@ int mlpl_refine_essential_linear_batch_dev(mlpl_ctx *ctx, int n_problems, const 
     }
     return linear_refine_batch(ctx, n_problems, d_p1, d_p2, stride, counts, th, method, steps, th_mult, ph_mult, max_loss, E, d_masks, n_inliers,
                                status, steps_done, pick_stream(ctx, stream), "mlpl_refine_essential_linear_batch_dev");
+}
+
+static int kneip_refine_entry(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, const double *th, int method,
+                              int steps, double th_mult, double ph_mult, double max_loss, double *E, uint8_t *d_masks, int32_t *n_inliers, int32_t *status,
+                              int32_t *steps_done, double *R, double *t, int32_t *rt_valid, const uint32_t *seeds, int32_t *attempts_used, hipStream_t s,
+                              const char *who) {
+    KneipTimes tm{0, 0, 0, 0};
+    const int rc = kneip_refine_batch(ctx, B, d_p1, d_p2, stride, counts, th, method, steps, th_mult, ph_mult, max_loss, E, d_masks, n_inliers, status,
+                                      steps_done, R, t, rt_valid, seeds, attempts_used, s, who, ctx->kneip_times_on ? &tm : nullptr);
+    ctx->kneip_times[0] = tm.sums, ctx->kneip_times[1] = tm.solve, ctx->kneip_times[2] = tm.eval, ctx->kneip_times[3] = tm.hops;
+    return rc;
+}
+
+int mlpl_refine_essential_linear_rt(mlpl_ctx *ctx, const double *p1, const double *p2, int n, int method, double th, int steps, double th_mult,
+                                    double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done, double R[9], double t[3],
+                                    int *rt_valid, uint32_t seed, int *attempts_used) {
+    static const char *who = "mlpl_refine_essential_linear_rt";
+    int rc;
+    if ((method & 0xF) != 4 || method < 0 || method > 0xFF) {
+        LinRefineArgs probe{};
+        if ((rc = linear_refine_method(method, probe, who))) return rc;
+    }
+    if (!ctx || !p1 || !p2 || !E || !mask || n < 0 || !R || !t || !rt_valid) {
+        set_error("%s: bad arguments", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nn = (size_t)std::max(n, 1);
+    void *dp1, *dp2, *dmask;
+    if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
+    if ((rc = ws_get(ctx, WS_MATCH, nn, &dmask))) return rc;
+    if (n > 0) {
+        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    const int32_t count = n;
+    int32_t st = 0, ninl = 0, done = 0, valid = *rt_valid ? 1 : 0, attempts = 0;
+    double E_io[9], R_io[9], t_io[3] = {t[0], t[1], t[2]};
+    std::memcpy(E_io, E, 72);
+    std::memcpy(R_io, R, 72);
+    if ((rc = kneip_refine_entry(ctx, 1, (const double *)dp1, (const double *)dp2, (int)nn, &count, &th, method, steps, th_mult, ph_mult, max_loss, E_io,
+                                 (uint8_t *)dmask, &ninl, &st, &done, R_io, t_io, &valid, &seed, &attempts, s, who)))
+        return rc;
+    if (attempts_used) *attempts_used = attempts;
+    if (st != 0) return st;
+    if (n > 0) MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    std::memcpy(E, E_io, 72);
+    if (valid) {
+        std::memcpy(R, R_io, 72);
+        std::memcpy(t, t_io, 24);
+    }
+    *rt_valid = valid;
+    if (n_inliers) *n_inliers = ninl;
+    if (steps_done) *steps_done = done;
+    return MLPL_OK;
+}
+
+int mlpl_refine_essential_linear_rt_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                              const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
+                                              uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, double *R, double *t,
+                                              int32_t *rt_valid, const uint32_t *seeds, int32_t *attempts_used, void *stream) {
+    if (!ctx) {
+        set_error("mlpl_refine_essential_linear_rt_batch_dev: ctx is mandatory");
+        return MLPL_E_BAD_INPUT;
+    }
+    return kneip_refine_entry(ctx, n_problems, d_p1, d_p2, stride, counts, th, method, steps, th_mult, ph_mult, max_loss, E, d_masks, n_inliers, status,
+                              steps_done, R, t, rt_valid, seeds, attempts_used, pick_stream(ctx, stream), "mlpl_refine_essential_linear_rt_batch_dev");
+}
+
+int mlpl_kneip_refine_times(mlpl_ctx *ctx, int enable, double out[4]) {
+    if (!ctx) {
+        set_error("mlpl_kneip_refine_times: ctx is mandatory");
+        return MLPL_E_BAD_INPUT;
+    }
+    if (enable >= 0) ctx->kneip_times_on = enable ? 1 : 0;
+    if (out)
+        for (int k = 0; k < 4; ++k) out[k] = ctx->kneip_times[k];
+    return MLPL_OK;
 }
 
 int mlpl_recover_pose_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,

@@ -765,9 +765,15 @@ inline void eigen_diag_order3(const double *M, double *d) {
 
 // opengv::relative_pose::eigensolver on n correspondences (f1 = adapter view 1, f2 = view 2), starting from R_init.  t is not normalised:
 // its length is what OpenGV returns (the root sum of squares of the eigenvalues at positions 1 and 2).
+// eigensolver_sums: the same from the summation terms and the first correspondence (f1_0, f2_0: the translation's sign test) -- what the
+// linear refinement (kneip_refine_impl.h) calls with sums accumulated on the device.
+inline void eigensolver_sums(const EigSums &Sx, const double *f1_0, const double *f2_0, const double *R_init, double *R, double *t);
 inline void eigensolver(const double (*f1)[3], const double (*f2)[3], int n, const double *R_init, double *R, double *t) {
     EigSums Sx;
     eig_sums(f1, f2, n, Sx);
+    eigensolver_sums(Sx, f1[0], f2[0], R_init, R, t);
+}
+inline void eigensolver_sums(const EigSums &Sx, const double *f1_0, const double *f2_0, const double *R_init, double *R, double *t) {
     double x[3];
     rot_to_cayley(R_init, x);
     lm_minimise_gradient(Sx, x);
@@ -785,8 +791,8 @@ inline void eigensolver(const double (*f1)[3], const double (*f2)[3], int n, con
     const double mag = std::sqrt(d[1] * d[1] + d[2] * d[2]);
     for (int k = 0; k < 3; ++k) t[k] = mag * vec[k0][k];
     double f2r[3], flow[3];
-    matvec(R, f2[0], f2r);
-    for (int k = 0; k < 3; ++k) flow[k] = f1[0][k] - f2r[k];
+    matvec(R, f2_0, f2r);
+    for (int k = 0; k < 3; ++k) flow[k] = f1_0[k] - f2r[k];
     if (flow[0] * t[0] + flow[1] * t[1] + flow[2] * t[2] < 0.0)
         for (int k = 0; k < 3; ++k) t[k] = -t[k];
 }

@@ -336,6 +336,79 @@ def refine_essential_linear_batch(d_p1, d_p2, counts, E, d_masks, th, refine_met
     return dict(status=status, E=E_io.reshape(B, 3, 3), n_inliers=ninl, steps_done=done)
 
 
+def refine_essential_linear_rt(p1, p2, E, mask, refine_method: int = PR_KNEIP | PR_PSEUDOHUBER_WEIGHTS, R=None, th: float = 0.008,
+                               num_iterative_steps: int = 4, threshold_multiplier: float = 2.0, pseudo_huber_threshold_multiplier: float = 0.1,
+                               max_relative_inlier_cnt_loss: float = 0.15, seed: int = 1, ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_essential_linear_rt: refineEssentialLinear with R and t, i.e. with PR_KNEIP (OpenGV's eigensolver) among the solvers.
+    R = a start rotation or None (the reference's empty R: up to 12 perturbed-identity starts drawn from srand(seed)).  Returns
+    dict(ok, E, mask, n_inliers, steps_done, rt_valid, R, t, attempts_used); R / t are None unless rt_valid (the reference clears R)."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    if p2.shape[0] != n:
+        raise ValueError("p1 and p2 differ in length")
+    E_io = np.array(E, np.float64).reshape(3, 3).copy()
+    m = np.array(mask, np.uint8).reshape(-1).copy()
+    if m.shape[0] != n:
+        raise ValueError("the mask must hold one byte per correspondence")
+    R_io = np.zeros((3, 3)) if R is None else np.array(R, np.float64).reshape(3, 3).copy()
+    t_io = np.zeros(3)
+    ninl, done, valid, used = C.c_int(0), C.c_int(0), C.c_int(0 if R is None else 1), C.c_int(0)
+    rc = ctx.lib.mlpl_refine_essential_linear_rt(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, int(refine_method), float(th), int(num_iterative_steps),
+                                                 float(threshold_multiplier), float(pseudo_huber_threshold_multiplier),
+                                                 float(max_relative_inlier_cnt_loss), E_io.ctypes.data, m.ctypes.data, C.byref(ninl), C.byref(done),
+                                                 R_io.ctypes.data, t_io.ctypes.data, C.byref(valid), int(seed) & 0xFFFFFFFF, C.byref(used))
+    if rc not in (0, _lib.MLPL_E_FAILED):
+        raise MlplError(rc, "mlpl_refine_essential_linear_rt", _lib.last_error())
+    ok = rc == 0
+    posed = ok and valid.value != 0
+    return dict(ok=ok, E=E_io, mask=m, n_inliers=ninl.value if ok else 0, steps_done=done.value if ok else 0, rt_valid=posed,
+                R=R_io if posed else None, t=t_io if posed else None, attempts_used=used.value)
+
+
+def refine_essential_linear_rt_batch(d_p1, d_p2, counts, E, d_masks, th, refine_method: int = PR_KNEIP | PR_PSEUDOHUBER_WEIGHTS, R=None, rt_valid=None,
+                                     seeds=None, num_iterative_steps: int = 4, threshold_multiplier: float = 2.0,
+                                     pseudo_huber_threshold_multiplier: float = 0.1, max_relative_inlier_cnt_loss: float = 0.15,
+                                     ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_essential_linear_rt_batch_dev in the layout of refine_essential_linear_batch.  R: [B, 3, 3] start rotations (host) with
+    rt_valid [B] saying which of them count (None: all when R is given, none otherwise); seeds [B] or None (1).  Returns dict(status, E,
+    n_inliers, steps_done, R [B, 3, 3], t [B, 3], rt_valid [B], attempts_used [B]); R[b] / t[b] are what was passed in / zero unless rt_valid[b]."""
+    import torch
+
+    B, stride = d_p1.shape[0], d_p1.shape[1]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (B, stride, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    assert d_masks.is_cuda and d_masks.dtype == torch.uint8 and d_masks.shape == (B, stride) and d_masks.is_contiguous()
+    ctx = ctx or default_context(d_p1.device.index or 0)
+    cn = np.ascontiguousarray(counts, np.int32).reshape(B)
+    thv = np.ascontiguousarray(np.broadcast_to(np.asarray(th, np.float64), (B,)))
+    E_io = np.array(E, np.float64).reshape(B, 9).copy()
+    R_io = np.zeros((B, 9)) if R is None else np.array(R, np.float64).reshape(B, 9).copy()
+    valid = np.full(B, 0 if R is None else 1, np.int32) if rt_valid is None else np.array(rt_valid, np.int32).reshape(B).copy()
+    sd = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, np.int64) & 0xFFFFFFFF, np.uint32).reshape(B)
+    t_io = np.zeros((B, 3))
+    ninl, status, done, used = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    rc = ctx.lib.mlpl_refine_essential_linear_rt_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, thv.ctypes.data,
+                                                           int(refine_method), int(num_iterative_steps), float(threshold_multiplier),
+                                                           float(pseudo_huber_threshold_multiplier), float(max_relative_inlier_cnt_loss),
+                                                           E_io.ctypes.data, d_masks.data_ptr(), ninl.ctypes.data, status.ctypes.data, done.ctypes.data,
+                                                           R_io.ctypes.data, t_io.ctypes.data, valid.ctypes.data, None if sd is None else sd.ctypes.data,
+                                                           used.ctypes.data, torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_refine_essential_linear_rt_batch_dev", _lib.last_error())
+    return dict(status=status, E=E_io.reshape(B, 3, 3), n_inliers=ninl, steps_done=done, R=R_io.reshape(B, 3, 3), t=t_io, rt_valid=valid,
+                attempts_used=used)
+
+
+def kneip_refine_times(ctx: Context, enable: int = -1) -> dict:
+    """mlpl_kneip_refine_times: switch the per-part timing of the PR_KNEIP refinement on / off (enable 1 / 0; -1 leaves it) and return the
+    last call's split in seconds: dict(sums, solve, eval, hops)."""
+    out = np.zeros(4)
+    rc = ctx.lib.mlpl_kneip_refine_times(ctx.handle, int(enable), out.ctypes.data)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_kneip_refine_times", _lib.last_error())
+    return dict(sums=float(out[0]), solve=float(out[1]), eval=float(out[2]), hops=float(out[3]))
+
+
 def recover_pose_batch(d_p1, d_p2, counts, E, d_masks=None, dist: float = 50.0, ctx: Optional[Context] = None) -> dict:
     """mlpl_recover_pose_batch_dev: the cheirality step (getPoseTriangPts without points) for a batch in the layout above; d_masks (uint8 CUDA
     tensor [B, stride] or None = all points) receives the chosen candidate's mask.  Returns dict(n_good [B], R [B, 3, 3], t [B, 3])."""

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "mlpl_internal.h"
@@ -377,9 +378,9 @@ struct HammingFuse {
 // XP (option hamming_expand_inkernel, NW = 8 and PD = 2 only) = the workgroup expands the train tiles it consumes ITSELF: `tsrc` is the raw
 // train set (rows of 8 words, `t_batch` words per image pair) instead of the fragment buffer, hamming_expand_kernel does not run and the
 // 4x expanded copy of the train set is neither written to memory nor read back.
-//   * Raw ring, NR = 4 slots of 1 KiB: waves 0..3 copy a quarter each of the raw tile (32 rows x 8 words, contiguous in memory) with 4-byte
-//     LDS-DMA, a scalar base plus a 32-bit lane offset that is clamped to the last word of the image pair's train set (the rows of a ragged last
-//     tile behind it start at -inf through its C and never count; nothing past the pair's rows is read).
+//   * Raw ring, NR = 4 slots of 1 KiB, raw tile t in slot (t + 3) & 3: waves 0..3 copy a quarter each of the raw tile (32 rows x 8 words,
+//     contiguous in memory) with 4-byte LDS-DMA, a scalar base plus a 32-bit lane offset that is clamped to the last word of the image pair's
+//     train set (the rows of a ragged last tile behind it start at -inf through its C and never count; nothing past the pair's rows is read).
 //   * Fragment ring, 2 slots of 4 KiB in the fragment order the tile body reads: lane (r, h) of K-step s holds the four planes of raw word
 //     4 h + s of row r.  Wave w expands word w of all 32 rows: lane l reads the word of row l >> 1 and writes dwords 2 (l & 1), 2 (l & 1) + 1,
 //     so a wave writes 512 CONTIGUOUS bytes with ds_write_b64 (no bank conflict; the read is a 4-way conflict of one ds_read_b32).
@@ -388,10 +389,20 @@ struct HammingFuse {
 //     fragments of tile `it`, expands it into fragment slot (it + 1) & 1 and runs the body of tile `it`.  The prologue does the same for tile 0.
 //     Slot reuse: a wave past the barrier of iteration `it` knows that every wave has finished the body of it - 1 (its MFMAs consumed those
 //     reads), so fragment slot (it + 1) & 1 is free, and that every wave's writes of tile `it` have completed (lgkmcnt(0) before the barrier).
-//     Raw slot (it + 2) & 3 last held tile it - 2, read behind the barrier of iteration it - 3 and complete before that of it - 2; the copy
+//     The raw slot of tile it + 2 last held tile it - 2, read behind the barrier of iteration it - 3 and complete before that of it - 2; the copy
 //     is issued behind the barrier of it - 1.  The tile after the last one does not exist: the last iteration expands a stale raw slot into the
 //     free fragment slot, which nobody reads -- cheaper than a branch around the hand-scheduled LDS sequence.
-template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false>
+//   * Unrolled form (the production instance, ST = false): while a PAIR of tiles it = 2 p, 2 p + 1 with both its copies (tiles it + 2, it + 3) lies
+//     inside the split's full tiles, the pair runs as straight-line code -- per tile still: the copy of tile it + 2, vmcnt(1) lgkmcnt(0), one
+//     s_barrier, the raw word of tile it + 1 and the fragments of tile `it` read, fragment slot (it + 1) & 1 written, the body.  It is the
+//     protocol above iteration by iteration, so the slot-reuse argument holds word for word; only the addresses are formed differently: the
+//     fragment slots are it & 1 = J and (it + 1) & 1, the raw slot read is (it + 4) & 3 = 2 (p & 1) + J, so everything but 2 (p & 1) is a
+//     constant in an instruction's offset field, and the lane parts are formed once in front of the loop.  The first KS waves and the others
+//     run their own copy of the loop (no test of the role per tile).  The rolled loop takes what is left (at most three full tiles) with the
+//     vmcnt(0) waits of the last two iterations, the clamp of the copy -- which can bind in the last tile only, never inside a pair -- and the
+//     stale-slot expansion; the ragged tile follows as before.
+//   * ST (option hamming_stamps = 1) = the instance with the per-tile clock stamp; it keeps the rolled loop throughout.
+template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false, bool ST = false>
 __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     const uint32_t *__restrict__ qw, size_t q_batch_words, const void *__restrict__ tsrc, size_t t_batch, int nq, int nt,
     int rows_per_split, int nsplit, int dshift, int qblocks, int n_items, uint2 *__restrict__ part,
@@ -442,13 +453,18 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     const uint4 *tbase = (const uint4 *)tsrc + (size_t)b * t_batch + (size_t)tile0 * KS * 64 + (size_t)w * 64;  // wave-uniform
     const char *rbase = (const char *)tsrc + ((size_t)b * t_batch + (size_t)tile0 * 32 * (2 * KS)) * 4;         // wave-uniform
     const uint32_t raw_last = (uint32_t)(nt - row0) * (8u * KS) - 4u;   // byte offset of the pair's last train word behind rbase
+    // XP: the lane parts of every address of the tile loop are formed ONCE (below, behind copies the compiler cannot see through: it would
+    // re-form them from the lane index per tile, or keep the lane index alive beside them -- 128 registers are all in use): where the lane reads
+    // the fragments (xp_frag), its raw word (xp_raw), where it writes its two planes (xp_plane), the plane shift l & 1 (xp_sh), and the byte
+    // offset behind rbase of its word of raw tile xp_it0 + PD (xp_voff; the unrolled loop advances both by two tiles at a time).
+    uint32_t xp_frag = 0, xp_raw = 0, xp_plane = 0, xp_sh = 0, xp_voff = 0;
+    int xp_it0 = 0;
     auto copy_tile = [&](int t_rel) {
         if (NW > KS && w >= KS) return;  // (wave-uniform: the K-steps are copied by the first KS waves)
         if constexpr (XP) {
-            const uint32_t lx = (uint32_t)l;
-            const uint32_t off = min((uint32_t)t_rel * 1024u + (uint32_t)w * 256u + lx * 4u, raw_last);
+            const uint32_t off = min(xp_voff + (uint32_t)(t_rel - PD - xp_it0) * 1024u, raw_last);
             __builtin_amdgcn_global_load_lds((const void *)(rbase + off),
-                                             (__attribute__((address_space(3))) void *)&raw_ring[(t_rel & (NR - 1)) * 256 + w * 64], 4, 0, 0);
+                                             (__attribute__((address_space(3))) void *)&raw_ring[((t_rel + NR - 1) & (NR - 1)) * 256 + w * 64], 4, 0, 0);
         } else {
             __builtin_amdgcn_global_load_lds((const void *)(tbase + (size_t)t_rel * KS * 64 + l),
                                              (__attribute__((address_space(3))) void *)&ring[t_rel & (NB - 1)][w * 64], 16, 0, 0);
@@ -463,46 +479,23 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     const uint32_t raw_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&raw_ring[0];
     const uint32_t frag_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0];
     // XP: where this lane reads its raw word of tile `t_rel` and where it writes the two planes it forms (see the protocol above)
-    auto raw_addr = [&](int t_rel, uint32_t lx) { return raw_lds + (uint32_t)(t_rel & (NR - 1)) * 1024u + (uint32_t)w * 4u + (lx >> 1) * 32u; };
-    auto plane_addr = [&](int t_rel, uint32_t lx) {
-        const uint32_t base = frag_lds + (uint32_t)(t_rel & 1) * (KS * 1024u) + (uint32_t)(w & 3) * 1024u + (uint32_t)(w >> 2) * 512u;   // scalar
-        return base + lx * 8u;
-    };
-    auto expand_pair = [&](uint32_t x, uint32_t lx) {
-        const uint32_t y = x >> (lx & 1u);   // dwords 0, 1 = planes 0, 2; dwords 2, 3 = planes 1, 3
+    if constexpr (XP) {
+        const uint32_t lx = (uint32_t)l;
+        xp_frag = ring_lds;
+        xp_raw = raw_lds + (uint32_t)w * 4u + (lx >> 1) * 32u;
+        xp_plane = frag_lds + (uint32_t)(w & 3) * 1024u + (uint32_t)(w >> 2) * 512u + lx * 8u;
+        xp_sh = lx & 1u;
+        xp_voff = PD * 1024u + (uint32_t)w * 256u + lx * 4u;
+        asm volatile("" : "+v"(xp_frag), "+v"(xp_raw), "+v"(xp_plane), "+v"(xp_sh), "+v"(xp_voff));
+    }
+    auto raw_addr = [&](int t_rel) { return xp_raw + (uint32_t)((t_rel + NR - 1) & (NR - 1)) * 1024u; };   // (raw tile t in slot (t + 3) & 3)
+    auto plane_addr = [&](int t_rel) { return xp_plane + (uint32_t)(t_rel & 1) * (KS * 1024u); };
+    auto expand_pair = [&](uint32_t x) {
+        const uint32_t y = x >> xp_sh;   // dwords 0, 1 = planes 0, 2; dwords 2, 3 = planes 1, 3
         return u32x2{expand_plane0(y, 0x22222222u), expand_plane2(y, 0x22222222u)};
     };
-    auto tile_body = [&](int it, const v16f &c0) {
-        u32x4 r[KS];
-        const uint32_t addr = ring_lds + (uint32_t)(it & (NB - 1)) * (KS * 1024u);
-        if constexpr (XP) {
-            uint32_t lx = (uint32_t)l, x;
-            const uint32_t ra = raw_addr(it + 1, lx), wa = plane_addr(it + 1, lx);
-            asm volatile(
-                "ds_read_b32 %4, %6\n\tds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:1024\n\tds_read_b128 %2, %5 offset:2048\n\t"
-                "ds_read_b128 %3, %5 offset:3072"
-                : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(x)
-                : "v"(addr), "v"(ra)
-                : "memory");
-            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x));
-            const u32x2 o = expand_pair(x, lx);
-            asm volatile("ds_write_b64 %0, %1" ::"v"(wa), "v"(o) : "memory");
-            // (in order behind the four fragment reads: K-step s is complete once at most 4 - s operations are outstanding)
-            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r[0]));
-            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
-            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
-            asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
-        } else {
-        asm volatile(
-            "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
-            : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-            : "v"(addr)
-            : "memory");
-        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[0]));
-        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[1]));
-        asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[2]));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[3]));
-        }
+    // the arithmetic of one tile: r[] = the tile's four K-steps in fragment order
+    auto tile_math = [&](const u32x4 (&r)[KS], const v16f &c0) {
         uint4 a[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) a[s] = make_uint4(r[s].x, r[s].y, r[s].z, r[s].w);
@@ -533,6 +526,39 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
             }
         }
     };
+    auto tile_body = [&](int it, const v16f &c0) {
+        u32x4 r[KS];
+        const uint32_t addr = (XP ? xp_frag : ring_lds) + (uint32_t)(it & (NB - 1)) * (KS * 1024u);
+        if constexpr (XP) {
+            uint32_t x;
+            const uint32_t ra = raw_addr(it + 1), wa = plane_addr(it + 1);
+            asm volatile(
+                "ds_read_b32 %4, %6\n\tds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:1024\n\tds_read_b128 %2, %5 offset:2048\n\t"
+                "ds_read_b128 %3, %5 offset:3072"
+                : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(x)
+                : "v"(addr), "v"(ra)
+                : "memory");
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x));
+            const u32x2 o = expand_pair(x);
+            asm volatile("ds_write_b64 %0, %1" ::"v"(wa), "v"(o) : "memory");
+            // (in order behind the four fragment reads: K-step s is complete once at most 4 - s operations are outstanding)
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r[0]));
+            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
+            asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
+        } else {
+        asm volatile(
+            "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
+            : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
+            : "v"(addr)
+            : "memory");
+        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[0]));
+        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[1]));
+        asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[2]));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[3]));
+        }
+        tile_math(r, c0);
+    };
 
 #pragma unroll
     for (int t = 0; t < PD; ++t)
@@ -562,11 +588,10 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         // wave expands its word of the tile into fragment slot 0
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        uint32_t lx = (uint32_t)l, x;
-        asm volatile("" : "+v"(lx));
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(x) : "v"(raw_addr(0, lx)) : "memory");
-        const u32x2 o = expand_pair(x, lx);
-        asm volatile("ds_write_b64 %0, %1" ::"v"(plane_addr(0, lx)), "v"(o) : "memory");
+        uint32_t x;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(x) : "v"(raw_addr(0)) : "memory");
+        const u32x2 o = expand_pair(x);
+        asm volatile("ds_write_b64 %0, %1" ::"v"(plane_addr(0)), "v"(o) : "memory");
     }
 
     // only the last tile of the train set can be ragged; it runs after the loop with its own C (rows >= nt start at -inf and stay there)
@@ -620,18 +645,82 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         else if (p == 2) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(3);
     };
-    for (int it = 0; it < nfull; ++it) {
+    int it = 0;
+    if constexpr (XP && !ST) {
+        // Steady state, unrolled by the period of the fragment ring: pairs of tiles it = 2 p + J.  The fragment slots and, thanks to the rotated
+        // raw slots (tile t in slot (t + 3) & 3: the pair reads raw slots 2 (p & 1) + J), the raw slot's low bit are constants of J and sit in the
+        // offset fields of the LDS instructions; the raw slot's high bit is one add to xp_raw per PAIR.  A pair runs only while it + 3 < nfull,
+        // so both tiles are full, have their copy of tile it + PD to issue (always vmcnt(1)) and copy a FULL tile: the clamp to raw_last
+        // cannot bind and is left to the rolled tail below, which also takes an odd tile, the last PD tiles and the stale-slot expansion of
+        // the last iteration.  (The ring period is four tiles; four tile bodies in one loop do not register-allocate in 128 VGPRs -- 276
+        // bytes of scratch per lane -- and two do.)
+        const uint32_t dma_lds = raw_lds + (uint32_t)w * 256u;
+        int raw_step = 2 * 1024;   // +2 KiB, -2 KiB, ...: the raw slots 0, 1 <-> 2, 3 (scalar)
+        auto tile_fixed = [&](auto jc, auto copier) {
+            constexpr int J = decltype(jc)::value;
+            __builtin_amdgcn_sched_barrier(0);   // (a tile's instructions stay inside the tile, as the back edge of the rolled loop keeps them)
+            if constexpr (decltype(copier)::value) {
+                // raw tile it + J + PD; the instruction's immediate offset J KiB applies to the source AND to the LDS destination, hence M0 =
+                // the tile's slot minus J KiB (scalar arithmetic; xp_voff is the lane's offset of raw tile it + PD)
+                const uint32_t m0 = dma_lds + (uint32_t)((it + J + PD + NR - 1) & (NR - 1)) * 1024u - (uint32_t)J * 1024u;
+                __builtin_amdgcn_global_load_lds((const void *)(rbase + xp_voff), (__attribute__((address_space(3))) void *)(uintptr_t)m0, 4, J * 1024, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            u32x4 r[KS];
+            uint32_t x;
+            asm volatile(
+                "ds_read_b32 %4, %6 offset:%7\n\tds_read_b128 %0, %5 offset:%8\n\tds_read_b128 %1, %5 offset:%8+1024\n\t"
+                "ds_read_b128 %2, %5 offset:%8+2048\n\tds_read_b128 %3, %5 offset:%8+3072"
+                : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(x)
+                : "v"(xp_frag), "v"(xp_raw), "i"(J * 1024), "i"((J & 1) * (KS * 1024))
+                : "memory");
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x));
+            const u32x2 o = expand_pair(x);
+            asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(xp_plane), "v"(o), "i"(((J + 1) & 1) * (KS * 1024)) : "memory");
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r[0]));
+            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
+            asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
+            tile_math(r, cinit);
+        };
+        // one copy of the loop per role: the first KS waves copy, the others only consume -- no test of the role inside the loop
+        auto run_pairs = [&](auto copier) {
+            while (it + 3 < nfull) {
+                tile_fixed(std::integral_constant<int, 0>{}, copier);
+                tile_fixed(std::integral_constant<int, 1>{}, copier);
+                if constexpr (decltype(copier)::value) xp_voff += 2 * 1024, xp_it0 += 2;
+                xp_raw += (uint32_t)raw_step;
+                raw_step = -raw_step;
+                it += 2;
+            }
+        };
+        if (w < KS) run_pairs(std::true_type{});
+        else run_pairs(std::false_type{});
+        if (raw_step < 0) xp_raw -= 2 * 1024;   // (back to raw slot 0 for the rolled tail)
+    }
+    for (; it < nfull; ++it) {
         rotate_prio();
         arrive(it);
-        if (stamps && l == 0 && it < 48) stamps[(size_t)n_items * NW * 4 + ((size_t)item * NW + w) * 48 + it] = __builtin_amdgcn_s_memtime();
+        if constexpr (!XP || ST)   // (the per-tile clock trace of hamming_stamps = 1; the in-kernel expansion has an instance of its own for it)
+            if (stamps && l == 0 && it < 48) stamps[(size_t)n_items * NW * 4 + ((size_t)item * NW + w) * 48 + it] = __builtin_amdgcn_s_memtime();
         tile_body(it, cinit);
+    }
+    // XP: what follows the tile loop forms the lane and thread indices anew (lane count below this lane, wave number from its scalar register):
+    // the loop does not use them any more, and kept alive across it for the ragged tile and the epilogue they would be spills
+    int l_end = l, h_end = h;
+    unsigned tid_end = threadIdx.x;
+    if constexpr (XP) {
+        l_end = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        h_end = l_end >> 5;
+        tid_end = (unsigned)(w * 64 + l_end);
     }
     if (ragged) {
         arrive(nfull);
         const int tile_row0 = row0 + nfull * 32;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int lr = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            const int lr = (reg & 3) + 8 * (reg >> 2) + 4 * h_end;
             cinit[reg] = (tile_row0 + lr < nt) ? -(float)lr * kEps : -INFINITY;
         }
         tile_body(nfull, cinit);
@@ -639,7 +728,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
 
     // (the epilogue's addresses are formed from copies of the lane and tile indices the compiler cannot see through: formed in the prologue
     // they would have to live -- as spills: 128 registers are all in use -- across the main loop)
-    int le = l, qt0e = qt0;
+    int le = l_end, qt0e = qt0;
     asm volatile("" : "+v"(le), "+s"(qt0e));
     const int he = le >> 5;
     const float frame = (float)(32 * (ntiles - 1));
@@ -713,7 +802,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         __shared__ int s_last;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (threadIdx.x == 0) {
+        if (tid_end == 0) {
             const int old = __hip_atomic_fetch_add(&fuse.tickets[(size_t)b * qblocks + qb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s_last = old == nsplit - 1;
             if (s_last) __hip_atomic_store(&fuse.tickets[(size_t)b * qblocks + qb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -724,7 +813,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
             const int q_first = qb * NW * QT * 32;
 #pragma unroll 1
             for (int rr = 0; rr * (64 * NW) < NW * QT * 32; ++rr) {  // (QT = 1: the first half of the threads)
-                const int ql = rr * (64 * NW) + (int)threadIdx.x;
+                const int ql = rr * (64 * NW) + (int)tid_end;
                 const int q = ql < NW * QT * 32 ? q_first + ql : nq;
                 unsigned long long b0 = ~0ull, b1 = ~0ull;
                 auto upd = [&](unsigned long long g) {
@@ -757,12 +846,12 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
                     }
                 }
                 const int c = __popcll(__ballot(pass));
-                const int q_wave = q_first + rr * (64 * NW) + (int)(threadIdx.x & ~63u);   // first query of this wave's 64
-                if (fuse.group_counts && le == 0 && q_wave < nq && rr * (64 * NW) + (int)(threadIdx.x & ~63u) < NW * QT * 32) fuse.group_counts[(size_t)b * ((nq + 63) >> 6) + (q_wave >> 6)] = c;
+                const int q_wave = q_first + rr * (64 * NW) + (int)(tid_end & ~63u);   // first query of this wave's 64
+                if (fuse.group_counts && le == 0 && q_wave < nq && rr * (64 * NW) + (int)(tid_end & ~63u) < NW * QT * 32) fuse.group_counts[(size_t)b * ((nq + 63) >> 6) + (q_wave >> 6)] = c;
             }
         }
     }
-    if (stamps && l == 0) {
+    if (stamps && l_end == 0) {
         unsigned long long *o = stamps + ((size_t)item * NW + w) * 4;
         o[0] = __builtin_amdgcn_s_memtime() - st_c;
         o[1] = __builtin_amdgcn_s_memrealtime() - st_r;
@@ -770,7 +859,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         o[2] = (unsigned long long)ntiles * QT | ((unsigned long long)(hw & 0xFFFFFu) << 32) | ((unsigned long long)(xcc & 15u) << 56);
         o[3] = st_r;
     }
-    if (fuse.clk && item == 0 && threadIdx.x == 0) {
+    if (fuse.clk && item == 0 && tid_end == 0) {
         fuse.clk[0] = __builtin_amdgcn_s_memtime() - st_c;
         fuse.clk[1] = __builtin_amdgcn_s_memrealtime() - st_r;
         fuse.clk[2] = st_r;
@@ -1231,7 +1320,10 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 0>), grid, dim3(256), 0, s, qw, q_batch_words, (const void *)tf,  \
                                t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
     } while (0)
-        if (inkernel)
+        if (inkernel && stamps)   // (hamming_stamps = 1: the rolled loop with the per-tile clock trace)
+            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 2, true, true>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tw, t_batch_words, nq, nt,
+                               rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
+        else if (inkernel)
             hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 2, true>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tw, t_batch_words, nq, nt,
                                rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
         else if (nwv == 16)

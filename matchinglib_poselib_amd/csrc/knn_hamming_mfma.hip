@@ -36,6 +36,8 @@ namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr float kEps = 1.0f / 16384.0f;  // 2^-14: row weight in the accumulator
 // Rows of one split.  A candidate's value is I - (row - frame) * 2^-14 with I = nbits - 2 d an integer of magnitude <= 512 and the frame the
@@ -77,6 +79,13 @@ __device__ __forceinline__ uint32_t expand_byte01(uint32_t x) {
     t = (t | (t << 6)) & 0x03030303u;
     t = (t | (t << 3)) & 0x11111111u;
     return t << 1;
+}
+// one 32-bit word -> the 16 bytes of its fragment (byte j of the word -> dword j), in either encoding
+__device__ __forceinline__ u32x4 expand_word(uint32_t v) {
+    return u32x4{expand_byte(v & 255u), expand_byte((v >> 8) & 255u), expand_byte((v >> 16) & 255u), expand_byte(v >> 24)};
+}
+__device__ __forceinline__ u32x4 expand_word01(uint32_t v) {
+    return u32x4{expand_byte01(v & 255u), expand_byte01((v >> 8) & 255u), expand_byte01((v >> 16) & 255u), expand_byte01(v >> 24)};
 }
 
 // The BIT-PLANE rule of the in-kernel expansion (option hamming_expand_inkernel): every output dword of a 16-byte fragment is one plane of ONE
@@ -146,12 +155,8 @@ __global__ __launch_bounds__(256) void hamming_expand_kernel(ExpandArgs qa, Expa
     uint4 *out = A.dst + ((size_t)b * A.tiles + tile) * KS * 64 + l;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 o = {expand_byte(v[s] & 255u), expand_byte((v[s] >> 8) & 255u), expand_byte((v[s] >> 16) & 255u),
-                   expand_byte(v[s] >> 24)};
-        if (train01)  // (only ever set for the train operand of the static LDS-ring kernel, which expands its queries itself)
-            o = u32x4{expand_byte01(v[s] & 255u), expand_byte01((v[s] >> 8) & 255u), expand_byte01((v[s] >> 16) & 255u),
-                      expand_byte01(v[s] >> 24)};
+        u32x4 o = expand_word(v[s]);
+        if (train01) o = expand_word01(v[s]);  // (only ever set for the train operand of the static LDS-ring kernel, which expands its queries itself)
         __builtin_nontemporal_store(o, reinterpret_cast<u32x4 *>(out + s * 64));
     }
 }
@@ -167,9 +172,8 @@ __global__ __launch_bounds__(256) void hamming_expand_fine_kernel(ExpandArgs A, 
     const int row = tile * 32 + (l & 31);
     const int w = (l >> 5) * KS + st;
     const uint32_t v = row < A.n ? A.src[(size_t)b * A.src_batch_words + (size_t)row * (2 * KS) + w] : 0u;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 o = {expand_byte(v & 255u), expand_byte((v >> 8) & 255u), expand_byte((v >> 16) & 255u), expand_byte(v >> 24)};
-    if (train01) o = u32x4{expand_byte01(v & 255u), expand_byte01((v >> 8) & 255u), expand_byte01((v >> 16) & 255u), expand_byte01(v >> 24)};
+    u32x4 o = expand_word(v);
+    if (train01) o = expand_word01(v);
     __builtin_nontemporal_store(o, reinterpret_cast<u32x4 *>(A.dst + ((size_t)b * A.tiles + tile) * KS * 64 + st * 64 + l));
 }
 
@@ -191,6 +195,107 @@ __device__ __forceinline__ v16f mfma_fp4(uint4 a, uint4 b, v16f c) {
 #endif
 }
 
+// Running top-2 (m1 >= m2) of a lane over the 16 candidates of one accumulator tile.  Four candidates per step, 5 VALU ops: with
+// T = {m1, a, b} the second largest of T + {m2} is max(med3(T), m2) because m2 <= m1; two such pairs share one max3 for m2 (values are
+// distinct, or -inf).
+__device__ __forceinline__ void top2_update4(float &m1, float &m2, float a0, float a1, float a2, float a3) {
+    const float s0 = __builtin_amdgcn_fmed3f(m1, a0, a1);
+    const float t0 = __builtin_fmaxf(__builtin_fmaxf(m1, a0), a1);
+    const float s1 = __builtin_amdgcn_fmed3f(t0, a2, a3);
+    m1 = __builtin_fmaxf(__builtin_fmaxf(t0, a2), a3);
+    m2 = __builtin_fmaxf(__builtin_fmaxf(m2, s0), s1);
+}
+
+// the train tile's row that accumulator register `reg` holds in a lane of half h
+__device__ __forceinline__ int acc_local_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+// C of the first MFMA of every tile: minus the local row of accumulator register `reg` in this lane, times eps
+__device__ __forceinline__ v16f row_weights(int h) {
+    v16f c;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) c[reg] = -(float)acc_local_row(reg, h) * kEps;
+    return c;
+}
+// the same for a ragged tile whose first row is `tile_row0`: rows >= nt start at -inf and stay there
+__device__ __forceinline__ v16f row_weights_ragged(int h, int tile_row0, int nt) {
+    v16f c;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int lr = acc_local_row(reg, h);
+        c[reg] = (tile_row0 + lr < nt) ? -(float)lr * kEps : -INFINITY;
+    }
+    return c;
+}
+
+// Epilogue of every kernel: a lane's running pair -> two packed (dist << dshift | local row) keys (decode_key; -inf = no candidate takes
+// the key 0xFFFFFFFF at the call site), then the top-2 of the four keys of the two lane halves (top2_across_halves).
+// How the integer part ip of a value becomes a distance:
+struct DistRule {
+    int nbits;    // +-1 train operand: d = (nbits - ip) >> 1, nbits = 64 KS
+    int train01;  // != 0: the {0, +1} train operand instead, d = qpop - ip with qpop = pop(query)
+    int qpop;
+    __device__ __forceinline__ int operator()(int ip) const { return train01 ? qpop - ip : (nbits - ip) >> 1; }
+};
+// A value is v = ip + (frame - local_row) * eps with `frame` the first row, relative to the split, of the last tile folded; the fraction
+// lies inside (-1/2, 1/2), so rint() recovers ip.
+__device__ __forceinline__ uint32_t decode_key(float v, float frame, int dshift, DistRule dist) {
+    const float ip = rintf(v);
+    const int d = dist((int)ip);
+    const int lrow = (int)(frame - (v - ip) * 16384.0f);
+    return ((uint32_t)d << dshift) | (uint32_t)lrow;
+}
+// the two lane halves hold disjoint rows of the same query: top-2 of the four keys, in both halves
+__device__ __forceinline__ uint2 top2_across_halves(const uint32_t (&k)[2]) {
+    const uint32_t o0 = __shfl_xor(k[0], 32), o1 = __shfl_xor(k[1], 32);
+    uint32_t k0 = k[0], k1 = k[1];
+    k1 = umed3(k0, k1, o0);
+    k0 = min(k0, o0);
+    k1 = umed3(k0, k1, o1);
+    k0 = min(k0, o1);
+    return make_uint2(k0, k1);
+}
+
+// XCD-aware work assignment.  Workgroups go round-robin to the 8 XCDs (each with its own L2), so workgroup L runs on XCD L % 8.  The
+// work items are ordered (batch item, split, query group or block) and XCD x takes the x-th contiguous eighth of that order: with 8
+// image pairs per launch every XCD streams ONE pair's train fragments (1 MiB at C2) through its L2 instead of all eight; with one pair
+// an XCD sees an eighth of the train splits.  Returns the workgroup's place in that order (the grid is padded to a multiple of 8).
+__device__ __forceinline__ int xcd_block_item() {
+    const int per_xcd = (int)(gridDim.x >> 3);
+    return (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+}
+
+// Diagnostics only ("hamming_stamps" option): shader-clock and 100 MHz real-time deltas per wave.
+__device__ __forceinline__ void clock_start(bool on, unsigned long long &st_c, unsigned long long &st_r) {
+    if (on) {
+        st_c = __builtin_amdgcn_s_memtime();
+        st_r = __builtin_amdgcn_s_memrealtime();
+    }
+}
+// the wave's record: {cycles, ticks, tiles * qt units | hardware ids, start tick}
+__device__ __forceinline__ void clock_stamp(unsigned long long *o, unsigned long long st_c, unsigned long long st_r, int tiles, int qt) {
+    o[0] = __builtin_amdgcn_s_memtime() - st_c;
+    o[1] = __builtin_amdgcn_s_memrealtime() - st_r;
+    // HW_REG_HW_ID (4): wave/simd/cu/sh/se ids; HW_REG_XCC_ID (20): the XCD
+    const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
+    o[2] = (unsigned long long)tiles * qt | ((unsigned long long)(hw & 0xFFFFFu) << 32) | ((unsigned long long)(xcc & 15u) << 56);
+    o[3] = st_r;
+}
+
+// One 4 KiB tile of an LDS ring (four K-steps, 1 KiB apart) into registers; `addr` = the lane's LDS byte address of K-step 0.
+// The tile is read back with hand-written ds_read_b128: for a compiler-visible LDS load the waitcnt pass would first drain EVERY
+// outstanding LDS-DMA (vmcnt(0): it cannot know that the copies in flight target other ring slots), which serialises the prefetch.
+// The reads return in order, so K-step s is complete once at most 3 - s of them are outstanding.
+__device__ __forceinline__ void ring_read_tile(u32x4 (&r)[4], uint32_t addr) {
+    asm volatile(
+        "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
+        : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
+        : "v"(addr)
+        : "memory");
+    asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[0]));
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[1]));
+    asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[2]));
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[3]));
+}
+
 // KS K-steps of 64 bits, QT query tiles (32 queries each) per wave.  A wave's work item is (batch item, train split, query
 // group of QT tiles); the 4 waves of a workgroup are independent (no LDS, no barriers) and take consecutive items, i.e.
 // neighbouring query groups of the same train split, so they stream the same train fragments through the CU's L1.
@@ -201,17 +306,11 @@ __global__ __launch_bounds__(256, (KS >= 8 ? 2 : 3)) void knn_hamming_mfma_kerne
     unsigned long long *__restrict__ stamps) {
     const int l = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
-    // diagnostics only (stamps != nullptr, "hamming_stamps" option): shader-clock and 100 MHz real-time deltas per wave
     unsigned long long st_c = 0, st_r = 0;
-    if (stamps) {
-        st_c = __builtin_amdgcn_s_memtime();
-        st_r = __builtin_amdgcn_s_memrealtime();
-    }
-    // XCD-aware work assignment.  Workgroups go round-robin to the 8 XCDs (each with its own L2), so workgroup L runs on
-    // XCD L % 8.  The work items are ordered (batch item, split, query group) and XCD x takes the x-th contiguous eighth of
-    // that order: with 8 image pairs per launch every XCD streams ONE pair's train fragments (1 MiB at C2) through its L2
-    // instead of all eight; with one pair an XCD sees an eighth of the train splits.
-    const int per_xcd = (int)(gridDim.x >> 3);  // the grid is padded to a multiple of 8
+    clock_start(stamps != nullptr, st_c, st_r);
+    // xcd_block_item() at wave granularity: item = (batch item, train split, query group).  Spelt out: through the helper the <2, 4> instance
+    // comes out with a differently associated address shift (same work, another instruction stream).
+    const int per_xcd = (int)(gridDim.x >> 3);
     const int item = ((int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3)) * 4 + w;
     if (item >= n_items) return;  // wave-uniform; the kernel has no barriers
     const int qg = item % qgroups;
@@ -227,11 +326,8 @@ __global__ __launch_bounds__(256, (KS >= 8 ? 2 : 3)) void knn_hamming_mfma_kerne
 #pragma unroll
         for (int s = 0; s < KS; ++s) bq[t][s] = qf[(size_t)(t * KS + s) * 64];
 
-    // C of the first MFMA of every tile: minus the local row of accumulator register `reg` in this lane, times eps
     const int h = l >> 5;
-    v16f cinit;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) cinit[reg] = -(float)((reg & 3) + 8 * (reg >> 2) + 4 * h) * kEps;
+    const v16f cinit = row_weights(h);
 
     const int row0 = split * rows_per_split;
     const int row1 = min(nt, row0 + rows_per_split);
@@ -258,16 +354,8 @@ __global__ __launch_bounds__(256, (KS >= 8 ? 2 : 3)) void knn_hamming_mfma_kerne
             // re-base the running pair to this tile's row origin (exact; -inf stays -inf)
             m1[t] += 32.0f * kEps;
             m2[t] += 32.0f * kEps;
-            // four candidates per step, 5 VALU ops: with T = {m1, a, b} the second largest of T + {m2} is max(med3(T), m2)
-            // because m2 <= m1; two such pairs share one max3 for m2 (values are distinct, or -inf)
 #pragma unroll
-            for (int reg = 0; reg < 16; reg += 4) {
-                const float s0 = __builtin_amdgcn_fmed3f(m1[t], acc[reg], acc[reg + 1]);
-                const float t0 = __builtin_fmaxf(__builtin_fmaxf(m1[t], acc[reg]), acc[reg + 1]);
-                const float s1 = __builtin_amdgcn_fmed3f(t0, acc[reg + 2], acc[reg + 3]);
-                m1[t] = __builtin_fmaxf(__builtin_fmaxf(t0, acc[reg + 2]), acc[reg + 3]);
-                m2[t] = __builtin_fmaxf(__builtin_fmaxf(m2[t], s0), s1);
-            }
+            for (int reg = 0; reg < 16; reg += 4) top2_update4(m1[t], m2[t], acc[reg], acc[reg + 1], acc[reg + 2], acc[reg + 3]);
         }
     };
 
@@ -292,14 +380,7 @@ __global__ __launch_bounds__(256, (KS >= 8 ? 2 : 3)) void knn_hamming_mfma_kerne
         for (int s = 0; s < KS; ++s) fa[s] = fb[s];
     }
     if (ragged) {
-        const int tile_row0 = row0 + nfull * 32;
-        v16f cl;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int lr = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            cl[reg] = (tile_row0 + lr < nt) ? -(float)lr * kEps : -INFINITY;
-        }
-        tile_body(fa, cl);
+        tile_body(fa, row_weights_ragged(h, row0 + nfull * 32, nt));
     }
 
     // decode (frame = last tile): v = (64 KS - 2 d) + (32 (ntiles - 1) - local_row) * eps
@@ -309,35 +390,13 @@ __global__ __launch_bounds__(256, (KS >= 8 ? 2 : 3)) void knn_hamming_mfma_kerne
         uint32_t k[2];
         const float mm[2] = {m1[t], m2[t]};
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (mm[j] == -INFINITY) {
-                k[j] = 0xFFFFFFFFu;
-            } else {
-                const float ip = rintf(mm[j]);
-                const int d = (64 * KS - (int)ip) >> 1;
-                const int lrow = (int)(frame - (mm[j] - ip) * 16384.0f);
-                k[j] = ((uint32_t)d << dshift) | (uint32_t)lrow;
-            }
-        }
-        // the two lane halves hold disjoint rows of the same query: top-2 of the four keys
-        const uint32_t o0 = __shfl_xor(k[0], 32), o1 = __shfl_xor(k[1], 32);
-        uint32_t k0 = k[0], k1 = k[1];
-        k1 = umed3(k0, k1, o0);
-        k0 = min(k0, o0);
-        k1 = umed3(k0, k1, o1);
-        k0 = min(k0, o1);
+        for (int j = 0; j < 2; ++j)  // (-inf: no candidate)
+            k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key(mm[j], frame, dshift, DistRule{64 * KS, 0, 0});
+        const uint2 kk = top2_across_halves(k);
         const int q = (qt0 + t) * 32 + (l & 31);
-        if (h == 0 && q < nq) part[((size_t)b * nsplit + split) * nq + q] = make_uint2(k0, k1);
+        if (h == 0 && q < nq) part[((size_t)b * nsplit + split) * nq + q] = kk;
     }
-    if (stamps && l == 0) {
-        unsigned long long *o = stamps + (size_t)item * 4;
-        o[0] = __builtin_amdgcn_s_memtime() - st_c;
-        o[1] = __builtin_amdgcn_s_memrealtime() - st_r;
-        // HW_REG_HW_ID (4): wave/simd/cu/sh/se ids; HW_REG_XCC_ID (20): the XCD
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
-        o[2] = (unsigned long long)ntiles * QT | ((unsigned long long)(hw & 0xFFFFFu) << 32) | ((unsigned long long)(xcc & 15u) << 56);
-        o[3] = st_r;
-    }
+    if (stamps && l == 0) clock_stamp(stamps + (size_t)item * 4, st_c, st_r, ntiles, QT);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -415,13 +474,8 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     const int l = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     unsigned long long st_c = 0, st_r = 0;
-    if (stamps || fuse.clk) {
-        st_c = __builtin_amdgcn_s_memtime();
-        st_r = __builtin_amdgcn_s_memrealtime();
-    }
-    // XCD-aware, as above, at workgroup granularity: item = (batch item, train split, block of 4 query groups)
-    const int per_xcd = (int)(gridDim.x >> 3);
-    const int item = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    clock_start(stamps || fuse.clk, st_c, st_r);
+    const int item = xcd_block_item();  // (workgroup granularity: item = (batch item, train split, block of NW query groups))
     if (item >= n_items) return;  // workgroup-uniform: no wave of this workgroup reaches a barrier
     const int qb = item % qblocks;
     const int split = (item / qblocks) % nsplit;
@@ -430,9 +484,10 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     const int h = l >> 5;
 
     uint4 bq[QT][KS];   // the wave's query fragments (filled below, behind the first tile copies)
+    // (row_weights(h) spelt out: through the helper the scalar prologue of twelve of the fourteen instances comes out in another order)
     v16f cinit;
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) cinit[reg] = -(float)((reg & 3) + 8 * (reg >> 2) + 4 * h) * kEps;
+    for (int reg = 0; reg < 16; ++reg) cinit[reg] = -(float)acc_local_row(reg, h) * kEps;
 
     // split geometry: equal splits, or the age-aware table of the launcher (tiles [tab[s], tab[s + 1]) per image pair)
     int row0 = split * rows_per_split;
@@ -470,12 +525,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
                                              (__attribute__((address_space(3))) void *)&ring[t_rel & (NB - 1)][w * 64], 16, 0, 0);
         }
     };
-    // The tile is read back with hand-written ds_read_b128: for a compiler-visible LDS load the waitcnt pass would first drain EVERY
-    // outstanding LDS-DMA (vmcnt(0): it cannot know that the copies in flight target other ring slots), which serialises the prefetch.
-    // The reads return in order, so K-step s is complete once at most 3 - s of them are outstanding.
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0] + (uint32_t)l * 16u;
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     const uint32_t raw_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&raw_ring[0];
     const uint32_t frag_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0];
     // XP: where this lane reads its raw word of tile `t_rel` and where it writes the two planes it forms (see the protocol above)
@@ -518,11 +568,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
                     const float g = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(acc[reg], acc[reg + 1]), acc[reg + 2]), acc[reg + 3]);
                     if (__builtin_amdgcn_ballot_w64(g > m2[t]) == 0) continue;
                 }
-                const float s0 = __builtin_amdgcn_fmed3f(m1[t], acc[reg], acc[reg + 1]);
-                const float t0 = __builtin_fmaxf(__builtin_fmaxf(m1[t], acc[reg]), acc[reg + 1]);
-                const float s1 = __builtin_amdgcn_fmed3f(t0, acc[reg + 2], acc[reg + 3]);
-                m1[t] = __builtin_fmaxf(__builtin_fmaxf(t0, acc[reg + 2]), acc[reg + 3]);
-                m2[t] = __builtin_fmaxf(__builtin_fmaxf(m2[t], s0), s1);
+                top2_update4(m1[t], m2[t], acc[reg], acc[reg + 1], acc[reg + 2], acc[reg + 3]);
             }
         }
     };
@@ -547,15 +593,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
             asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
             asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
         } else {
-        asm volatile(
-            "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
-            : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-            : "v"(addr)
-            : "memory");
-        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[0]));
-        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[1]));
-        asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[2]));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[3]));
+            ring_read_tile(r, addr);
         }
         tile_math(r, c0);
     };
@@ -579,9 +617,10 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         for (int s = 0; s < KS; ++s)
             if constexpr (XP)   // (the rule of the train operand)
                 bq[t][s] = make_uint4(expand_plane(vs[s], 0), expand_plane(vs[s], 2), expand_plane(vs[s], 1), expand_plane(vs[s], 3));
-            else
-                bq[t][s] = make_uint4(expand_byte(vs[s] & 255u), expand_byte((vs[s] >> 8) & 255u), expand_byte((vs[s] >> 16) & 255u),
-                                      expand_byte(vs[s] >> 24));
+            else {
+                const u32x4 o = expand_word(vs[s]);
+                bq[t][s] = make_uint4(o.x, o.y, o.z, o.w);
+            }
     }
     if constexpr (XP) {
         // tile 0: the query loads' wait has covered the first copies (see above); one barrier makes the four quarters visible, then every
@@ -717,12 +756,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     }
     if (ragged) {
         arrive(nfull);
-        const int tile_row0 = row0 + nfull * 32;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int lr = (reg & 3) + 8 * (reg >> 2) + 4 * h_end;
-            cinit[reg] = (tile_row0 + lr < nt) ? -(float)lr * kEps : -INFINITY;
-        }
+        cinit = row_weights_ragged(h_end, row0 + nfull * 32, nt);
         tile_body(nfull, cinit);
     }
 
@@ -748,22 +782,10 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         uint32_t k[2];
         const float mm[2] = {m1[t], m2[t]};
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (mm[j] == -INFINITY) {
-                k[j] = 0xFFFFFFFFu;
-            } else {
-                const float ip = rintf(mm[j]);
-                const int d = fuse.train01 ? qpop - (int)ip : (64 * KS - (int)ip) >> 1;
-                const int lrow = (int)(frame - (mm[j] - ip) * 16384.0f);
-                k[j] = ((uint32_t)d << dshift) | (uint32_t)lrow;
-            }
-        }
-        const uint32_t o0 = __shfl_xor(k[0], 32), o1 = __shfl_xor(k[1], 32);
-        uint32_t k0 = k[0], k1 = k[1];
-        k1 = umed3(k0, k1, o0);
-        k0 = min(k0, o0);
-        k1 = umed3(k0, k1, o1);
-        k0 = min(k0, o1);
+        for (int j = 0; j < 2; ++j)  // (-inf: no candidate)
+            k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key(mm[j], frame, dshift, DistRule{64 * KS, fuse.train01, qpop});
+        const uint2 kk = top2_across_halves(k);
+        const uint32_t k0 = kk.x, k1 = kk.y;
         const int q = (qt0e + t) * 32 + (le & 31);
         if (fuse.idx && nsplit == 1) {  // the final top-2 of the query: outputs straight from the registers
             const uint32_t lmask = (1u << dshift) - 1u;
@@ -851,14 +873,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
             }
         }
     }
-    if (stamps && l_end == 0) {
-        unsigned long long *o = stamps + ((size_t)item * NW + w) * 4;
-        o[0] = __builtin_amdgcn_s_memtime() - st_c;
-        o[1] = __builtin_amdgcn_s_memrealtime() - st_r;
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
-        o[2] = (unsigned long long)ntiles * QT | ((unsigned long long)(hw & 0xFFFFFu) << 32) | ((unsigned long long)(xcc & 15u) << 56);
-        o[3] = st_r;
-    }
+    if (stamps && l_end == 0) clock_stamp(stamps + ((size_t)item * NW + w) * 4, st_c, st_r, ntiles, QT);
     if (fuse.clk && item == 0 && tid_end == 0) {
         fuse.clk[0] = __builtin_amdgcn_s_memtime() - st_c;
         fuse.clk[1] = __builtin_amdgcn_s_memrealtime() - st_r;
@@ -891,12 +906,8 @@ __global__ __launch_bounds__(256, 4) void knn_hamming_mfma_dyn_kernel(
     const int l = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     unsigned long long st_c = 0, st_r = 0;
-    if (stamps) {
-        st_c = __builtin_amdgcn_s_memtime();
-        st_r = __builtin_amdgcn_s_memrealtime();
-    }
-    const int per_xcd = (int)(gridDim.x >> 3);
-    const int item = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    clock_start(stamps != nullptr, st_c, st_r);
+    const int item = xcd_block_item();
     if (item >= n_items) return;  // workgroup-uniform
     const int slots = nspan * nmem;
     const int qb = item % qblocks;
@@ -917,9 +928,7 @@ __global__ __launch_bounds__(256, 4) void knn_hamming_mfma_dyn_kernel(
         for (int s = 0; s < KS; ++s) bq[t][s] = qf[(size_t)(t * KS + s) * 64];
 
     const int h = l >> 5;
-    v16f cinit;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) cinit[reg] = -(float)((reg & 3) + 8 * (reg >> 2) + 4 * h) * kEps;
+    const v16f cinit = row_weights(h);
 
     const int total_tiles = nt >> 5;  // FULL tiles only: the < 32 rows behind them are folded in by the merge kernel
     const int span_tile0 = span * span_tiles;
@@ -936,20 +945,11 @@ __global__ __launch_bounds__(256, 4) void knn_hamming_mfma_dyn_kernel(
         __builtin_amdgcn_global_load_lds((const void *)(reinterpret_cast<const char *>(tbase + (size_t)tile * KS * 64) + l16),
                                          (__attribute__((address_space(3))) void *)&ring[slot][w * 64], 16, 0, 0);
     };
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t ring_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0];
     auto tile_body = [&](int slot, float rebase) {
         u32x4 r[KS];
         const uint32_t addr = l16 + (ring_base + (uint32_t)slot * (KS * 1024u));
-        asm volatile(
-            "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
-            : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-            : "v"(addr)
-            : "memory");
-        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[0]));
-        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[1]));
-        asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[2]));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[3]));
+        ring_read_tile(r, addr);
         uint4 a[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) a[s] = make_uint4(r[s].x, r[s].y, r[s].z, r[s].w);
@@ -961,13 +961,7 @@ __global__ __launch_bounds__(256, 4) void knn_hamming_mfma_dyn_kernel(
             m1[t] += rebase;  // to this tile's row origin (exact; -inf stays -inf)
             m2[t] += rebase;
 #pragma unroll
-            for (int reg = 0; reg < 16; reg += 4) {
-                const float s0 = __builtin_amdgcn_fmed3f(m1[t], acc[reg], acc[reg + 1]);
-                const float t0 = __builtin_fmaxf(__builtin_fmaxf(m1[t], acc[reg]), acc[reg + 1]);
-                const float s1 = __builtin_amdgcn_fmed3f(t0, acc[reg + 2], acc[reg + 3]);
-                m1[t] = __builtin_fmaxf(__builtin_fmaxf(t0, acc[reg + 2]), acc[reg + 3]);
-                m2[t] = __builtin_fmaxf(__builtin_fmaxf(m2[t], s0), s1);
-            }
+            for (int reg = 0; reg < 16; reg += 4) top2_update4(m1[t], m2[t], acc[reg], acc[reg + 1], acc[reg + 2], acc[reg + 3]);
             // one accumulator tile alive at a time: without this tie the scheduler interleaves the next unit's MFMA chain on a second
             // accumulator (which buys nothing: MFMA and VALU do not overlap on a SIMD) and pays for it by spilling query fragments.
             // (An empty volatile asm that "rewrites" this unit's result and the next unit's first operand orders the two.)
@@ -1038,16 +1032,9 @@ __global__ __launch_bounds__(256, 4) void knn_hamming_mfma_dyn_kernel(
         uint32_t k[2];
         const float mm[2] = {m1[t], m2[t]};
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (mm[j] == -INFINITY) {
-                k[j] = 0xFFFFFFFFu;
-            } else {
-                const float ip = rintf(mm[j]);
-                const int d = (64 * KS - (int)ip) >> 1;
-                const int lrow = (int)(frame - (mm[j] - ip) * 16384.0f);
-                k[j] = ((uint32_t)d << dshift) | (uint32_t)lrow;
-            }
-        }
+        for (int j = 0; j < 2; ++j)  // (-inf: no candidate)
+            k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key(mm[j], frame, dshift, DistRule{64 * KS, 0, 0});
+        // (top2_across_halves(k) spelt out: through the helper two scalar copies of the tile loop change places in all three instances)
         const uint32_t o0 = __shfl_xor(k[0], 32), o1 = __shfl_xor(k[1], 32);
         uint32_t k0 = k[0], k1 = k[1];
         k1 = umed3(k0, k1, o0);
@@ -1057,33 +1044,83 @@ __global__ __launch_bounds__(256, 4) void knn_hamming_mfma_dyn_kernel(
         const int q = (qt0 + t) * 32 + (l & 31);
         if (h == 0 && q < nq) part[((size_t)b * slots + slot_id) * nq + q] = make_uint2(k0, k1);
     }
-    if (stamps && l == 0) {
-        unsigned long long *o = stamps + ((size_t)item * 4 + w) * 4;
-        o[0] = __builtin_amdgcn_s_memtime() - st_c;
-        o[1] = __builtin_amdgcn_s_memrealtime() - st_r;
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
-        o[2] = 1ull | ((unsigned long long)(hw & 0xFFFFFu) << 32) | ((unsigned long long)(xcc & 15u) << 56);
-        o[3] = st_r;
+    if (stamps && l == 0) clock_stamp(stamps + ((size_t)item * 4 + w) * 4, st_c, st_r, 1, 1);
+}
+
+template <int N> using int_c = std::integral_constant<int, N>;
+
+// f(int_c<KS>) for the instantiated K-step count: ks = 1, 2, 4, else 8
+template <class F>
+void dispatch_ks(int ks, F &&f) {
+    switch (ks) {
+        case 1: f(int_c<1>{}); break;
+        case 2: f(int_c<2>{}); break;
+        case 4: f(int_c<4>{}); break;
+        default: f(int_c<8>{}); break;
     }
 }
 
-template <int KS>
-void launch_mfma(int qt, dim3 grid, hipStream_t s, const uint4 *qf, size_t qb, const uint4 *tf, size_t tb, int nq, int nt, int rps,
-                 int nsplit, int dshift, int qgroups, int n_items, uint2 *part, unsigned long long *stamps) {
-#define MLPL_MFMA_LAUNCH(QT_)                                                                                                    \
-    hipLaunchKernelGGL((knn_hamming_mfma_kernel<KS, QT_>), grid, dim3(256), 0, s, qf, qb, tf, tb, nq, nt, rps, nsplit, dshift, qgroups, \
-                       n_items, part, stamps)
-    if constexpr (KS <= 4) {
-        if (qt == 4) {
-            MLPL_MFMA_LAUNCH(4);
-            return;
-        }
+// what every instance of the static LDS-ring kernel is launched with (its arguments, in order, behind the grid and the stream)
+struct RingLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const uint32_t *qw;
+    size_t q_batch_words;
+    const void *tsrc;  // train fragments, or the raw train rows for the in-kernel expansion
+    size_t t_batch;
+    int nq, nt, rps, nsplit, dshift, qblocks, n_items;
+    uint2 *part;
+    unsigned long long *stamps;
+    const int32_t *split_tab;
+    HammingFuse fuse;
+};
+template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false, bool ST = false>
+void launch_ring(const RingLaunch &a) {
+    hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT, PRIO, NW, PD, XP, ST>), a.grid, dim3(64 * NW), 0, a.s, a.qw, a.q_batch_words, a.tsrc,
+                       a.t_batch, a.nq, a.nt, a.rps, a.nsplit, a.dshift, a.qblocks, a.n_items, a.part, a.stamps, a.split_tab, a.fuse);
+}
+
+// Age-aware split sizes (static LDS-ring kernel).  With exactly R = 4 workgroups per CU the dispatcher deals workgroups breadth
+// first, so workgroup L is the (L / num_cus)-th oldest wave set on its CU, and the SIMD arbitrates oldest-first: measured per-tile
+// costs with all four ranks active are 1700 / 2100 / 3200 / 5300 cycles (tools/hamming_trace.py), i.e. equal splits finish at
+// 62k / 75k / 90k / 105k cycles and the CU runs the second half of the launch under-occupied.  Splits sized by the ranks' rates
+// (weights 1/cost) let the four finish together.  Correctness never depends on this: the table only moves split boundaries, and
+// it is used only when every query block of a (pair, split) has the same rank.
+// For a grid of `grid_x` workgroups over `items` = batch * nsplit * qblocks work items: tab = [batch][nsplit + 1] first tiles of the
+// splits (tiles [tab[s], tab[s + 1]) per image pair), or false = not applicable (mixed ranks, or a split above max_rps rows).
+bool age_aware_split_table(unsigned grid_x, long long items, int num_cus, int qblocks, int nsplit, int batch, int t_tiles, int max_rps,
+                           std::vector<int32_t> &tab) {
+    const int per_xcd = (int)(grid_x >> 3);
+    tab.assign((size_t)batch * (nsplit + 1), -1);  // first the rank of every (pair, split), then in place its first tile
+    for (long long bid = 0; bid < items; ++bid) {  // one workgroup per item; the grid's padding behind them has no work
+        const long long item = (bid & 7) * per_xcd + (bid >> 3);
+        if (item >= items) continue;
+        const int sp = (int)((item / qblocks) % nsplit), bb = (int)(item / ((long long)qblocks * nsplit));
+        const int r = (int)(bid / num_cus);
+        int32_t &slot = tab[(size_t)bb * (nsplit + 1) + sp];
+        if (slot < 0) slot = r;
+        else if (slot != r) return false;
     }
-    if (qt >= 2)
-        MLPL_MFMA_LAUNCH(2);
-    else
-        MLPL_MFMA_LAUNCH(1);
-#undef MLPL_MFMA_LAUNCH
+    static const double kRate[4] = {1.0 / 1700, 1.0 / 2100, 1.0 / 3200, 1.0 / 5300};
+    for (int bb = 0; bb < batch; ++bb) {
+        int32_t *h = tab.data() + (size_t)bb * (nsplit + 1);
+        double wsum = 0;
+        for (int sp = 0; sp < nsplit; ++sp) wsum += kRate[h[sp]];
+        int acc_tiles = 0;
+        double acc_w = 0;
+        for (int sp = 0; sp < nsplit; ++sp) {
+            acc_w += kRate[h[sp]];
+            h[sp] = acc_tiles;
+            int upto = (int)std::llround(t_tiles * acc_w / wsum);
+            upto = std::max(upto, acc_tiles + 1);                        // at least one tile per split
+            upto = std::min(upto, t_tiles - (nsplit - 1 - sp));          // and one left for every later split
+            upto = std::min(upto, acc_tiles + max_rps / 32);          // exact re-basing bound
+            acc_tiles = upto;
+        }
+        h[nsplit] = t_tiles;
+        if (t_tiles - h[nsplit - 1] > max_rps / 32) return false;
+    }
+    return true;
 }
 
 }  // namespace
@@ -1111,7 +1148,7 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     const int qgroups = (nqt + qt - 1) / qt;  // wave-level work: one group of qt query tiles against one train split
     const bool lds_ring = ks == 4 && ctx->opt_hamming_mfma_lds != 0;  // workgroup-level work: NW query groups share the train tiles
     const bool dyn = lds_ring && ctx->opt_hamming_mfma_lds == 2 && nt >= 32;  // ... and the train splits are drawn dynamically
-    // waves per workgroup of the static ring kernel (option hamming_mfma_waves: 0 = automatic, 4, 8): eight when every wave carries four query
+    // waves per workgroup of the static ring kernel (option hamming_mfma_waves: 0 = automatic, 4, 8, 16): eight when every wave carries four query
     // tiles (the throughput shape) -- a tile fetched and a barrier passed once per eight waves' units
     const int nwv = (lds_ring && !dyn && qt == 4 && ctx->opt_hamming_mfma_waves != 4) ? (ctx->opt_hamming_mfma_waves == 16 ? 16 : 8) : 4;
     const int qblocks = (qgroups + nwv - 1) / nwv;
@@ -1192,74 +1229,32 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
         // nothing to expand here: the ring kernel reads the raw train rows
     } else if (expand_fine) {
         hipLaunchKernelGGL(hamming_expand_fine_kernel, dim3((unsigned)t_tiles, batch), dim3(256), 0, s, ta, train01);
-    } else
-    switch (ks) {
-        case 1: hipLaunchKernelGGL(hamming_expand_kernel<1>, egrid, dim3(256), 0, s, qa, ta, nw, counters, counters_per_batch, train01); break;
-        case 2: hipLaunchKernelGGL(hamming_expand_kernel<2>, egrid, dim3(256), 0, s, qa, ta, nw, counters, counters_per_batch, train01); break;
-        case 4: hipLaunchKernelGGL(hamming_expand_kernel<4>, egrid, dim3(256), 0, s, qa, ta, nw, counters, counters_per_batch, train01); break;
-        default: hipLaunchKernelGGL(hamming_expand_kernel<8>, egrid, dim3(256), 0, s, qa, ta, nw, counters, counters_per_batch, train01); break;
+    } else {
+        dispatch_ks(ks, [&](auto KS) {
+            hipLaunchKernelGGL(hamming_expand_kernel<decltype(KS)::value>, egrid, dim3(256), 0, s, qa, ta, nw, counters, counters_per_batch, train01);
+        });
     }
     // 1-D grid, remapped in the kernel (XCD-aware); padded so that every XCD gets the same number of workgroups
     const long long blocks = lds_ring ? items : (items + 3) / 4;
     dim3 grid((unsigned)((blocks + 7) / 8 * 8));
-    // Age-aware split sizes (static LDS-ring kernel).  With exactly R = 4 workgroups per CU the dispatcher deals workgroups breadth
-    // first, so workgroup L is the (L / num_cus)-th oldest wave set on its CU, and the SIMD arbitrates oldest-first: measured per-tile
-    // costs with all four ranks active are 1700 / 2100 / 3200 / 5300 cycles (tools/hamming_trace.py), i.e. equal splits finish at
-    // 62k / 75k / 90k / 105k cycles and the CU runs the second half of the launch under-occupied.  Splits sized by the ranks' rates
-    // (weights 1/cost) let the four finish together.  Correctness never depends on this: the table only moves split boundaries, and
-    // it is used only when every query block of a (pair, split) has the same rank.
+    // age-aware split sizes: the table is rebuilt and uploaded only when the shape changes
     const int32_t *split_tab = nullptr;
+    std::vector<int32_t> tab;
     if (lds_ring && !dyn && nwv == 4 && ctx->opt_hamming_mfma_weighted && blocks == 4LL * ctx->num_cus && nsplit >= 4 && nsplit <= 256 &&
-        batch * (nsplit + 1) <= 4096) {
-        const int per_xcd = (int)(grid.x >> 3);
-        std::vector<int> rank((size_t)batch * nsplit, -1);
-        bool ok = true;
-        for (long long bid = 0; bid < blocks && ok; ++bid) {
-            const long long item = (bid & 7) * per_xcd + (bid >> 3);
-            if (item >= items) continue;
-            const int sp = (int)((item / qblocks) % nsplit), bb = (int)(item / ((long long)qblocks * nsplit));
-            const int r = (int)(bid / ctx->num_cus);
-            int &slot = rank[(size_t)bb * nsplit + sp];
-            if (slot < 0) slot = r;
-            else if (slot != r) ok = false;
+        batch * (nsplit + 1) <= 4096 && age_aware_split_table(grid.x, items, ctx->num_cus, qblocks, nsplit, batch, t_tiles, max_rps, tab)) {
+        const long long key = ((long long)nt << 32) ^ ((long long)nsplit << 20) ^ ((long long)batch << 8) ^ qblocks;
+        void *tabp = nullptr;
+        if ((rc = ws_get(ctx, WS_SPLIT_TAB, 4096 * sizeof(int32_t), &tabp))) return rc;
+        if (ctx->split_tab_key != key || ctx->split_tab_ptr != tabp) {
+            // staging in pageable memory of this call (`tab`): the context's pinned block belongs to the entry point that called us (the pair
+            // batch entries keep pointers into it across the matching call, and pinned_get frees the block when it grows)
+            MLPL_HIP_TRY(hipStreamSynchronize(s));  // the previous table may still be read by kernels in flight
+            MLPL_HIP_TRY(hipMemcpyAsync(tabp, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            MLPL_HIP_TRY(hipStreamSynchronize(s));  // the staging vector dies with this call
+            ctx->split_tab_key = key;
+            ctx->split_tab_ptr = tabp;
         }
-        if (ok) {
-            static const double kRate[4] = {1.0 / 1700, 1.0 / 2100, 1.0 / 3200, 1.0 / 5300};
-            const long long key = ((long long)nt << 32) ^ ((long long)nsplit << 20) ^ ((long long)batch << 8) ^ qblocks;
-            void *tabp = nullptr;
-            if ((rc = ws_get(ctx, WS_SPLIT_TAB, 4096 * sizeof(int32_t), &tabp))) return rc;
-            if (ctx->split_tab_key != key || ctx->split_tab_ptr != tabp) {
-                // staging in pageable memory of this call: the context's pinned block belongs to the entry point that called us (the pair
-                // batch entries keep pointers into it across the matching call, and pinned_get frees the block when it grows)
-                std::vector<int32_t> hv((size_t)batch * (nsplit + 1));
-                int32_t *h = hv.data();
-                for (int bb = 0; bb < batch; ++bb) {
-                    double wsum = 0;
-                    for (int sp = 0; sp < nsplit; ++sp) wsum += kRate[rank[(size_t)bb * nsplit + sp]];
-                    int acc_tiles = 0;
-                    double acc_w = 0;
-                    for (int sp = 0; sp < nsplit; ++sp) {
-                        h[bb * (nsplit + 1) + sp] = acc_tiles;
-                        acc_w += kRate[rank[(size_t)bb * nsplit + sp]];
-                        int upto = (int)std::llround(t_tiles * acc_w / wsum);
-                        upto = std::max(upto, acc_tiles + 1);                        // at least one tile per split
-                        upto = std::min(upto, t_tiles - (nsplit - 1 - sp));          // and one left for every later split
-                        upto = std::min(upto, acc_tiles + max_rps / 32);          // exact re-basing bound
-                        acc_tiles = upto;
-                    }
-                    h[bb * (nsplit + 1) + nsplit] = t_tiles;
-                    if (t_tiles - h[bb * (nsplit + 1) + nsplit - 1] > max_rps / 32) ok = false;
-                }
-                if (ok) {
-                    MLPL_HIP_TRY(hipStreamSynchronize(s));  // the previous table may still be read by kernels in flight
-                    MLPL_HIP_TRY(hipMemcpyAsync(tabp, h, (size_t)batch * (nsplit + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                    MLPL_HIP_TRY(hipStreamSynchronize(s));  // the staging vector dies with this scope
-                    ctx->split_tab_key = key;
-                    ctx->split_tab_ptr = tabp;
-                }
-            }
-            if (ok) split_tab = (const int32_t *)tabp;
-        }
+        split_tab = (const int32_t *)tabp;
     }
     unsigned long long *stamps = nullptr;
     ctx->dbg_stamp_items = 0;
@@ -1303,57 +1298,39 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     }
     prof_mark(ctx, MLPL_PROF_KNN_HAMMING, 0, s);
     if (dyn) {
-#define MLPL_DYN_LAUNCH(QT_)                                                                                                          \
-    hipLaunchKernelGGL((knn_hamming_mfma_dyn_kernel<QT_>), grid, dim3(256), 0, s, (const uint4 *)qf, q_u4, (const uint4 *)tf, t_u4, nq, nt, \
-                       span_tiles, nspan, nmem, chunk_tiles, dshift, qblocks, (int)items, (uint2 *)part, counters, stamps)
-        if (qt == 4) MLPL_DYN_LAUNCH(4);
-        else if (qt == 2) MLPL_DYN_LAUNCH(2);
-        else MLPL_DYN_LAUNCH(1);
-#undef MLPL_DYN_LAUNCH
+        auto launch_dyn = [&](auto QT) {
+            hipLaunchKernelGGL((knn_hamming_mfma_dyn_kernel<decltype(QT)::value>), grid, dim3(256), 0, s, (const uint4 *)qf, q_u4, (const uint4 *)tf, t_u4, nq,
+                               nt, span_tiles, nspan, nmem, chunk_tiles, dshift, qblocks, (int)items, (uint2 *)part, counters, stamps);
+        };
+        if (qt == 4) launch_dyn(int_c<4>{});
+        else if (qt == 2) launch_dyn(int_c<2>{});
+        else launch_dyn(int_c<1>{});
     } else if (lds_ring) {
-#define MLPL_RING_LAUNCH(QT_)                                                                                                          \
-    do {                                                                                                                               \
-        if (prio == 1)                                                                                                                 \
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 1>), grid, dim3(256), 0, s, qw, q_batch_words, (const void *)tf,  \
-                               t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT_, 0>), grid, dim3(256), 0, s, qw, q_batch_words, (const void *)tf,  \
-                               t_u4, nq, nt, rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);         \
-    } while (0)
-        if (inkernel && stamps)   // (hamming_stamps = 1: the rolled loop with the per-tile clock trace)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 2, true, true>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tw, t_batch_words, nq, nt,
-                               rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (inkernel)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 2, true>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tw, t_batch_words, nq, nt,
-                               rps, nsplit, dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (nwv == 16)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 16>), grid, dim3(1024), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
-                               dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (nwv == 8 && pd == 4)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 4>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
-                               dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (nwv == 8 && pd == 6)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8, 6>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
-                               dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (nwv == 8 && prio == 3)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 3, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
-                               dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (nwv == 8 && prio == 1)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 1, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
-                               dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (nwv == 8)
-            hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<4, 0, 8>), grid, dim3(512), 0, s, qw, q_batch_words, (const void *)tf, t_u4, nq, nt, rps, nsplit,
-                               dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse);
-        else if (qt == 4) MLPL_RING_LAUNCH(4);
-        else if (qt == 2) MLPL_RING_LAUNCH(2);
-        else MLPL_RING_LAUNCH(1);
-#undef MLPL_RING_LAUNCH
-    } else
-    switch (ks) {
-        case 1: launch_mfma<1>(qt, grid, s, (const uint4 *)qf, q_u4, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit, dshift, qgroups, (int)items, (uint2 *)part, stamps); break;
-        case 2: launch_mfma<2>(qt, grid, s, (const uint4 *)qf, q_u4, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit, dshift, qgroups, (int)items, (uint2 *)part, stamps); break;
-        case 4: launch_mfma<4>(qt, grid, s, (const uint4 *)qf, q_u4, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit, dshift, qgroups, (int)items, (uint2 *)part, stamps); break;
-        default: launch_mfma<8>(qt, grid, s, (const uint4 *)qf, q_u4, (const uint4 *)tf, t_u4, nq, nt, rps, nsplit, dshift, qgroups, (int)items, (uint2 *)part, stamps); break;
+        const RingLaunch ra{grid, s, qw, q_batch_words, inkernel ? (const void *)tw : (const void *)tf, inkernel ? t_batch_words : t_u4, nq, nt, rps, nsplit,
+                            dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse};
+        if (inkernel && stamps) launch_ring<4, 0, 8, 2, true, true>(ra);   // (hamming_stamps = 1: the rolled loop with the per-tile clock trace)
+        else if (inkernel) launch_ring<4, 0, 8, 2, true>(ra);
+        else if (nwv == 16) launch_ring<4, 0, 16>(ra);
+        else if (nwv == 8 && pd == 4) launch_ring<4, 0, 8, 4>(ra);
+        else if (nwv == 8 && pd == 6) launch_ring<4, 0, 8, 6>(ra);
+        else if (nwv == 8 && prio == 3) launch_ring<4, 3, 8>(ra);
+        else if (nwv == 8 && prio == 1) launch_ring<4, 1, 8>(ra);
+        else if (nwv == 8) launch_ring<4, 0, 8>(ra);
+        else if (qt == 4) prio == 1 ? launch_ring<4, 1>(ra) : launch_ring<4, 0>(ra);
+        else if (qt == 2) prio == 1 ? launch_ring<2, 1>(ra) : launch_ring<2, 0>(ra);
+        else prio == 1 ? launch_ring<1, 1>(ra) : launch_ring<1, 0>(ra);
+    } else {
+        dispatch_ks(ks, [&](auto KS) {
+            auto launch_mfma = [&](auto QT) {
+                hipLaunchKernelGGL((knn_hamming_mfma_kernel<decltype(KS)::value, decltype(QT)::value>), grid, dim3(256), 0, s, (const uint4 *)qf, q_u4,
+                                   (const uint4 *)tf, t_u4, nq, nt, rps, nsplit, dshift, qgroups, (int)items, (uint2 *)part, stamps);
+            };
+            if constexpr (decltype(KS)::value <= 4) {
+                if (qt == 4) return launch_mfma(int_c<4>{});
+            }
+            if (qt >= 2) launch_mfma(int_c<2>{});
+            else launch_mfma(int_c<1>{});
+        });
     }
     prof_mark(ctx, MLPL_PROF_KNN_HAMMING, 1, s);
     *rps_out = rps;

@@ -3,7 +3,7 @@ mlpl_debug_last_kernels (a silent fallback to another instance would make a case
 
 Record fields (include/mlpl_debug.h): [2] kernel (0-2 VALU, 3 register-prefetch MFMA, 4 static LDS ring, 5 dynamic ring), [3] query tiles
 per wave / queries per lane, [4] PRIO, [5] waves per workgroup, [6] prefetch distance, [7] fused merge, [8] split table, [9] fine expand,
-[10] train splits, [11] K-steps."""
+[10] train splits, [11] K-steps, [12] in-kernel train expansion."""
 import numpy as np
 import pytest
 
@@ -14,7 +14,7 @@ from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
-KIND, QT, PRIO, NWV, PD, FUSED, TAB, FINE, NSPLIT, KS = range(2, 12)
+KIND, QT, PRIO, NWV, PD, FUSED, TAB, FINE, NSPLIT, KS, INKERNEL = range(2, 13)
 
 # name -> (options, {record field: value} on the 32-byte-descriptor calls with >= 32 train rows)
 # Precedence of the static ring kernel's options (knn_hamming_mfma.hip): waves 16 beats prefetch 4 / 6, which beats prio; prefetch and
@@ -49,6 +49,10 @@ OPTION_SETS = {
     "stamps1": (dict(hamming_stamps=1), {KIND: 4}),
     "stamps2": (dict(hamming_stamps=2), {KIND: 4}),
     "variant1_qpl2": (dict(hamming_variant=1, hamming_qpl=2), {KIND: 1}),
+    # paths of the shared key decode that no row above pins: the pop(query) - ip rule of the {0, +1} train operand (never expanded in the
+    # kernel) and, under hamming_split_rows, the decode's frame with several splits (asserted below)
+    "train01": (dict(hamming_train01=1), {KIND: 4, INKERNEL: 0}),
+    "split_rows4096": (dict(hamming_split_rows=4096), {KIND: 4}),
 }
 
 
@@ -62,6 +66,8 @@ def test_hamming_instance_bit_exact(ctx, oracle, name):
         if nbytes == 32 and nt >= 32:
             got = {f: rec[f] for f in expect}
             assert got == expect, (name, nq, nt, rec)
+            if name == "split_rows4096" and nt == 4097:   # several splits (the launcher cuts this shape far below the cap anyway)
+                assert rec[NSPLIT] >= 2, rec
             seen.append(rec)
 
     with options(ctx, **opts):

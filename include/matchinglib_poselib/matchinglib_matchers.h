@@ -3,6 +3,7 @@
 // libmlpl_hip.so (include/mlpl_c.h).  Every other matcher name returns -2 ("Matcher not supported"): those matchers are
 // outside the hot path this library accelerates.
 #pragma once
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -18,5 +19,15 @@ int getMatches(const std::vector<cv::KeyPoint> &keypoints1, const std::vector<cv
                std::vector<cv::DMatch> &finalMatches, std::string const &matcher_name = "GMBSOF", bool VFCrefine = false,
                bool ratioTest = true, std::string const &descriptor_name = "", std::string idxPars_NMSLIB = "",
                std::string queryPars_NMSLIB = "", const size_t nr_threads = 0);
+
+// Sub-pixel refinement of matched keypoints by template matching (reference matchinglib_matchers.h:86, matchers.cpp:1085-1297), through
+// mlpl_subpix_matches (include/mlpl_c.h states what is computed and the declared deviations: an exact-integer difference table, and matches
+// the reference would assert on are dropped).  keypoints1[i] matches keypoints2[i]; the refined positions are written to keypoints2, the
+// inlier mask to *inliers when given.  Return value: 0 ok, -1 refinement failed for too many keypoints (fewer than a third, or fewer than 2,
+// were refined; keypoints2 and *inliers are written all the same), -2 the keypoint sets differ in size.  Throws cv::Exception for images
+// that are not 8-bit single channel (the reference's matchTemplate accepts float images too) and for more than 65535 keypoints.
+// getSubPixMatches_seperate_Imgs (subPixRefine == 2) is cv::cornerSubPix twice and is not provided.
+int getSubPixMatches(cv::Mat &img1, cv::Mat &img2, std::vector<cv::KeyPoint> *keypoints1, std::vector<cv::KeyPoint> *keypoints2,
+                     std::vector<bool> *inliers = NULL);
 
 }  // namespace matchinglib

@@ -280,6 +280,55 @@ int mlpl_gms_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_m
                                 int use_scale, int use_rotation, int min_final_rule, mlpl_dmatch *d_out, int32_t *d_n_out,
                                 int32_t *d_n_inliers, void *stream);
 
+/* ---- sub-pixel refinement: matchinglib::getSubPixMatches ------------------------------------------------------
+ * Template matching around matched keypoints (M/source/matchers.cpp:1085-1297), the step getCorrespondences runs with subPixRefine == 1
+ * behind getMatches and the filters (M/source/correspondences.cpp:444-494).  Keypoint lists 1 and 2 are matched index by index.  Match i:
+ *  1. side fs = (int)(size1 > size2 ? size1 : size2) + 6, at least 18 (a NaN or negative size ends here), minus 1 when even; d1 = (fs - 1) / 2.
+ *  2. template: fs x fs pixels of image 1 at (cvRound(x1) - d1, cvRound(y1) - d1); window: (fs + 10)^2 pixels of image 2 at
+ *     (cvRound(x2) - d1 - 5, cvRound(y2) - d1 - 5); cvRound rounds half to even; pixels outside an image read as 0.
+ *  3. R[v][u], u, v in 0..10 = sum over the template of (window[v + r][u + c] - template[r][c])^2 as an EXACT integer, then rounded to float32.
+ *  4. (mx, my) = the first minimum of the float32 table in row-major order.
+ *  5. inlier iff (mx - 5)^2 + (my - 5)^2 <= 16.
+ *  6. an inlier's parabola fit in float32, every operation rounded on its own: nx = 2 (2 c - xn - xp), ny likewise; if both are non-zero,
+ *     keypoint 2 = ((float)(window x + mx + d1) + (xp - xn) / nx, (float)(window y + my + d1) + (yp - yn) / ny) and the match counts as refined.
+ *     Keypoint 1 and an outlier's keypoint 2 never change.
+ *  7. *status = -1 if refined < n / 3 or refined < 2 (MIN_FINAL_MATCHES), else 0; mask and keypoints are written in both cases.
+ * Deviations:
+ *  - The reference's table comes from cv::matchTemplate, which forms the cross term in float32 (OpenCV is not in this tree; its exact
+ *    arithmetic is not reproduced).  The table here is the exact integer, bit for bit the restatement tests/subpix_oracle.py.  Against the
+ *    reference a near-tie may pick a neighbouring placement and offsets may differ by about 1e-3 px; the difference is unmeasured.
+ *  - Dropped matches (mask 0, keypoint unchanged, counted in info under the first rule that applies, in this order): a coordinate that is
+ *    not finite or whose rounded value does not fit an int; a side above 255 (it bounds the LDS footprint and keeps the sum in 32 bits);
+ *    a template or window that leaves the 100-pixel border the reference pads the images with (it asserts in cv::Mat::operator() there).
+ *  - Images are 8-bit single channel; anything else is MLPL_E_BAD_INPUT at this level.
+ * img1 / img2: HOST pointers, `step` bytes from row to row (>= width).  kp1 [n][2], kp2 [n][2] (in / out), size1 / size2 [n] or NULL (all 0:
+ * side 17), inlier [n] bytes of 0 / 1.  info (optional) = {dropped by the border rule, by the side rule, by the coordinate rule, largest
+ * side used (0 when every match was dropped)}.  Returns MLPL_OK, MLPL_E_BAD_INPUT (n > 65535, a non-positive size, step < width) or
+ * another MLPL_E_* code; the reference's 0 / -1 goes to *status.  n = 0 returns MLPL_OK with *status = -1. */
+int mlpl_subpix_matches(mlpl_ctx *ctx, const uint8_t *img1, int width1, int height1, size_t step1, const uint8_t *img2, int width2, int height2,
+                        size_t step2, const float *kp1, float *kp2, const float *size1, const float *size2, int n, uint8_t *inlier,
+                        int *n_refined, int *status, int info[4]);
+/* Step 1 on the host: the template side for a pair of keypoint sizes, 17 ... 255, or 0 when the side rule drops the match. */
+int mlpl_subpix_template_side(float size1, float size2);
+/* The same for a batch of match lists, device-resident and non-synchronising (one kernel launch on `stream`, no upload): the layouts of
+ * mlpl_gms_filter_matches_dev -- problem b refines d_matches + b * match_stride (d_n_matches[b] <= match_stride entries) on
+ * d_kp1[b][queryIdx], d_kp2[b][trainIdx] ([batch][nq][2] / [batch][nt][2] floats; indices outside are clamped), sizes d_size1[b][queryIdx],
+ * d_size2[b][trainIdx] (or NULL), images d_img1 + b * batch_stride1 and d_img2 + b * batch_stride2 (bytes; row steps step1 / step2).
+ * max_side: the largest template side LDS is provisioned for, 0 = 255; a match with a larger side is dropped by the side rule (pass the
+ * largest mlpl_subpix_template_side of the data, or 17 with NULL sizes, for more workgroups per compute unit; with 0 every per-match
+ * result is bit-identical to mlpl_subpix_matches on the same data: the same kernel).
+ * d_kp2_out [batch][nt][2] (may be d_kp2) starts as a copy of d_kp2; then, as correspondences.cpp:480-483, every match writes its refined or
+ * unchanged position to its train keypoint, and of several matches with one trainIdx the LAST in list order wins.  d_status[b] = step 7.
+ * correspondences_rule == 0: the inliers are compacted in list order into d_out + b * match_stride (d_out must not be d_matches),
+ * d_n_out[b] their number.  correspondences_rule != 0 applies correspondences.cpp:474-494: on status -1 the list and the keypoints pass
+ * through unchanged; on status 0 the inliers are emitted in REVERSE list order (the reference's loop runs from the end).
+ * d_inlier (optional) [batch][match_stride] bytes: the mask of step 5.  batch, match_stride in [1, 65535]. */
+int mlpl_subpix_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                            const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2,
+                            const uint8_t *d_img1, int width1, int height1, size_t step1, size_t batch_stride1, const uint8_t *d_img2,
+                            int width2, int height2, size_t step2, size_t batch_stride2, int max_side, int correspondences_rule,
+                            mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, float *d_kp2_out, uint8_t *d_inlier, void *stream);
+
 /* ---- correspondence gather (pre-step of the pose path) -------------------------------------------------------
  * Replaces the gather + ImgToCamCoordTrans of StereoRefine::addNewCorrespondences (P/source/stereo_pose_refinement.cpp:
  * 428-455, P/source/pose_helper.cpp:1100-1109): p1[i] = ((double)kp1[m.queryIdx] - c0) / f0 rounded to float and widened

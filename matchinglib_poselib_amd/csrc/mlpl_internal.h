@@ -64,6 +64,7 @@ enum WsSlot {
     WS_TICKETS,   // ticket counters of the fused Hamming epilogue (zero between launches; knn_hamming_mfma.hip)
     WS_VFC,       // VFC match filter (vfc.hip): per-point state, per-problem results, the raw rand() values of the control-point draws
     WS_GMS,       // GMS match filter (gms.hip): per-match cell codes, buckets and flags, per-problem results
+    WS_SUBPIX,    // sub-pixel refinement (subpix.hip): per-match records and positions, per-keypoint winners, per-list results and tickets
     WS_NUM_SLOTS
 };
 
@@ -319,6 +320,20 @@ struct GmsWork {
 int launch_gms(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches, int n_direct,
                const float *d_kp1, int nq, const float *d_kp2, int nt, int width1, int height1, int width2, int height2, int use_scale,
                int use_rotation, int rule, mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_n_inliers, GmsWork *work, hipStream_t s);
+
+// Sub-pixel refinement (subpix.hip) of match lists (d_matches [batch][match_stride], nullptr = match i joins keypoint i of both lists;
+// d_n_matches [batch] or nullptr = n_direct for every list; d_kp1 [batch][nq][2], d_kp2 [batch][nt][2]; d_size1 / d_size2 [batch][nq] /
+// [batch][nt] or nullptr; 8-bit images as [batch] planes with a row step and a batch stride in bytes).  max_side: the largest template side
+// LDS is provisioned for (0 = 255).  One kernel launch on s, no upload, no synchronisation.  *work (optional) receives the workspace view
+// res [batch][8] = {refined, status, dropped by the border / side / coordinate rule, largest side used, n_out, inliers}.
+struct SubpixWork {
+    const int32_t *res;
+};
+int launch_subpix(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches, int n_direct,
+                  const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2, const uint8_t *d_img1,
+                  int width1, int height1, size_t step1, size_t bstride1, const uint8_t *d_img2, int width2, int height2, size_t step2,
+                  size_t bstride2, int max_side, int rule, mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, float *d_kp2_out,
+                  uint8_t *d_inlier, SubpixWork *work, hipStream_t s);
 
 // glibc srand()/rand() (TYPE_3 additive feedback generator: r[k+3] += r[k] over a ring of 31 words, output r >> 1, the first 310
 // outputs discarded), produced 31 values at a time: one unrolled pass over the ring has no index wrap-around and three independent

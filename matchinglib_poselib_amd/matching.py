@@ -359,3 +359,92 @@ def gms_filter_matches_device(matches, count, kp1, kp2, size1, size2, use_scale:
         torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
     check(rc, "mlpl_gms_filter_matches_dev")
     return out
+
+
+# ---- sub-pixel refinement -----------------------------------------------------------------------------------------
+
+def _image_u8(img) -> np.ndarray:
+    """an 8-bit single-channel image with contiguous pixels inside each row (the row step may exceed the width)"""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise MlplError(-1, "subpix_matches", "images are 8-bit, single channel and not empty")
+    if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img)
+    return img
+
+
+def subpix_matches(img1, img2, kp1, kp2, size1=None, size2=None, ctx: Optional[Context] = None) -> dict:
+    """mlpl_subpix_matches (matchinglib::getSubPixMatches) -> dict(status, kp2 float32 [n, 2], inlier bool [n], n_refined, dropped_border,
+    dropped_side, dropped_coord, max_side).  img1 / img2: uint8 [height, width] arrays (rows may be strided views); kp1 / kp2: matched
+    keypoint coordinates, index by index ([n, 2] arrays, (x, y) pairs or objects with .pt); size1 / size2: the keypoints' sizes [n] or None
+    (all 0: a 17 x 17 template).  status: 0, or -1 when fewer than n / 3 or fewer than 2 matches were refined (kp2 and inlier are filled in
+    either way).  The declared deviations from the reference: include/mlpl_c.h."""
+    ctx = ctx or default_context()
+    i1, i2 = _image_u8(img1), _image_u8(img2)
+    a = _keypoint_xy(kp1)
+    b = np.array(_keypoint_xy(kp2), np.float32, copy=True)
+    n = a.shape[0]
+    if b.shape[0] != n:
+        raise MlplError(-1, "subpix_matches", "the keypoint lists must have the same length")
+    s1 = None if size1 is None else np.ascontiguousarray(size1, np.float32).reshape(-1)
+    s2 = None if size2 is None else np.ascontiguousarray(size2, np.float32).reshape(-1)
+    if (s1 is not None and len(s1) != n) or (s2 is not None and len(s2) != n):
+        raise MlplError(-1, "subpix_matches", "one size per keypoint")
+    inl, info, nr, st = np.zeros(max(n, 1), np.uint8), np.zeros(4, np.int32), C.c_int(0), C.c_int(0)
+    rc = ctx.lib.mlpl_subpix_matches(ctx.handle, i1.ctypes.data, i1.shape[1], i1.shape[0], i1.strides[0], i2.ctypes.data, i2.shape[1],
+                                     i2.shape[0], i2.strides[0], a.ctypes.data, b.ctypes.data, None if s1 is None else s1.ctypes.data,
+                                     None if s2 is None else s2.ctypes.data, n, inl.ctypes.data, C.byref(nr), C.byref(st), info.ctypes.data)
+    check(rc, "mlpl_subpix_matches")
+    return dict(status=st.value, kp2=b, inlier=inl[:n].astype(bool), n_refined=nr.value, dropped_border=int(info[0]), dropped_side=int(info[1]),
+                dropped_coord=int(info[2]), max_side=int(info[3]))
+
+
+def subpix_template_side(size1: float, size2: float, ctx: Optional[Context] = None) -> int:
+    """mlpl_subpix_template_side: the template side for a pair of keypoint sizes (17 ... 255), 0 when the side rule drops the match"""
+    ctx = ctx or default_context()
+    return int(ctx.lib.mlpl_subpix_template_side(float(size1), float(size2)))
+
+
+def subpix_matches_device(matches, count, kp1, kp2, img1, img2, size1=None, size2=None, max_side: int = 0, correspondences_rule: bool = False,
+                          ctx: Optional[Context] = None, out=None, stream: Optional[int] = None):
+    """Batched sub-pixel refinement on device-resident match lists (mlpl_subpix_matches_dev), the step behind match_hamming_device /
+    match_l2_device and the VFC / GMS filters and in front of the gather.  matches: int32 [B, stride, 4] (DMatch rows), count: int32 [B],
+    kp1: float32 [B, nq, 2], kp2: float32 [B, nt, 2], img1 / img2: uint8 [B, height, width] (the last dimension contiguous; row and batch
+    strides are passed on), size1 / size2: float32 [B, nq] / [B, nt] or None -- CUDA/HIP tensors.  max_side: the largest template side to
+    provision for (0 = 255; 17 is enough without sizes).  Returns dict of torch tensors matches [B, stride, 4] (the inliers, compacted),
+    count [B], status [B], kp2 [B, nt, 2] (every match's refined or unchanged position at its train keypoint, the last match of a keypoint
+    wins), inlier uint8 [B, stride].  correspondences_rule: correspondences.cpp:474-494 -- on status -1 list and keypoints pass through,
+    on status 0 the inliers come in reverse list order.  Enqueues on `stream` (None = torch's current stream) without synchronising."""
+    import torch
+
+    if matches.dim() == 2:
+        matches, count, kp1, kp2, img1, img2 = matches.unsqueeze(0), count.reshape(1), kp1.unsqueeze(0), kp2.unsqueeze(0), img1.unsqueeze(0), img2.unsqueeze(0)
+        size1 = None if size1 is None else size1.unsqueeze(0)
+        size2 = None if size2 is None else size2.unsqueeze(0)
+    assert matches.is_cuda and matches.dtype == torch.int32 and matches.is_contiguous() and matches.shape[2] == 4
+    assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()
+    assert kp1.is_cuda and kp2.is_cuda and kp1.dtype == torch.float32 and kp2.dtype == torch.float32 and kp1.is_contiguous() and kp2.is_contiguous()
+    B, stride = matches.shape[0], matches.shape[1]
+    assert count.shape == (B,) and kp1.shape[0] == B and kp2.shape[0] == B and kp1.shape[2] == 2 and kp2.shape[2] == 2
+    for im in (img1, img2):
+        assert im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[0] == B and im.stride(2) == 1 and im.stride(1) >= im.shape[2]
+    for sz, k in ((size1, kp1), (size2, kp2)):
+        assert sz is None or (sz.is_cuda and sz.dtype == torch.float32 and sz.is_contiguous() and sz.shape == k.shape[:2])
+    ctx = ctx or default_context(matches.device.index or 0)
+    if out is None:
+        out = {
+            "matches": torch.empty_like(matches),
+            "count": torch.empty((B,), dtype=torch.int32, device=matches.device),
+            "status": torch.empty((B,), dtype=torch.int32, device=matches.device),
+            "kp2": torch.empty_like(kp2),
+            "inlier": torch.zeros((B, stride), dtype=torch.uint8, device=matches.device),
+        }
+    rc = ctx.lib.mlpl_subpix_matches_dev(
+        ctx.handle, B, matches.data_ptr(), stride, count.data_ptr(), kp1.data_ptr(), kp1.shape[1], kp2.data_ptr(), kp2.shape[1],
+        None if size1 is None else size1.data_ptr(), None if size2 is None else size2.data_ptr(),
+        img1.data_ptr(), img1.shape[2], img1.shape[1], img1.stride(1), img1.stride(0) if B > 1 else 0,
+        img2.data_ptr(), img2.shape[2], img2.shape[1], img2.stride(1), img2.stride(0) if B > 1 else 0, int(max_side),
+        1 if correspondences_rule else 0, out["matches"].data_ptr(), out["count"].data_ptr(), out["status"].data_ptr(), out["kp2"].data_ptr(),
+        out["inlier"].data_ptr(), torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
+    check(rc, "mlpl_subpix_matches_dev")
+    return out

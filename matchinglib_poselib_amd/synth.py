@@ -205,3 +205,74 @@ def gms_scene(kind: str, n: int, seed: int = 0, width: int = 1280, height: int =
     matches["queryIdx"], matches["trainIdx"] = np.arange(n), perm
     matches["distance"] = rng.integers(0, 64, n).astype(np.float32)
     return dict(kp1=np.ascontiguousarray(x1, np.float32), kp2=kp2, matches=matches, size1=(width, height), size2=(width, height), inlier=~out)
+
+
+def _smooth_texture(rng, terms: int = 24):
+    """a smooth random function of the plane with values in about [0, 255]: a sum of sinusoids of 10 to 48 pixels wavelength"""
+    wl = rng.uniform(10.0, 48.0, terms)
+    ang = rng.uniform(0.0, 2.0 * np.pi, terms)
+    ph = rng.uniform(0.0, 2.0 * np.pi, terms)
+    amp = rng.uniform(0.5, 1.0, terms)
+    kx, ky = 2.0 * np.pi / wl * np.cos(ang), 2.0 * np.pi / wl * np.sin(ang)
+
+    def f(x, y):
+        v = sum(a * np.sin(p + cx * x + cy * y) for a, p, cx, cy in zip(amp, ph, kx, ky))
+        return 127.5 + v * (110.0 / np.sqrt(0.5 * np.sum(amp * amp)) / 3.0)
+
+    return f
+
+
+def subpix_scene(kind: str, n: int, seed: int = 0, width: int = 320, height: int = 240, shift=(3.3, -2.6), noise: float = 0.0,
+                 scramble: float = 0.0, side: float = 0.0):
+    """Images, keypoints and keypoint sizes for the sub-pixel refinement (matchinglib::getSubPixMatches); lists 1 and 2 match index by index.
+    kind "texture":  a smooth texture; image 2 shows it moved by `shift` pixels (sampled from the continuous function, so the shift is exact),
+                     both images with Gaussian noise of `noise` grey levels.  Keypoint 1 is uniform over the image, keypoint 2 = keypoint 1 +
+                     shift + up to 1.5 px of jitter.  A share `scramble` of the keypoints 2 is moved 6 to 8 px further, which puts the true
+                     position outside the search window: outliers.  `truth` = cvRound(keypoint 1) + shift, what the refinement should return.
+    kind "constant": both images hold one grey level and the keypoints stay 24 px from the edges: all 121 sums are 0.
+    kind "rounding": 200 x 200 images.  Image 1 holds a block of 96 x 96 pixels of 255 that every template contains whole, image 2 holds 0
+                     wherever a placement can put that block, so all 121 sums share 96^2 * 255^2 > 2^29, where float32 steps by 64; the other
+                     pixels are grey levels 0 to 3 (image 1: nine in ten of them 0), so the sums differ by the few pixels of image 2's
+                     border that a placement covers: least, and nearly equal, around the centre.  Keypoints within 1.4 px of the centre, size 111.1 (side 117) unless `side`
+                     says otherwise (at least 107).
+    Returns dict(img1, img2: uint8 [height, width], kp1, kp2: float32 [n, 2], size1, size2: float32 [n], truth: float32 [n, 2],
+    scrambled: bool [n])."""
+    if kind not in ("texture", "constant", "rounding"):
+        raise ValueError("kind is 'texture', 'constant' or 'rounding'")
+    rng = np.random.default_rng(20261019 + 15485863 * seed + {"texture": 0, "constant": 1, "rounding": 2}[kind])
+    scr = np.zeros(n, bool)
+    if kind == "rounding":
+        width = height = 200
+        lo, hi = 100 - 48, 100 + 48
+        img1 = (rng.integers(1, 4, (height, width)) * (rng.random((height, width)) < 0.1)).astype(np.uint8)
+        img2 = rng.integers(0, 4, (height, width)).astype(np.uint8)
+        img1[lo:hi, lo:hi] = 255
+        img2[lo - 9:hi + 9, lo - 9:hi + 9] = 0
+        kp1 = 100.0 + rng.integers(-1, 2, (n, 2)) + rng.uniform(-0.4, 0.4, (n, 2))
+        kp2 = 100.0 + rng.integers(-1, 2, (n, 2)) + rng.uniform(-0.4, 0.4, (n, 2))
+        sizes = np.full(n, side if side else 111.1, np.float32)
+        truth = kp2.copy()
+    else:
+        if kind == "constant":
+            img1 = np.full((height, width), 93, np.uint8)
+            img2 = img1.copy()
+        else:
+            f = _smooth_texture(rng)
+            yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+            a, b = f(xx, yy), f(xx - shift[0], yy - shift[1])
+            if noise > 0.0:
+                a, b = a + rng.normal(0.0, noise, a.shape), b + rng.normal(0.0, noise, b.shape)
+            img1, img2 = np.clip(np.rint(a), 0, 255).astype(np.uint8), np.clip(np.rint(b), 0, 255).astype(np.uint8)
+        kp1 = rng.random((n, 2)) * np.array([width - 1.0, height - 1.0])
+        if kind == "constant":
+            kp1 = 24.0 + rng.random((n, 2)) * np.array([width - 49.0, height - 49.0])   # templates and windows whole inside the images
+        truth = np.rint(kp1.astype(np.float32)) + np.array(shift)
+        kp2 = kp1 + np.array(shift) + rng.uniform(-1.5, 1.5, (n, 2))
+        scr[rng.permutation(n)[: int(round(scramble * n))]] = True
+        ang = rng.uniform(0.0, 2.0 * np.pi, n)
+        far = rng.uniform(6.0, 8.0, n)[:, None] * np.stack([np.sign(np.cos(ang)), np.sign(np.sin(ang))], axis=1)
+        kp2[scr] += far[scr]
+        sizes = np.full(n, side, np.float32)
+    return dict(img1=np.ascontiguousarray(img1), img2=np.ascontiguousarray(img2), kp1=np.ascontiguousarray(kp1, np.float32),
+                kp2=np.ascontiguousarray(kp2, np.float32), size1=sizes.copy(), size2=sizes.copy(), truth=np.ascontiguousarray(truth, np.float32),
+                scrambled=scr)

@@ -26,8 +26,16 @@ int getMatches(const std::vector<cv::KeyPoint> &keypoints1, const std::vector<cv
 // inlier mask to *inliers when given.  Return value: 0 ok, -1 refinement failed for too many keypoints (fewer than a third, or fewer than 2,
 // were refined; keypoints2 and *inliers are written all the same), -2 the keypoint sets differ in size.  Throws cv::Exception for images
 // that are not 8-bit single channel (the reference's matchTemplate accepts float images too) and for more than 65535 keypoints.
-// getSubPixMatches_seperate_Imgs (subPixRefine == 2) is cv::cornerSubPix twice and is not provided.
 int getSubPixMatches(cv::Mat &img1, cv::Mat &img2, std::vector<cv::KeyPoint> *keypoints1, std::vector<cv::KeyPoint> *keypoints2,
                      std::vector<bool> *inliers = NULL);
+
+// Sub-pixel refinement of matched keypoints by cv::cornerSubPix on each image on its own (reference matchinglib_matchers.h:90,
+// matchers.cpp:1318-1391; subPixRefine == 2, the variant for large rotations and scale changes), through mlpl_subpix_separate
+// (include/mlpl_c.h restates cv::cornerSubPix and declares the deviations).  keypoints1[i] matches keypoints2[i]; a match whose two points
+// both stay within sqrt(12) px takes its refined positions in BOTH lists and is an inlier.  Return value: 0 ok, -1 fewer than a third, or
+// fewer than 2, of the matches are inliers (keypoints and *inliers are written all the same), -2 the keypoint sets differ in size.  Throws
+// cv::Exception for images that are not 8-bit single channel, for an image smaller than 2 w + 5 pixels and for more than 65535 keypoints.
+int getSubPixMatches_seperate_Imgs(cv::Mat &img1, cv::Mat &img2, std::vector<cv::KeyPoint> *keypoints1, std::vector<cv::KeyPoint> *keypoints2,
+                                   std::vector<bool> *inliers = NULL);
 
 }  // namespace matchinglib

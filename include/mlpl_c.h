@@ -329,6 +329,80 @@ int mlpl_subpix_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_match
                             int width2, int height2, size_t step2, size_t batch_stride2, int max_side, int correspondences_rule,
                             mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, float *d_kp2_out, uint8_t *d_inlier, void *stream);
 
+/* ---- sub-pixel refinement, each image on its own: matchinglib::getSubPixMatches_seperate_Imgs ------------------
+ * cv::cornerSubPix on the matched keypoints of image 1 and of image 2 independently (M/source/matchers.cpp:1318-1391), the step
+ * getCorrespondences runs with subPixRefine == 2 (M/source/correspondences.cpp:444-494): the variant for pairs with large rotation or scale
+ * change, where a template of image 1 is not found in image 2.  OpenCV is not in this tree: the arithmetic of cv::cornerSubPix and
+ * cv::getRectSubPix is RESTATED here from OpenCV 4.2's cornersubpix.cpp / samplers.cpp as remembered, and this text is the definition.  The
+ * device result equals the restatement tests/subpix_separate_oracle.py bit for bit; the distance to a real OpenCV build is unmeasured.
+ * Keypoint lists 1 and 2 are matched index by index.  Per call (one match list):
+ *  1. window half-size per image, w1 and w2: m = the smallest keypoint size of that list that is > 0 (a NaN or non-positive size never
+ *     compares true and is ignored; FLT_MAX when there is none or the size array is NULL), clamped to at most 20, then to at least 6;
+ *     w = (int)ceilf(m / 2.f), so w is 3 ... 10, and every point of that image uses it.
+ *  2. mask: g[i] = (float)exp(-(double)(y * y)) with float y = (float)(i - w) / w, i = 0 ... 2w; mask[i][j] = g[i] * g[j], a float32 product.
+ *     The eight profiles are evaluated on the host in double by libm's exp, rounded to float and uploaded when the context is created.
+ *  3. refinement of one point cT (float32 x, y) in an image of cols x rows: cI = cT, iter = 0, then repeat
+ *     a. sampling: cx = cI.x - (float)(w + 1), ix = floor(cx), a = cx - (float)ix, the same in y for iy and b, all float32; the weights, every
+ *        operation rounded to float32, a11 = (1-a)*(1-b), a12 = a*(1-b), a21 = (1-a)*b, a22 = a*b; for r, c in 0 ... 2w+2
+ *        S[r][c] = ((P(iy+r, ix+c)*a11 + P(iy+r, ix+c+1)*a12) + P(iy+r+1, ix+c)*a21) + P(iy+r+1, ix+c+1)*a22 in float32, each product and
+ *        each sum rounded on its own; P is the 8-bit image with row and column indices clamped to the image (edge replication).
+ *     b. terms: for window element k = i*(2w+1) + j, i, j in 0 ... 2w, all in double: tgx = S[i+1][j+2] - S[i+1][j],
+ *        tgy = S[i+2][j+1] - S[i][j+1], m = mask[i][j], gxx = (tgx*tgx)*m, gxy = (tgx*tgy)*m, gyy = (tgy*tgy)*m, px = j - w, py = i - w;
+ *        the five terms are gxx, gxy, gyy, gxx*px + gxy*py, gxy*px + gyy*py.
+ *     c. summation order (part of the contract: double addition is not associative): lane l = k mod 64 adds its terms in increasing k,
+ *        starting from its first term; a lane without terms holds +0.0; the 64 lane sums are folded by v[l] = v[l] + v[l + s] for
+ *        s = 32, 16, 8, 4, 2, 1 and the result is v[0] -- the halving tree of one wave.  Results: a, b, c, bb1, bb2.
+ *     d. det = a*c - b*b; if fabs(det) <= DBL_EPSILON*DBL_EPSILON the loop ends and cI stays.
+ *     e. scale = 1.0/det; nx = (float)(((double)cI.x + (c*scale)*bb1) - (b*scale)*bb2), ny = (float)(((double)cI.y - (b*scale)*bb1) +
+ *        (a*scale)*bb2); err = (nx-cI.x)*(nx-cI.x) + (ny-cI.y)*(ny-cI.y) in float32, widened to double; cI = (nx, ny).
+ *     f. if cI.x < 0 || cI.x >= cols || cI.y < 0 || cI.y >= rows the loop ends.
+ *     g. the loop continues while ++iter < 40 && err > 1e-6 (TermCriteria(EPS + COUNT, 40, 0.001), squared).
+ *     After the loop: if fabsf(cI.x - cT.x) > w || fabsf(cI.y - cT.y) > w the result is cT ("too far"), else cI.
+ *  4. match i: d1 = the squared float32 distance between the old and the refined point 1 (dx*dx + dy*dy, each operation rounded), d2
+ *     likewise for point 2.  d1 > 12 || d2 > 12: mask 0 and neither keypoint changes.  Otherwise mask 1, both keypoints take their refined
+ *     positions and the match counts as refined.  A point that never moved is an inlier: a constant image refines nothing, every match is
+ *     an inlier and the status is 0 (unlike mlpl_subpix_matches).
+ *  5. *status = -1 if refined < n / 3 or refined < 2 (MIN_FINAL_MATCHES), else 0; mask and keypoints are written in both cases.
+ * Deviations:
+ *  - Sampling: OpenCV's in-image fast path factors the expression of 3a differently; the out-of-image path is the one restated.  Mask:
+ *    OpenCV calls std::exp on a float; the double route rounded to float equals a correctly rounded expf, the reference's libm may not.
+ *    Neither difference is measured.
+ *  - A point with a coordinate that is not finite or does not fit an int is dropped: its match has mask 0, stays unchanged and the point
+ *    is counted in info (the reference's behaviour there is undefined); the other point of the match is still iterated.
+ *  - A non-finite nx or ny ends the loop and the result is cT.
+ *  - Images are 8-bit single channel.  An image with cols < 2w + 5 or rows < 2w + 5 is MLPL_E_BAD_INPUT (OpenCV asserts there).
+ * img1 / img2: HOST pointers, `step` bytes from row to row (>= width).  kp1, kp2 [n][2] (both in / out), size1 / size2 [n] or NULL, inlier [n]
+ * bytes of 0 / 1, iters NULL or [n][2]: the value of step 3's `iter` when the loop of point 1 / point 2 of the match ended (the passes that
+ * reached 3g; 0 for a dropped point) -- the sensitive witness that two implementations walk the same trajectory.  info (optional) = {w1, w2,
+ * points dropped by the coordinate rule, points reset by the "too far" rule}.  Returns MLPL_OK, MLPL_E_BAD_INPUT (n > 65535, a non-positive
+ * size, step < width, an image too small) or another MLPL_E_* code; the reference's 0 / -1 goes to *status.  n = 0 returns MLPL_OK with
+ * *status = -1. */
+int mlpl_subpix_separate(mlpl_ctx *ctx, const uint8_t *img1, int width1, int height1, size_t step1, const uint8_t *img2, int width2, int height2,
+                         size_t step2, float *kp1, float *kp2, const float *size1, const float *size2, int n, uint8_t *inlier, int32_t *iters,
+                         int *n_refined, int *status, int info[4]);
+/* Step 1's clamp and ceil on the host: the window half-size, 3 ... 10, for the smallest positive keypoint size of a list (FLT_MAX or a
+ * NaN: none, 10). */
+int mlpl_subpix_separate_window(float min_size);
+/* The same for a batch of match lists, device-resident and non-synchronising (two kernel launches on `stream`: the windows of every list,
+ * then the refinement; no upload: the mask profiles are in the context): the layouts and the argument order of
+ * mlpl_subpix_matches_dev without max_side and with d_kp1_out.  The windows of list b are step 1 over the sizes of that list's matched
+ * keypoints, d_size1[b][queryIdx] and d_size2[b][trainIdx] (indices outside are clamped); the windows are only known on the device, so
+ * images smaller than 25 x 25 are MLPL_E_BAD_INPUT whatever the sizes.  Every per-match result is bit-identical to mlpl_subpix_separate on
+ * the gathered keypoints (the same kernel).
+ * d_kp2_out [batch][nt][2] (may be d_kp2) starts as a copy of d_kp2; then, as correspondences.cpp:480-483, every match writes its refined or
+ * unchanged position to its train keypoint, and of several matches with one trainIdx the LAST in list order wins.  d_kp1_out (NULL or
+ * [batch][nq][2], may be d_kp1) likewise by queryIdx when correspondences_rule == 0; under the rule it is a plain copy of d_kp1: the
+ * reference's caller discards the refined keypoints 1.  d_status[b] = step 5.
+ * correspondences_rule == 0: the inliers are compacted in list order into d_out + b * match_stride (d_out must not be d_matches),
+ * d_n_out[b] their number.  correspondences_rule != 0 applies correspondences.cpp:474-494: on status -1 the list and the keypoints pass
+ * through unchanged; on status 0 the inliers are emitted in REVERSE list order.  d_inlier (optional) [batch][match_stride] bytes: the mask
+ * of step 4.  batch, match_stride in [1, 65535]. */
+int mlpl_subpix_separate_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                             const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2,
+                             const uint8_t *d_img1, int width1, int height1, size_t step1, size_t batch_stride1, const uint8_t *d_img2,
+                             int width2, int height2, size_t step2, size_t batch_stride2, int correspondences_rule, mlpl_dmatch *d_out,
+                             int32_t *d_n_out, int32_t *d_status, float *d_kp1_out, float *d_kp2_out, uint8_t *d_inlier, void *stream);
+
 /* ---- correspondence gather (pre-step of the pose path) -------------------------------------------------------
  * Replaces the gather + ImgToCamCoordTrans of StereoRefine::addNewCorrespondences (P/source/stereo_pose_refinement.cpp:
  * 428-455, P/source/pose_helper.cpp:1100-1109): p1[i] = ((double)kp1[m.queryIdx] - c0) / f0 rounded to float and widened

@@ -6,7 +6,7 @@ declared in include/mlpl_c.h (libmlpl_hip.so).  This package is the thin host-si
 reference's operator interface; all arithmetic runs in the HIP library and there is no CPU fallback.
 """
 from ._lib import MlplError, Context, load_library, library_path  # noqa: F401
-from .matching import DMATCH_DTYPE, filter_matches_gms, filter_with_vfc, getMatches, gms_filter, gms_filter_matches_device, knn_hamming, knn_l2sq, ratio_compact, subpix_matches, subpix_matches_device  # noqa: F401
+from .matching import DMATCH_DTYPE, filter_matches_gms, filter_with_vfc, getMatches, gms_filter, gms_filter_matches_device, knn_hamming, knn_l2sq, ratio_compact, subpix_matches, subpix_matches_device, subpix_separate, subpix_separate_device, subpix_separate_window, subpix_template_side  # noqa: F401
 
 __all__ = [
     "MlplError",
@@ -21,6 +21,10 @@ __all__ = [
     "gms_filter_matches_device",
     "subpix_matches",
     "subpix_matches_device",
+    "subpix_separate",
+    "subpix_separate_device",
+    "subpix_separate_window",
+    "subpix_template_side",
     "knn_hamming",
     "knn_l2sq",
     "ratio_compact",

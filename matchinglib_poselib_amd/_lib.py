@@ -178,6 +178,12 @@ _SIGNATURES = {
     "mlpl_subpix_matches_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_subpix_separate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_subpix_separate_window": (c_int, [c_float]),
+    "mlpl_subpix_separate_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_int, c_size_t, c_size_t, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mlpl_recover_pose_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
     "mlpl_recover_pose_translation": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,

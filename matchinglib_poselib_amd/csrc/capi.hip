@@ -2,6 +2,7 @@
 // Every compute path here ends in a HIP kernel launch; there is no CPU fallback.
 
 #include <algorithm>
+#include <cfloat>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -174,6 +175,10 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
         set_error("helper stream / events: %s", hipGetErrorString(e));
         mlpl_ctx_destroy(ctx);
         return MLPL_E_HIP;
+    }
+    if (int rc = subpix_separate_init(ctx)) {   // the mask profiles of mlpl_subpix_separate*: 768 bytes, so that no entry uploads
+        mlpl_ctx_destroy(ctx);
+        return rc;
     }
     *out = ctx;
     return MLPL_OK;
@@ -675,6 +680,84 @@ int mlpl_subpix_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_match
     return launch_subpix(ctx, batch, d_matches, match_stride, d_n_matches, 0, d_kp1, nq, d_kp2, nt, d_size1, d_size2, d_img1, width1, height1,
                          step1, batch_stride1, d_img2, width2, height2, step2, batch_stride2, max_side, correspondences_rule, d_out, d_n_out,
                          d_status, d_kp2_out, d_inlier, nullptr, pick_stream(ctx, stream));
+}
+
+int mlpl_subpix_separate(mlpl_ctx *ctx, const uint8_t *img1, int width1, int height1, size_t step1, const uint8_t *img2, int width2, int height2,
+                         size_t step2, float *kp1, float *kp2, const float *size1, const float *size2, int n, uint8_t *inlier, int32_t *iters,
+                         int *n_refined, int *status, int info[4]) {
+    if (!ctx || n < 0 || n > 65535 || !img1 || !img2 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 || step1 < (size_t)width1 ||
+        step2 < (size_t)width2 || (n > 0 && (!kp1 || !kp2 || !inlier))) {
+        set_error("mlpl_subpix_separate: bad arguments (n in [0, 65535], 8-bit images of positive size, row step >= width)");
+        return MLPL_E_BAD_INPUT;
+    }
+    // step 1 on the host as well: the image size rule needs the windows in front of the launch
+    float m1 = FLT_MAX, m2 = FLT_MAX;
+    for (int i = 0; i < n; ++i) {
+        if (size1 && size1[i] > 0.f && size1[i] < m1) m1 = size1[i];
+        if (size2 && size2[i] > 0.f && size2[i] < m2) m2 = size2[i];
+    }
+    const int w1 = mlpl_subpix_separate_window(m1), w2 = mlpl_subpix_separate_window(m2);
+    if (width1 < 2 * w1 + 5 || height1 < 2 * w1 + 5 || width2 < 2 * w2 + 5 || height2 < 2 * w2 + 5) {
+        set_error("mlpl_subpix_separate: an image is smaller than 2 w + 5 pixels (w = %d, %d)", w1, w2);
+        return MLPL_E_BAD_INPUT;
+    }
+    if (n_refined) *n_refined = 0;
+    if (status) *status = -1;
+    if (info) info[0] = w1, info[1] = w2, info[2] = info[3] = 0;
+    if (n == 0) return MLPL_OK;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    void *di1, *di2, *d1, *d2, *dsz, *dinl, *dit;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, (size_t)width1 * height1, &di1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, (size_t)width2 * height2, &di2))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX2, (size_t)n * 8, &d1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX3, (size_t)n * 8, &d2))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX4, (size_t)n * 8, &dsz))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX5, (size_t)n, &dinl))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX6, (size_t)n * 8, &dit))) return rc;
+    float *ds1 = size1 ? (float *)dsz : nullptr, *ds2 = size2 ? (float *)dsz + n : nullptr;
+    MLPL_HIP_TRY(hipMemcpy2DAsync(di1, (size_t)width1, img1, step1, (size_t)width1, (size_t)height1, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpy2DAsync(di2, (size_t)width2, img2, step2, (size_t)width2, (size_t)height2, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(d1, kp1, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(d2, kp2, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    if (ds1) MLPL_HIP_TRY(hipMemcpyAsync(ds1, size1, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (ds2) MLPL_HIP_TRY(hipMemcpyAsync(ds2, size2, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    SubpixWork work{};
+    if ((rc = launch_subpix_separate(ctx, 1, nullptr, n, nullptr, n, (const float *)d1, n, (const float *)d2, n, ds1, ds2, (const uint8_t *)di1,
+                                     width1, height1, (size_t)width1, 0, (const uint8_t *)di2, width2, height2, (size_t)width2, 0, 0, nullptr,
+                                     nullptr, nullptr, (float *)d1, (float *)d2, (uint8_t *)dinl, (int32_t *)dit, &work, s)))
+        return rc;
+    int32_t res[8];
+    MLPL_HIP_TRY(hipMemcpyAsync(res, work.res, sizeof(res), hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(kp1, d1, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(kp2, d2, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipMemcpyAsync(inlier, dinl, (size_t)n, hipMemcpyDeviceToHost, s));
+    if (iters) MLPL_HIP_TRY(hipMemcpyAsync(iters, dit, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipStreamSynchronize(s));
+    if (n_refined) *n_refined = res[0];
+    if (status) *status = res[1];
+    if (info) info[0] = res[2], info[1] = res[3], info[2] = res[4], info[3] = res[5];
+    return MLPL_OK;
+}
+
+int mlpl_subpix_separate_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
+                             const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2,
+                             const uint8_t *d_img1, int width1, int height1, size_t step1, size_t batch_stride1, const uint8_t *d_img2,
+                             int width2, int height2, size_t step2, size_t batch_stride2, int correspondences_rule, mlpl_dmatch *d_out,
+                             int32_t *d_n_out, int32_t *d_status, float *d_kp1_out, float *d_kp2_out, uint8_t *d_inlier, void *stream) {
+    // the windows are taken on the device, so the image size rule is applied for the largest one: 2 * 10 + 5
+    if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
+        nq < 1 || nt < 1 || !d_img1 || !d_img2 || width1 < 25 || height1 < 25 || width2 < 25 || height2 < 25 || step1 < (size_t)width1 ||
+        step2 < (size_t)width2 || !d_out || d_out == d_matches || !d_n_out || !d_status || !d_kp2_out) {
+        set_error("mlpl_subpix_separate_dev: bad arguments (batch, match_stride in [1, 65535]; 8-bit images of at least 25 x 25 pixels, row step "
+                  ">= width; d_out apart from d_matches)");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_subpix_separate(ctx, batch, d_matches, match_stride, d_n_matches, 0, d_kp1, nq, d_kp2, nt, d_size1, d_size2, d_img1, width1,
+                                  height1, step1, batch_stride1, d_img2, width2, height2, step2, batch_stride2, correspondences_rule, d_out,
+                                  d_n_out, d_status, d_kp1_out, d_kp2_out, d_inlier, nullptr, nullptr, pick_stream(ctx, stream));
 }
 
 int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_stride, size_t q_batch_stride,

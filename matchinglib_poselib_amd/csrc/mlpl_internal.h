@@ -65,6 +65,8 @@ enum WsSlot {
     WS_VFC,       // VFC match filter (vfc.hip): per-point state, per-problem results, the raw rand() values of the control-point draws
     WS_GMS,       // GMS match filter (gms.hip): per-match cell codes, buckets and flags, per-problem results
     WS_SUBPIX,    // sub-pixel refinement (subpix.hip): per-match records and positions, per-keypoint winners, per-list results and tickets
+    WS_SUBPIX_SEP,      // cornerSubPix refinement (subpix_separate.hip): per-match records and positions, per-keypoint winners, per-list results and tickets
+    WS_SUBPIX_SEP_MASK, // ... its eight mask profiles (uploaded when the context is created)
     WS_NUM_SLOTS
 };
 
@@ -136,6 +138,7 @@ struct mlpl_ctx {
     int opt_hamming_train01;        // 1 = {0, +1} train fragments in the static LDS-ring kernel (accumulator = pop(query) - distance), 0 = +-1
     int opt_vfc_store_u;            // 1 = the VFC kernel keeps the m x n kernel matrix U in the workspace; 0 (default, unmeasured: DESIGN section 8) = it recomputes U in both passes of an iteration
     int opt_hamming_expand_inkernel;   // 1 = the static LDS-ring kernel's throughput instance expands the raw train tiles itself (no expansion launch, no WS_FRAG_T)
+    void *subpix_sep_mask_ptr;      // the WS_SUBPIX_SEP_MASK block that holds the mask profiles of subpix_separate.hip
     int dbg_stamp_items;
     // diagnostics (mlpl_debug_last_kernels): what the last launches chose -- {count instance code, its point splits} of the last
     // inlier-count pass, and the Hamming instance of the last knn_hamming call (layout: include/mlpl_debug.h)
@@ -334,6 +337,18 @@ int launch_subpix(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int ma
                   int width1, int height1, size_t step1, size_t bstride1, const uint8_t *d_img2, int width2, int height2, size_t step2,
                   size_t bstride2, int max_side, int rule, mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, float *d_kp2_out,
                   uint8_t *d_inlier, SubpixWork *work, hipStream_t s);
+
+// cornerSubPix refinement of each image on its own (subpix_separate.hip): the arguments of launch_subpix without max_side, plus d_kp1_out
+// ([batch][nq][2] or nullptr) and d_iters ([batch][match_stride][2] loop passes per match and image, or nullptr).  Two kernel launches on s
+// (the per-list windows, the refinement), no upload (subpix_separate_init, called by mlpl_ctx_create, puts the eight mask profiles into
+// WS_SUBPIX_SEP_MASK), no synchronisation.  *work (optional)
+// receives res [batch][8] = {refined, status, w1, w2, points dropped by the coordinate rule, points reset by the "too far" rule, n_out, inliers}.
+int subpix_separate_init(mlpl_ctx *ctx);
+int launch_subpix_separate(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches, int n_direct,
+                           const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2,
+                           const uint8_t *d_img1, int width1, int height1, size_t step1, size_t bstride1, const uint8_t *d_img2, int width2,
+                           int height2, size_t step2, size_t bstride2, int rule, mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status,
+                           float *d_kp1_out, float *d_kp2_out, uint8_t *d_inlier, int32_t *d_iters, SubpixWork *work, hipStream_t s);
 
 // glibc srand()/rand() (TYPE_3 additive feedback generator: r[k+3] += r[k] over a ring of 31 words, output r >> 1, the first 310
 // outputs discarded), produced 31 values at a time: one unrolled pass over the ring has no index wrap-around and three independent

@@ -448,3 +448,84 @@ def subpix_matches_device(matches, count, kp1, kp2, img1, img2, size1=None, size
         out["inlier"].data_ptr(), torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
     check(rc, "mlpl_subpix_matches_dev")
     return out
+
+
+def subpix_separate(img1, img2, kp1, kp2, size1=None, size2=None, ctx: Optional[Context] = None) -> dict:
+    """mlpl_subpix_separate (matchinglib::getSubPixMatches_seperate_Imgs: cv::cornerSubPix on each image on its own) -> dict(status,
+    kp1, kp2 float32 [n, 2], inlier bool [n], iters int32 [n, 2], n_refined, w1, w2, dropped_coord, reset_far).  Arguments as subpix_matches;
+    the smallest positive size of a list sets the window half-size of its image (3 ... 10; None: 10).  status: 0, or -1 when fewer than
+    n / 3 or fewer than 2 matches stayed within sqrt(12) px (kp1, kp2 and inlier are filled in either way).  iters: loop passes per match
+    and image.  The contract and its declared deviations: include/mlpl_c.h."""
+    ctx = ctx or default_context()
+    try:
+        i1, i2 = _image_u8(img1), _image_u8(img2)
+    except MlplError as e:
+        raise MlplError(e.code, "subpix_separate", "images are 8-bit, single channel and not empty") from None
+    a = np.array(_keypoint_xy(kp1), np.float32, copy=True)
+    b = np.array(_keypoint_xy(kp2), np.float32, copy=True)
+    n = a.shape[0]
+    if b.shape[0] != n:
+        raise MlplError(-1, "subpix_separate", "the keypoint lists must have the same length")
+    s1 = None if size1 is None else np.ascontiguousarray(size1, np.float32).reshape(-1)
+    s2 = None if size2 is None else np.ascontiguousarray(size2, np.float32).reshape(-1)
+    if (s1 is not None and len(s1) != n) or (s2 is not None and len(s2) != n):
+        raise MlplError(-1, "subpix_separate", "one size per keypoint")
+    inl, its, info, nr, st = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 2), np.int32), np.zeros(4, np.int32), C.c_int(0), C.c_int(0)
+    rc = ctx.lib.mlpl_subpix_separate(ctx.handle, i1.ctypes.data, i1.shape[1], i1.shape[0], i1.strides[0], i2.ctypes.data, i2.shape[1],
+                                      i2.shape[0], i2.strides[0], a.ctypes.data, b.ctypes.data, None if s1 is None else s1.ctypes.data,
+                                      None if s2 is None else s2.ctypes.data, n, inl.ctypes.data, its.ctypes.data, C.byref(nr), C.byref(st),
+                                      info.ctypes.data)
+    check(rc, "mlpl_subpix_separate")
+    return dict(status=st.value, kp1=a, kp2=b, inlier=inl[:n].astype(bool), iters=its[:n], n_refined=nr.value, w1=int(info[0]), w2=int(info[1]),
+                dropped_coord=int(info[2]), reset_far=int(info[3]))
+
+
+def subpix_separate_window(min_size: float, ctx: Optional[Context] = None) -> int:
+    """mlpl_subpix_separate_window: the window half-size (3 ... 10) for the smallest positive keypoint size of a list"""
+    ctx = ctx or default_context()
+    return int(ctx.lib.mlpl_subpix_separate_window(float(min_size)))
+
+
+def subpix_separate_device(matches, count, kp1, kp2, img1, img2, size1=None, size2=None, correspondences_rule: bool = False,
+                           ctx: Optional[Context] = None, out=None, stream: Optional[int] = None):
+    """Batched cornerSubPix refinement on device-resident match lists (mlpl_subpix_separate_dev); tensors as subpix_matches_device (images of
+    at least 25 x 25 pixels).  Returns dict of torch tensors matches [B, stride, 4] (the inliers, compacted), count [B], status [B],
+    kp1 [B, nq, 2] and kp2 [B, nt, 2] (every match's refined or unchanged position at its keypoint, the last match of a keypoint wins; under
+    correspondences_rule kp1 is a copy of the input), inlier uint8 [B, stride].  correspondences_rule: correspondences.cpp:474-494 -- on
+    status -1 list and keypoints pass through, on status 0 the inliers come in reverse list order.  Enqueues on `stream` (None = torch's
+    current stream) without synchronising."""
+    import torch
+
+    if matches.dim() == 2:
+        matches, count, kp1, kp2, img1, img2 = matches.unsqueeze(0), count.reshape(1), kp1.unsqueeze(0), kp2.unsqueeze(0), img1.unsqueeze(0), img2.unsqueeze(0)
+        size1 = None if size1 is None else size1.unsqueeze(0)
+        size2 = None if size2 is None else size2.unsqueeze(0)
+    assert matches.is_cuda and matches.dtype == torch.int32 and matches.is_contiguous() and matches.shape[2] == 4
+    assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()
+    assert kp1.is_cuda and kp2.is_cuda and kp1.dtype == torch.float32 and kp2.dtype == torch.float32 and kp1.is_contiguous() and kp2.is_contiguous()
+    B, stride = matches.shape[0], matches.shape[1]
+    assert count.shape == (B,) and kp1.shape[0] == B and kp2.shape[0] == B and kp1.shape[2] == 2 and kp2.shape[2] == 2
+    for im in (img1, img2):
+        assert im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[0] == B and im.stride(2) == 1 and im.stride(1) >= im.shape[2]
+    for sz, k in ((size1, kp1), (size2, kp2)):
+        assert sz is None or (sz.is_cuda and sz.dtype == torch.float32 and sz.is_contiguous() and sz.shape == k.shape[:2])
+    ctx = ctx or default_context(matches.device.index or 0)
+    if out is None:
+        out = {
+            "matches": torch.empty_like(matches),
+            "count": torch.empty((B,), dtype=torch.int32, device=matches.device),
+            "status": torch.empty((B,), dtype=torch.int32, device=matches.device),
+            "kp1": torch.empty_like(kp1),
+            "kp2": torch.empty_like(kp2),
+            "inlier": torch.zeros((B, stride), dtype=torch.uint8, device=matches.device),
+        }
+    rc = ctx.lib.mlpl_subpix_separate_dev(
+        ctx.handle, B, matches.data_ptr(), stride, count.data_ptr(), kp1.data_ptr(), kp1.shape[1], kp2.data_ptr(), kp2.shape[1],
+        None if size1 is None else size1.data_ptr(), None if size2 is None else size2.data_ptr(),
+        img1.data_ptr(), img1.shape[2], img1.shape[1], img1.stride(1), img1.stride(0) if B > 1 else 0,
+        img2.data_ptr(), img2.shape[2], img2.shape[1], img2.stride(1), img2.stride(0) if B > 1 else 0,
+        1 if correspondences_rule else 0, out["matches"].data_ptr(), out["count"].data_ptr(), out["status"].data_ptr(),
+        None if out.get("kp1") is None else out["kp1"].data_ptr(), out["kp2"].data_ptr(), out["inlier"].data_ptr(),
+        torch.cuda.current_stream(matches.device).cuda_stream if stream is None else stream)
+    check(rc, "mlpl_subpix_separate_dev")
+    return out

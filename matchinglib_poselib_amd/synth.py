@@ -276,3 +276,27 @@ def subpix_scene(kind: str, n: int, seed: int = 0, width: int = 320, height: int
     return dict(img1=np.ascontiguousarray(img1), img2=np.ascontiguousarray(img2), kp1=np.ascontiguousarray(kp1, np.float32),
                 kp2=np.ascontiguousarray(kp2, np.float32), size1=sizes.copy(), size2=sizes.copy(), truth=np.ascontiguousarray(truth, np.float32),
                 scrambled=scr)
+
+
+def corner_scene(width: int = 320, height: int = 240, cell: float = 24.0, angle: float = 0.12, origin=(5.3, 7.7), low: int = 40, high: int = 210,
+                 supersample: int = 8, margin: float = 14.0):
+    """An anti-aliased checkerboard with known sub-pixel corner positions, for the corner refinement (matchinglib::getSubPixMatches_seperate_Imgs).
+    The board has square cells of `cell` pixels and grey levels `low` / `high`, is rotated by `angle` radians and has a corner at `origin`;
+    pixel (x, y) is the mean of supersample^2 samples of the board over the unit square centred on (x, y).  Returns dict(img: uint8
+    [height, width], corners: float32 [m, 2] (x, y), row by row of the board: the cell corners at least `margin` pixels inside the image)."""
+    c, s = np.cos(angle), np.sin(angle)
+    sub = (np.arange(supersample) + 0.5) / supersample - 0.5
+    ys = (np.arange(height)[:, None] + sub[None, :]).reshape(-1)
+    xs = (np.arange(width)[:, None] + sub[None, :]).reshape(-1)
+    X, Y = xs[None, :] - origin[0], ys[:, None] - origin[1]
+    u, v = c * X + s * Y, -s * X + c * Y
+    odd = (np.floor(u / cell) + np.floor(v / cell)).astype(np.int64) & 1
+    fine = np.where(odd == 1, float(high), float(low))
+    img = fine.reshape(height, supersample, width, supersample).mean(axis=(1, 3))
+    reach = int(np.ceil((width + height) / cell)) + 2
+    k = np.arange(-reach, reach + 1) * cell
+    bu, bv = np.meshgrid(k, k)                                   # rows of the board: v fixed, u running
+    cx, cy = origin[0] + c * bu - s * bv, origin[1] + s * bu + c * bv
+    keep = (cx >= margin) & (cx <= width - 1 - margin) & (cy >= margin) & (cy <= height - 1 - margin)
+    corners = np.stack([cx[keep], cy[keep]], axis=1)
+    return dict(img=np.ascontiguousarray(np.clip(np.rint(img), 0, 255).astype(np.uint8)), corners=np.ascontiguousarray(corners, np.float32))

@@ -172,6 +172,14 @@ int getPoseTriangPts(cv::InputArray E, cv::InputArray p1, cv::InputArray p2, cv:
                      cv::OutputArray Q, cv::InputOutputArray mask = cv::noArray(), const double dist = 50.0,
                      bool translatE = false);
 
+// poselib::triangPts3D (pose_estim.h:202, pose_estim.cpp:964-1044): triangulation with a GIVEN pose, P0 = [I|0], P1 = [R|t].  R 3 x 3,
+// t 3 x 1, points n x 2, all CV_64F (asserted); Q3D receives n x 3 CV_64F, every point (inf / NaN where the homogeneous w is zero); mask
+// (1 x n CV_8U, optional) is AND-ed with (P1 X).z * w > 0, z / w < dist and z / w > 0 -- an incoming 1 stays 1; an empty or absent mask means all
+// points and receives nothing.  Returns the number of valid points; -1 for an empty point set (checked first, the mask untouched) and -1 when Q3D is
+// cv::noArray() (checked after the mask has been updated, as in the reference).
+int triangPts3D(cv::InputArray R, cv::InputArray t, cv::InputArray points1, cv::InputArray points2, cv::OutputArray Q3D,
+                cv::InputOutputArray mask = cv::noArray(), const double dist = 50.0);
+
 // Convenience named in BASELINE.json: estimateEssentialMat(..., "RANSAC", ...) followed by getPoseTriangPts, the
 // sequence the reference's README prescribes (README.md:497-521).
 bool estimateRelativePose(cv::InputArray p1, cv::InputArray p2, cv::OutputArray E, cv::OutputArray R, cv::OutputArray t,

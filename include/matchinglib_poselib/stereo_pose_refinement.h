@@ -8,17 +8,25 @@
 // near-to-mean pose rating and the stability flags (:2817-3298), maxSkipPairs handling (:3300-3317).
 // Every robust estimation and every error evaluation runs on the MI355X (estimateEssentialMat / getPoseTriangPts / mlpl_get_inliers_strict).
 //
-// Not built (outside the hot path): homography alignment (Halign), the linear refinement solvers
-// (refineMethod / refineMethod_CorrPool: Nister/Stewenius/Kneip/8pt with weights) and bundle adjustment (BART).  refineRTold IS built: the
-// estimator's own refinement step plus poselib::robustEssentialRefine on the inliers (:1460-1474), on the device.  Consequences, all
-// reported once on std::cout:
+// The refinement schedule is the reference's: after the robust estimation refineRTold (the estimator's own refinement step plus
+// poselib::robustEssentialRefine on the inliers, :1460-1474) or poselib::refineEssentialLinear with refineMethod (:1476-1553), then
+// getPoseTriangPts -- or, when Kneip's solver returned the pose itself, poselib::triangPts3D with that pose, falling back to
+// getPoseTriangPts when fewer than a third of the inliers and fewer than 100 points triangulate (:1556-1578); kneipInsteadBA runs Kneip's
+// solver in the place of bundle adjustment, with the reference's failure path (:1594-1692).  Between robust estimations
+// (checkPoolPoseRobust != 1, :680-716) the pool pose is refined by refinePoseFromPool (:1767-2074) with refineRTold_CorrPool,
+// refineMethod_CorrPool or kneipInsteadBA_CorrPool in the same way, starting from R_new / t_new.  All of it on the device.
+//
+// Not built (outside the hot path): homography alignment (Halign), bundle adjustment (BART, BART_CorrPool)
+// and, inside USAC, Kneip's estimator and refinements.  Consequences:
 //   * RobMethod is "USAC" (the reference's default; estimateEssentialOrPoseUSAC with the ConfigUSAC handed to addNewCorrespondences, a
 //     degenerate pair -> -2, :1355-1413), "RANSAC", "LMEDS" or "ARRSAC"; Halign makes addNewCorrespondences() return -1; autoTH (ARRSAC
 //     with poselib::AutoThEpi's threshold estimation, :1330-1342) is built;
-//   * refinement / BA options are ignored;
-//   * between robust estimations the pool pose is REFINED (checkPoolPoseRobust != 1, the reference's schedule :680-716) only with
-//     refineRTold_CorrPool, the refinement that is built (refinePoseFromPool :1767-2084 with robustEssentialRefine on the device);
-//     with the linear solvers selected the pool is re-estimated robustly on every frame (the reference's checkPoolPoseRobust = 1);
+//   * BART / BART_CorrPool are ignored (reported once on std::cout); where the reference would hand a failed Kneip-instead-of-BA step to
+//     bundle adjustment it takes its other path, Stewenius with pseudo-Huber weights;
+//   * no estimator hands a pose over, so the refinement after the robust estimation never starts from one (`availableRT` starts false,
+//     :1429-1449): Kneip's solver there starts from up to 12 perturbed identities drawn from setRansacSeed's seed;
+//   * a configuration without a linear refinement keeps the estimator's E as it is, where the reference rebuilds it from R and t
+//     (:1721); with one selected E is rebuilt as there;
 //   * thinning an over-full pool follows checkPoolSize (:2550-2816): a density image of the pool's left keypoints, elliptic dilate /
 //     erode with the reference's border handling, then the weights;
 //   * the radius search over the pool returns neighbours by ascending squared distance, as the reference's
@@ -137,6 +145,9 @@ class StereoRefine {
     double inlierThreshold() const;
     size_t nrInliersNew() const;
     size_t nrCorrsNew() const;
+    // where the pose of the last addNewCorrespondences() came from: 0 no pose was computed, 1 getPoseTriangPts, 2 triangPts3D with the pose of
+    // Kneip's solver, 3 that triangulation rejected and getPoseTriangPts instead, 4 Kneip's solver instead of bundle adjustment
+    int lastPoseSource() const;
     size_t nrEstimations() const;
     size_t skipCounter() const;
     size_t poseHistorySize() const;

@@ -808,6 +808,24 @@ int mlpl_recover_pose_translation(mlpl_ctx *ctx, const double t_only[3], const d
 int mlpl_recover_pose_dev(mlpl_ctx *ctx, const double E[9], const double *d_p1, const double *d_p2, int n, double dist,
                           double R[9], double t[3], double *d_Q, uint8_t *d_mask_inout, void *stream);
 
+/* Triangulation with a GIVEN pose: poselib::triangPts3D (P/source/pose_estim.cpp:964-1044), P0 = [I|0], P1 = [R|t].  Per correspondence
+ * the DLT null vector X of mlpl_recover_pose (unit norm), then m = ((P1 X).z * X.w > 0) & mask, Q = X.xyz / X.w by division,
+ * m &= (Q.z < dist) & (Q.z > 0): both comparisons on the quotient, so that X.w = 0 (inf / NaN) fails them, as in the reference.
+ * R: 9, t: 3 (host); Q: n x 3 doubles or NULL, written for EVERY point, masked or not; mask_inout: n bytes or NULL (= all points), rewritten
+ * as in & (m ? 255 : 0).  Returns the number of points that pass (>= 0) or a negative error.  With Q NULL a point outside the incoming mask
+ * is not triangulated at all.  (The reference returns -1 without Q after it has updated the mask; that rule lives in the C++ drop-in.) */
+int mlpl_triang_pts3d(mlpl_ctx *ctx, const double R[9], const double t[3], const double *p1, const double *p2, int n, double dist, double *Q,
+                      uint8_t *mask_inout);
+/* The same on device-resident correspondences (d_p1, d_p2: n x 2 doubles; d_Q: n x 3 doubles or NULL; d_mask_inout: n bytes or NULL);
+ * only the count is read back. */
+int mlpl_triang_pts3d_dev(mlpl_ctx *ctx, const double R[9], const double t[3], const double *d_p1, const double *d_p2, int n, double dist,
+                          double *d_Q, uint8_t *d_mask_inout, void *stream);
+/* A batch in the layout of mlpl_recover_pose_batch_dev (it chains behind mlpl_refine_essential_linear_rt_batch_dev): R + 9 b, t + 3 b
+ * (host), d_masks NULL or [n_problems][stride] (in / out; bytes beyond counts[b] untouched), d_Q NULL or [n_problems][stride][3],
+ * n_good[b] (host).  One launch for the whole batch; every problem's mask, count and points are bit-identical to mlpl_triang_pts3d's. */
+int mlpl_triang_pts3d_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                const double *R, const double *t, double dist, uint8_t *d_masks, double *d_Q, int32_t *n_good, void *stream);
+
 
 /* The diagnostics entry points (mlpl_debug_*: traces, clock stamps, solver statistics, self-tests -- exported by the same library, used by
  * the tests and by bench.py, not part of the drop-in surface) are declared in mlpl_debug.h. */

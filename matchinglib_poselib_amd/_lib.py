@@ -190,6 +190,10 @@ _SIGNATURES = {
                                               c_void_p, c_void_p]),
     "mlpl_recover_pose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "mlpl_triang_pts3d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p]),
+    "mlpl_triang_pts3d_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_triang_pts3d_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
 }
 
 

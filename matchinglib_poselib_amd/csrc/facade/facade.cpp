@@ -754,6 +754,46 @@ int getPoseTriangPts(cv::InputArray E_, cv::InputArray p1, cv::InputArray p2, cv
     return rc;
 }
 
+int triangPts3D(cv::InputArray R_, cv::InputArray t_, cv::InputArray points1, cv::InputArray points2, cv::OutputArray Q3D,
+                cv::InputOutputArray mask_, const double dist) {
+    // pose_estim.cpp:964-1044.  An empty point set returns first (:992-994, the mask untouched); without Q3D the mask is updated and
+    // -1 returned afterwards (:1011-1012)
+    CV_Assert(points1.type() == CV_64F && points2.type() == CV_64F && R_.type() == CV_64F && t_.type() == CV_64F);
+    int n1 = 0, n2 = 0;
+    std::vector<double> a = points64(points1, n1), b = points64(points2, n2);
+    CV_Assert(n1 == n2);
+    if (n1 == 0) return -1;
+    const cv::Mat R = R_.getMat(), t = t_.getMat();
+    CV_Assert(R.rows == 3 && R.cols == 3 && t.rows * t.cols == 3);
+    double Rv[9], tv[3];
+    for (int i = 0; i < 9; ++i) Rv[i] = R.at<double>(i / 3, i % 3);
+    for (int i = 0; i < 3; ++i) tv[i] = t.rows == 1 ? t.at<double>(0, i) : t.at<double>(i, 0);
+    // a mask counts when one is passed AND holds something (:973-976, :997-1004): the reference's result then lands in the caller's
+    // matrix (a MatExpr assigned in place into a header that shares its data); an empty passed mask stays empty, as there
+    const bool use_mask = mask_.needed() && !mask_.empty();
+    std::vector<uint8_t> m;
+    if (use_mask) {
+        const cv::Mat mask = mask_.getMat();
+        CV_Assert(mask.rows * mask.cols == n1 && mask.type() == CV_8U);
+        m.resize((size_t)n1);
+        for (int i = 0; i < n1; ++i) m[i] = mask.rows == 1 ? mask.at<uint8_t>(0, i) : mask.at<uint8_t>(i, 0);
+    }
+    const bool want_Q = Q3D.needed();
+    std::vector<double> Qv(want_Q ? (size_t)n1 * 3 : 0);
+    const int rc = mlpl_triang_pts3d(default_ctx(), Rv, tv, a.data(), b.data(), n1, dist, want_Q ? Qv.data() : nullptr, use_mask ? m.data() : nullptr);
+    if (rc < 0) throw cv::Exception(std::string("mlpl_triang_pts3d: ") + mlpl_last_error());
+    if (use_mask) {
+        cv::Mat mo = mask_.getMat();
+        for (int i = 0; i < n1; ++i) (mo.rows == 1 ? mo.at<uint8_t>(0, i) : mo.at<uint8_t>(i, 0)) = m[i];
+    }
+    if (!want_Q) return -1;  // "The matrix for the 3D points must be provided"
+    Q3D.create(n1, 3, CV_64F);
+    cv::Mat Q = Q3D.getMat();
+    for (int i = 0; i < n1; ++i)
+        for (int c = 0; c < 3; ++c) Q.at<double>(i, c) = Qv[(size_t)i * 3 + c];
+    return rc;
+}
+
 bool estimateRelativePose(cv::InputArray p1, cv::InputArray p2, cv::OutputArray E, cv::OutputArray R, cv::OutputArray t,
                           cv::OutputArray Q, cv::OutputArray mask, double threshold, bool refine, double dist) {
     cv::Mat m;

@@ -13,6 +13,7 @@
 #include <unordered_set>
 
 #include "facade_internal.h"
+#include "matchinglib_poselib/pose_linear_refinement.h"
 #include "matchinglib_poselib/stereo_pose_refinement.h"
 #include "mlpl_c.h"
 
@@ -95,6 +96,42 @@ cv::Mat mat31(const double *v) {
     cv::Mat m(3, 1, CV_64F);
     for (int i = 0; i < 3; ++i) m.at<double>(i, 0) = v[i];
     return m;
+}
+
+int countNonZero(const cv::Mat &m) {
+    int c = 0;
+    for (int i = 0; i < m.cols; ++i) c += m.at<uint8_t>(0, i) != 0;
+    return c;
+}
+
+// isMatRoationMat (pose_helper.cpp:2947-2954): every entry of R^T R - I within 1e-3 (Eigen's isZero against the unit reference) and
+// det R - 1 near zero
+bool isRotation(const double *R) {
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R[i])) return false;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double v = R[r] * R[c] + R[3 + r] * R[3 + c] + R[6 + r] * R[6 + c] - (r == c ? 1.0 : 0.0);
+            if (std::abs(v) > 1e-3) return false;
+        }
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    return nearZero(det - 1.0);
+}
+
+// getEfromRT (pose_helper.cpp:785-788): [t / |t|]x R
+void eFromRT(const cv::Mat &R, const cv::Mat &t, double *E) {
+    double nrm = 0;
+    for (int i = 0; i < 3; ++i) nrm += t.at<double>(i, 0) * t.at<double>(i, 0);
+    nrm = std::sqrt(nrm);
+    double tn[3];
+    for (int i = 0; i < 3; ++i) tn[i] = t.at<double>(i, 0) / nrm;
+    const double S[9] = {0, -tn[2], tn[1], tn[2], 0, -tn[0], -tn[1], tn[0], 0};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            double v = 0;
+            for (int k = 0; k < 3; ++k) v += S[r * 3 + k] * R.at<double>(k, c);
+            E[r * 3 + c] = v;
+        }
 }
 
 }  // namespace
@@ -211,6 +248,15 @@ struct StereoRefine::Impl {
     int robustEstimationOnPool();
     int refinePoseFromPool();
     size_t failed_refinements = 0;  // function-local static in the reference (:678): process-wide there, per object here
+    int last_pose_source = 0;  // lastPoseSource()
+    // refineEssentialLinear as StereoRefine always calls it: th, 4 steps, 2.0, 0.1, 0.15; nr_inliers_new follows an accepted refinement
+    bool refineLinear(const cv::Mat &P1, const cv::Mat &P2, cv::Mat &E, cv::Mat &mask, int method, cv::Mat *R, cv::Mat *t) {
+        if (R && t) return refineEssentialLinear(P1, P2, E, mask, method, nr_inliers_new, *R, *t, th, 4, 2.0, 0.1, 0.15);
+        return refineEssentialLinear(P1, P2, E, mask, method, nr_inliers_new, cv::noArray(), cv::noArray(), th, 4, 2.0, 0.1, 0.15);
+    }
+    bool triangWithPose(const cv::Mat &P1, const cv::Mat &P2, const cv::Mat &E, cv::Mat &R, cv::Mat &t, cv::Mat &Q3, cv::Mat &mask,
+                       const cv::Mat &mask_before, int &source);
+    void storePose(const cv::Mat &E, const cv::Mat &R, const cv::Mat &t, bool rebuildE, const cv::Mat &mask, const cv::Mat &Q3);
     int addCorrespondencesToPool(const std::vector<cv::DMatch> &matches, const std::vector<cv::KeyPoint> &kp1,
                                  const std::vector<cv::KeyPoint> &kp2);
     int filterNewCorrespondences(std::vector<cv::DMatch> &matches, const std::vector<cv::KeyPoint> &kp1,
@@ -266,17 +312,9 @@ void StereoRefine::Impl::checkInputParamters() {  // :187-400 (values only; the 
     if (c.minContStablePoses <= 2) c.minContStablePoses = 3;
     if (c.absThRankingStable < 0.01) c.absThRankingStable = 0.01;
     else if (c.absThRankingStable > 0.9) c.absThRankingStable = 0.6;
-    // The pool is REFINED between robust estimations (checkPoolPoseRobust != 1) only through refineRTold_CorrPool, the refinement that is
-    // built (robustEssentialRefine on the device); with the linear solvers (refineMethod_CorrPool) selected instead, the pool is
-    // re-estimated robustly on every frame (the reference's checkPoolPoseRobust = 1).
-    if (c.checkPoolPoseRobust != 1 && !c.refineRTold_CorrPool) {
-        notice("the linear refinement solvers of the correspondence pool are not built; the pool is re-estimated robustly on every frame "
-               "(the reference's checkPoolPoseRobust = 1); set refineRTold_CorrPool for the refinement that is built");
-        c.checkPoolPoseRobust = 1;
-    }
-    if ((c.refineMethod & 0xF) != PR_NO_REFINEMENT || c.refineRTold || c.kneipInsteadBA || c.BART || c.BART_CorrPool)
-        notice("refinement after the robust estimation (refineMethod, refineRTold beyond the estimator's own refit, kneipInsteadBA, "
-               "BART) is not built and is skipped");
+    // Built: the linear refinement solvers after the robust estimation (refineMethod, kneipInsteadBA) and on the pool between robust
+    // estimations (refineMethod_CorrPool, kneipInsteadBA_CorrPool, checkPoolPoseRobust != 1).  Not built: bundle adjustment.
+    if (c.BART || c.BART_CorrPool) notice("bundle adjustment (BART, BART_CorrPool) is not built and is skipped");
     noticed = true;
 }
 
@@ -325,7 +363,8 @@ void StereoRefine::Impl::reprojErrors(const std::vector<double> &a, const std::v
 }
 
 // robustPoseEstimation (:1272-1760), the branches of the estimators built here: optional switch to RANSAC for < 100 matches,
-// estimateEssentialMat(RobMethod, th, refineRTold), getPoseTriangPts(maxDist3DPtsZ), t normalised.
+// estimateEssentialMat(RobMethod, th, refineRTold), the refinement (refineRTold / refineMethod / kneipInsteadBA), getPoseTriangPts or
+// triangPts3D(maxDist3DPtsZ), t normalised.
 int StereoRefine::Impl::robustPoseEstimation() {
     have_Q = false;
     Qv.clear();
@@ -365,29 +404,117 @@ int StereoRefine::Impl::robustPoseEstimation() {
         std::cout << "Estimation of essential matrix using " << method << " failed!" << std::endl;
         return -1;
     }
+    nr_inliers_new = (size_t)countNonZero(mask);
     mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
-    nr_inliers_new = 0;
-    for (uint8_t v : mask_E_new) nr_inliers_new += v != 0;
-    if (cfg_pose.refineRTold)  // :1460-1474: the "old" robust refinement on the inliers, threshold th / 10; the mask stays
-        robustEssentialRefine(P1, P2, E, E, th / 10.0, 0, true, nullptr, nullptr, cv::noArray(), mask, 0);
+    // :1429-1579.  availableRT starts false: the poses Halign and USAC's Kneip refinements hand over are not built, so of the reference's
+    // three refineEssentialLinear call shapes the one that passes such a pose never runs.
+    bool availableRT = false;
+    const int solver = cfg_pose.refineMethod & 0xF;
+    // what follows :1695-1722 literally (useBA -> E rebuilt from R and t); without a linear refinement E is copied, as before
+    const bool rebuild = cfg_pose.kneipInsteadBA || (solver != PR_NO_REFINEMENT && !cfg_pose.refineRTold);
     cv::Mat R, t, Q3;
-    if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {  // :1557
+    if (cfg_pose.refineRTold) {  // :1460-1474: the "old" robust refinement on the inliers, threshold th / 10; the mask stays
+        robustEssentialRefine(P1, P2, E, E, th / 10.0, 0, true, nullptr, nullptr, cv::noArray(), mask, 0);
+    } else if (solver != PR_NO_REFINEMENT && !cfg_pose.kneipInsteadBA) {
+        if (solver == PR_KNEIP) {  // :1508-1535: R passed empty -> the 12 perturbed starts drawn from setRansacSeed's seed
+            cv::Mat R_tmp, t_tmp;
+            if (refineLinear(P1, P2, E, mask, cfg_pose.refineMethod, &R_tmp, &t_tmp)) {
+                if (!R_tmp.empty() && !t_tmp.empty()) {
+                    R = R_tmp.clone(), t = t_tmp.clone();
+                    availableRT = true;
+                } else {
+                    std::cout << "Refinement failed!" << std::endl;
+                }
+            }
+        } else if (!refineLinear(P1, P2, E, mask, cfg_pose.refineMethod, nullptr, nullptr)) {  // :1538-1551
+            std::cout << "Refinement failed!" << std::endl;
+        }
+    }
+    mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);  // :1554
+    if (!availableRT) {
+        if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {  // :1557
+            std::cout << "Unable to triangulate 3D points" << std::endl;
+            return -1;
+        }
+        last_pose_source = 1;
+    } else if (!triangWithPose(P1, P2, E, R, t, Q3, mask, mask.clone(), last_pose_source)) {  // :1563-1577
         std::cout << "Unable to triangulate 3D points" << std::endl;
         return -1;
     }
-    copy9(E, E_);
+    bool useBA = true;
+    if (cfg_pose.kneipInsteadBA) {  // :1594-1692
+        cv::Mat R_tmp = R.clone(), t_tmp = t.clone();
+        bool kneipSuccess = false;
+        if (refineLinear(P1, P2, E, mask, cfg_pose.refineMethod, &R_tmp, &t_tmp) && !R_tmp.empty() && !t_tmp.empty()) {
+            mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
+            int src = 0;
+            if (triangWithPose(P1, P2, E, R_tmp, t_tmp, Q3, mask, mask.clone(), src)) {
+                R = R_tmp.clone(), t = t_tmp.clone();
+                useBA = false;
+                kneipSuccess = true;
+                last_pose_source = 4;
+            }
+        }
+        if (!kneipSuccess) {
+            std::cout << "Refinement using Kneips Eigen solver instead of bundle adjustment (BA) failed!" << std::endl;
+            // BART is not built: the reference's path without it
+            std::cout << "Trying refinement with weighted (Pseudo-Huber) Stewenius instead!" << std::endl;
+            const int refineMethod_save = cfg_pose.refineMethod;
+            cfg_pose.refineMethod = PR_STEWENIUS | PR_PSEUDOHUBER_WEIGHTS;
+            // (sic) :1665-1689: the test is inverted -- a refinement that SUCCEEDS is reported as failed and ends the estimation (with
+            // refineMethod left at the fallback's value), only a failing one goes on to the triangulation
+            if (!refineLinear(P1, P2, E, mask, cfg_pose.refineMethod, nullptr, nullptr)) {
+                mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
+                Q3 = cv::Mat();
+                if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+                    std::cout << "Unable to triangulate 3D points" << std::endl;
+                    return -1;
+                }
+                last_pose_source = 1;
+            } else {
+                std::cout << "Refinement failed!" << std::endl;
+                return -1;
+            }
+            cfg_pose.refineMethod = refineMethod_save;
+        }
+    }
+    storePose(E, R, t, useBA && rebuild, mask, Q3);
+    return 0;
+}
+
+// triangPts3D with the pose a Kneip refinement returned and the reference's plausibility rule (:1566-1577, :1900-1912): fewer valid points
+// than a third of the inliers and fewer than 100 -> the four-way test of getPoseTriangPts on the mask from before.  source: 2 = accepted,
+// 3 = rejected.  False: triangPts3D returned an error (an empty set) or the four-way test found no point.
+bool StereoRefine::Impl::triangWithPose(const cv::Mat &P1, const cv::Mat &P2, const cv::Mat &E, cv::Mat &R, cv::Mat &t, cv::Mat &Q3,
+                                       cv::Mat &mask, const cv::Mat &mask_before, int &source) {
+    const int n_triang = triangPts3D(R, t, P1, P2, Q3, mask, cfg_pose.maxDist3DPtsZ);
+    source = 2;
+    if (n_triang < 0) return false;
+    if (n_triang < countNonZero(mask_before) / 3 && n_triang < 100) {
+        source = 3;
+        Q3 = cv::Mat();
+        mask = mask_before.clone();
+        return getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) > 0;
+    }
+    return true;
+}
+
+// E_new / R_new / t_new (unit length) / mask_Q_new / Q of an estimation (:1724-1729, :2055-2059)
+void StereoRefine::Impl::storePose(const cv::Mat &E, const cv::Mat &R, const cv::Mat &t, bool rebuildE, const cv::Mat &mask, const cv::Mat &Q3) {
+    const int n = mask.cols;
+    if (rebuildE) eFromRT(R, t, E_);
+    else copy9(E, E_);
     copy9(R, R_);
     double nrm = 0;
     for (int i = 0; i < 3; ++i) nrm += t.at<double>(i, 0) * t.at<double>(i, 0);
     nrm = std::sqrt(nrm);
-    for (int i = 0; i < 3; ++i) t_[i] = t.at<double>(i, 0) / nrm;  // :1727-1728
+    for (int i = 0; i < 3; ++i) t_[i] = t.at<double>(i, 0) / nrm;
     have_pose = true;
     mask_Q_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
     Qv.resize((size_t)n * 3);
     for (int i = 0; i < n; ++i)
         for (int c = 0; c < 3; ++c) Qv[(size_t)i * 3 + c] = Q3.at<double>(i, c);
     have_Q = true;
-    return 0;
 }
 
 int StereoRefine::Impl::robustInitialization(double &inlier_ratio, std::vector<cv::DMatch> &matches, std::vector<cv::KeyPoint> &kp1,
@@ -451,9 +578,9 @@ int StereoRefine::Impl::robustEstimationOnPool() {  // :1075-1128: the robust es
     return rc ? -1 : 0;
 }
 
-// refinePoseFromPool (:1767-2084) for refineRTold_CorrPool: robustEssentialRefine of the current E on ALL pool correspondences (th / 10),
-// R, t and the 3-D points from the refined matrix, E rebuilt from them (getEfromRT, pose_helper.cpp:785-788).  No correspondence is
-// marked as an outlier on this path.
+// refinePoseFromPool (:1767-2084): the current E refined on ALL pool correspondences -- robustEssentialRefine (refineRTold_CorrPool, th / 10)
+// or refineEssentialLinear with refineMethod_CorrPool, starting from R_new / t_new when they are a pose -- then R, t and the 3-D points,
+// E rebuilt from them (getEfromRT) unless Kneip's solver ran instead of bundle adjustment.
 int StereoRefine::Impl::refinePoseFromPool() {
     const int n = (int)(p1Cam.size() / 2);
     nr_inliers_new = (size_t)n;
@@ -463,32 +590,90 @@ int StereoRefine::Impl::refinePoseFromPool() {
     cv::Mat E(3, 3, CV_64F), mask(1, n, CV_8U);
     for (int i = 0; i < 9; ++i) E.at<double>(i / 3, i % 3) = E_[i];
     std::memset(mask.ptr<uint8_t>(0), 1, (size_t)n);
-    robustEssentialRefine(P1, P2, E, E, th / 10.0, 0, true, nullptr, nullptr, cv::noArray(), mask, 0);
-    mask_E_new.assign((size_t)n, 1);
-    cv::Mat R, t, Q3;
-    if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+    cv::Mat R, t, Q3;  // R_new, t_new
+    bool availableRT = false;
+    if (have_pose) {  // :1781-1792
+        R = mat33(R_), t = mat31(t_);
+        availableRT = !nearZero(t_[0] + t_[1] + t_[2]) && isRotation(R_);
+    }
+    const int solver = cfg_pose.refineMethod_CorrPool & 0xF;
+    if (cfg_pose.refineRTold_CorrPool) {
+        robustEssentialRefine(P1, P2, E, E, th / 10.0, 0, true, nullptr, nullptr, cv::noArray(), mask, 0);
+        availableRT = false;
+    } else if (solver != PR_NO_REFINEMENT && !cfg_pose.kneipInsteadBA_CorrPool) {
+        cv::Mat R_tmp, t_tmp;
+        if (availableRT) {  // :1802-1836 (a solver other than Kneip's clears the passed R: the four-way test decides the pose)
+            R_tmp = R.clone(), t_tmp = t.clone();
+            if (!refineLinear(P1, P2, E, mask, cfg_pose.refineMethod_CorrPool, &R_tmp, &t_tmp)) {
+                std::cout << "Refinement failed!" << std::endl;
+                return -1;
+            }
+            if (!R_tmp.empty() && !t_tmp.empty()) R = R_tmp.clone(), t = t_tmp.clone();
+            else availableRT = false;
+        } else if (solver == PR_KNEIP) {  // :1837-1866
+            if (refineLinear(P1, P2, E, mask, cfg_pose.refineMethod_CorrPool, &R_tmp, &t_tmp)) {
+                if (R_tmp.empty() || t_tmp.empty()) {
+                    std::cout << "Refinement failed!" << std::endl;
+                    return -1;
+                }
+                R = R_tmp.clone(), t = t_tmp.clone();
+                availableRT = true;
+            }
+        } else if (!refineLinear(P1, P2, E, mask, cfg_pose.refineMethod_CorrPool, nullptr, nullptr)) {  // :1869-1885
+            std::cout << "Refinement failed!" << std::endl;
+            return -1;
+        }
+    }
+    mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);  // :1888
+    if (!availableRT) {
+        if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+            std::cout << "No 3D points left after triangulation!" << std::endl;
+            return -1;
+        }
+        last_pose_source = 1;
+    } else if (!triangWithPose(P1, P2, E, R, t, Q3, mask, mask.clone(), last_pose_source)) {  // :1900-1912
         std::cout << "No 3D points left after triangulation!" << std::endl;
         return -1;
     }
-    double nrm = 0;
-    for (int i = 0; i < 3; ++i) nrm += t.at<double>(i, 0) * t.at<double>(i, 0);
-    nrm = std::sqrt(nrm);
-    double tn[3];
-    for (int i = 0; i < 3; ++i) tn[i] = t.at<double>(i, 0) / nrm;
-    const double S[9] = {0, -tn[2], tn[1], tn[2], 0, -tn[0], -tn[1], tn[0], 0};
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            double v = 0;
-            for (int k = 0; k < 3; ++k) v += S[r * 3 + k] * R.at<double>(k, c);
-            E_[r * 3 + c] = v;
+    bool useBA = true;
+    if (cfg_pose.kneipInsteadBA_CorrPool) {  // :1929-2032
+        cv::Mat R_tmp = R.clone(), t_tmp = t.clone();
+        bool kneipSuccess = false;
+        if (refineLinear(P1, P2, E, mask, cfg_pose.refineMethod_CorrPool, &R_tmp, &t_tmp) && !R_tmp.empty() && !t_tmp.empty()) {
+            const cv::Mat mask_tmp1 = mask.clone();
+            int src = 0;
+            const bool ok = triangWithPose(P1, P2, E, R_tmp, t_tmp, Q3, mask, mask_tmp1, src);
+            if (!ok && src == 3) {  // :1958-1961: here a fallback without points ends the refinement
+                std::cout << "No 3D points left after triangulation!" << std::endl;
+                return -1;
+            }
+            if (ok) {
+                R = R_tmp.clone(), t = t_tmp.clone();
+                mask_E_new.assign(mask_tmp1.ptr<uint8_t>(0), mask_tmp1.ptr<uint8_t>(0) + n);
+                useBA = false;
+                kneipSuccess = true;
+                last_pose_source = 4;
+            }
         }
-    copy9(R, R_);
-    for (int i = 0; i < 3; ++i) t_[i] = tn[i];
-    mask_Q_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
-    Qv.resize((size_t)n * 3);
-    for (int i = 0; i < n; ++i)
-        for (int c = 0; c < 3; ++c) Qv[(size_t)i * 3 + c] = Q3.at<double>(i, c);
-    have_Q = true;
+        if (!kneipSuccess) {
+            std::cout << "Refinement using Kneips Eigen solver instead of bundle adjustment (BA) failed!" << std::endl;
+            std::cout << "Trying refinement with weighted (Pseudo-Huber) Stewenius instead!" << std::endl;  // BART_CorrPool is not built
+            const int method = PR_STEWENIUS | PR_PSEUDOHUBER_WEIGHTS;
+            // (sic) :2001-2028: inverted as in robustPoseEstimation; here refineMethod_CorrPool is restored on every path
+            if (refineLinear(P1, P2, E, mask, method, &R_tmp, &t_tmp)) {
+                std::cout << "Refinement failed!" << std::endl;
+                return -1;
+            }
+            mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
+            Q3 = cv::Mat();
+            if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+                std::cout << "No 3D points left after triangulation!" << std::endl;
+                return -1;
+            }
+            last_pose_source = 1;
+        }
+    }
+    storePose(E, R, t, useBA, mask, Q3);
     return 0;
 }
 
@@ -1198,6 +1383,7 @@ int StereoRefine::Impl::checkPoseStability() {  // :3131-3298
 int StereoRefine::Impl::addNewCorrespondences(std::vector<cv::DMatch> &matches, std::vector<cv::KeyPoint> &kp1,
                                               std::vector<cv::KeyPoint> &kp2, const ConfigUSAC &cfg) {
     cfg_usac = cfg;
+    last_pose_source = 0;
     // the caller's pointers describe the matches of this call (tests/poselib-test/main.cpp:1944-1957); the by-value copies this function
     // works on are the same data and stay alive for the whole call, where the reference re-points cfg_usac.matches at them (:625-649)
     if (cfg.matches) cfg_usac.matches = &matches, cfg_usac.keypoints1 = &kp1, cfg_usac.keypoints2 = &kp2;
@@ -1517,6 +1703,7 @@ size_t StereoRefine::getCorrespondencePoolSize() { return d->correspondencePool.
 double StereoRefine::inlierThreshold() const { return d->th; }
 size_t StereoRefine::nrInliersNew() const { return d->nr_inliers_new; }
 size_t StereoRefine::nrCorrsNew() const { return d->nr_corrs_new; }
+int StereoRefine::lastPoseSource() const { return d->last_pose_source; }
 size_t StereoRefine::nrEstimations() const { return d->nrEstimation; }
 size_t StereoRefine::skipCounter() const { return d->skipCount; }
 size_t StereoRefine::poseHistorySize() const { return d->pose_history.size(); }

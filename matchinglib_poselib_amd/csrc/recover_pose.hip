@@ -14,6 +14,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "mlpl_internal.h"
 
@@ -142,6 +143,30 @@ __device__ __forceinline__ void jacobi4_right_vectors(double (&G)[4][4], double 
     }
 }
 
+// The DLT step of every triangulation here (cv::triangulatePoints for one correspondence): the 4 x 4 system of view 1 = [I|0] and view 2 = Pc
+// (3 x 4, row-major), its right singular vectors, and the one of the smallest singular value -> X (unit norm, homogeneous).
+__device__ __forceinline__ void dlt_null_vector(const double *__restrict__ Pc, double x1, double y1, double x2, double y2, double (&X)[4]) {
+    double G[4][4], V[4][4];
+    const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        G[0][k] = x1 * P0[8 + k] - P0[k];
+        G[1][k] = y1 * P0[8 + k] - P0[4 + k];
+        G[2][k] = x2 * Pc[8 + k] - Pc[k];
+        G[3][k] = y2 * Pc[8 + k] - Pc[4 + k];
+    }
+    jacobi4_right_vectors(G, V);
+    double w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = G[0][j] * G[0][j] + G[1][j] * G[1][j] + G[2][j] * G[2][j] + G[3][j] * G[3][j];
+    int m = 0;
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (w[j] < w[m]) m = j;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) X[k] = (m == 0) ? V[k][0] : (m == 1 ? V[k][1] : (m == 2 ? V[k][2] : V[k][3]));
+}
+
 __device__ __forceinline__ double det3(const double *M) {
     return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
@@ -222,27 +247,8 @@ __global__ __launch_bounds__(256) void triangulate_kernel(const double *__restri
     if (i < n) {
         const double *Pc = P + c * 12;
         const double x1 = p1[2 * i], y1 = p1[2 * i + 1], x2 = p2[2 * i], y2 = p2[2 * i + 1];
-        double G[4][4], V[4][4];
-        // view 1: P0 = [I|0]
-        const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            G[0][k] = x1 * P0[8 + k] - P0[k];
-            G[1][k] = y1 * P0[8 + k] - P0[4 + k];
-            G[2][k] = x2 * Pc[8 + k] - Pc[k];
-            G[3][k] = y2 * Pc[8 + k] - Pc[4 + k];
-        }
-        jacobi4_right_vectors(G, V);
-        double w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = G[0][j] * G[0][j] + G[1][j] * G[1][j] + G[2][j] * G[2][j] + G[3][j] * G[3][j];
-        int m = 0;
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (w[j] < w[m]) m = j;
         double X[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) X[k] = (m == 0) ? V[k][0] : (m == 1 ? V[k][1] : (m == 2 ? V[k][2] : V[k][3]));
+        dlt_null_vector(Pc, x1, y1, x2, y2, X);
         bool mk = (X[2] * X[3] > 0);
         const double qz = Pc[8] * X[0] + Pc[9] * X[1] + Pc[10] * X[2] + Pc[11] * X[3];
         mk = mk && (qz * X[3] > 0);
@@ -363,26 +369,8 @@ __global__ __launch_bounds__(256) void triangulate_batch_kernel(const double *__
             const int i = todo[wv][at0 + lane];
             const size_t at = ((size_t)b * pair_stride + i) * 2;
             const double x1 = p1[at], y1 = p1[at + 1], x2 = p2[at], y2 = p2[at + 1];
-            double G[4][4], V[4][4];
-            const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                G[0][k] = x1 * P0[8 + k] - P0[k];
-                G[1][k] = y1 * P0[8 + k] - P0[4 + k];
-                G[2][k] = x2 * Pc[8 + k] - Pc[k];
-                G[3][k] = y2 * Pc[8 + k] - Pc[4 + k];
-            }
-            jacobi4_right_vectors(G, V);
-            double w[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w[j] = G[0][j] * G[0][j] + G[1][j] * G[1][j] + G[2][j] * G[2][j] + G[3][j] * G[3][j];
-            int m = 0;
-#pragma unroll
-            for (int j = 1; j < 4; ++j)
-                if (w[j] < w[m]) m = j;
             double X[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) X[k] = (m == 0) ? V[k][0] : (m == 1 ? V[k][1] : (m == 2 ? V[k][2] : V[k][3]));
+            dlt_null_vector(Pc, x1, y1, x2, y2, X);
             bool mk = (X[2] * X[3] > 0);
             const double qz = Pc[8] * X[0] + Pc[9] * X[1] + Pc[10] * X[2] + Pc[11] * X[3];
             mk = mk && (qz * X[3] > 0);
@@ -433,6 +421,64 @@ __global__ __launch_bounds__(256) void select_pose_batch_kernel(const double *__
     }
     for (int i = threadIdx.x; i < n; i += blockDim.x)
         mask[(size_t)b * pair_stride + i] = pick >= 0 ? cand_masks[((size_t)b * 4 + pick) * pair_stride + i] : 0;
+}
+
+// ---- triangulation with a given pose (poselib::triangPts3D, pose_estim.cpp:964-1044) -------------------------------------------------------------
+// One candidate P1 = [R|t] per problem (blockIdx.y), no decomposition and no choice: X by dlt_null_vector, m = ((P1 X).z * X.w > 0) & mask,
+// Q = X.xyz / X.w by division, m &= (Q.z < dist) & (Q.z > 0) -- the comparisons on the QUOTIENT, as the reference makes them (w = 0 gives
+// inf or NaN and every comparison false).  The mask is read and written in place (byte i only by the lane that works on point i).
+// Q requested: every point is triangulated, masked or not, as the reference does.  Q not requested: a point outside the incoming mask stays
+// 0 and gets no SVD; the wave compacts the others as triangulate_batch_kernel does.  The single entries run the same kernel with one problem.
+__global__ __launch_bounds__(256) void triang_pts3d_kernel(const double *__restrict__ P_all /*[B][12]*/, const double *__restrict__ p1,
+                                                           const double *__restrict__ p2, const int32_t *__restrict__ counts, int stride,
+                                                           double dist, uint8_t *mask /*[B][stride] in / out, or NULL*/,
+                                                           double *__restrict__ Q /*[B][stride][3] or NULL*/,
+                                                           int32_t *__restrict__ n_good /*[B], zeroed*/) {
+    __shared__ int todo[4][kTriPointsPerWave];
+    const int b = blockIdx.y;
+    const int n = counts[b];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int base = (blockIdx.x * 4 + wv) * kTriPointsPerWave;
+    if (base >= n) return;  // wave-uniform
+    int total = 0;
+#pragma unroll
+    for (int k = 0; k < kTriPointsPerWave / 64; ++k) {
+        const int i0 = base + k * 64 + lane;
+        const bool want = i0 < n && (Q || !mask || mask[(size_t)b * stride + i0]);
+        const unsigned long long wb = __ballot(want);
+        if (want) todo[wv][total + __popcll(wb & ((1ull << lane) - 1ull))] = i0;
+        total += __popcll(wb);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the list is this wave's own (see triangulate_batch_kernel)
+    __builtin_amdgcn_wave_barrier();
+    const double *Pc = P_all + (size_t)b * 12;
+    int good_cnt = 0;
+    for (int at0 = 0; at0 < total; at0 += 64) {
+        bool good = false;
+        if (at0 + lane < total) {
+            const int i = todo[wv][at0 + lane];
+            const size_t at = (size_t)b * stride + i;
+            const double x1 = p1[at * 2], y1 = p1[at * 2 + 1], x2 = p2[at * 2], y2 = p2[at * 2 + 1];
+            double X[4];
+            dlt_null_vector(Pc, x1, y1, x2, y2, X);
+            const double qz = Pc[8] * X[0] + Pc[9] * X[1] + Pc[10] * X[2] + Pc[11] * X[3];
+            bool mk = (qz * X[3] > 0);
+            const double qx = X[0] / X[3], qy = X[1] / X[3], qzz = X[2] / X[3];
+            mk = mk && (qzz < dist) && (qzz > 0);
+            if (Q) {
+                double *q = Q + at * 3;
+                q[0] = qx, q[1] = qy, q[2] = qzz;
+            }
+            uint8_t mv = mk ? 255 : 0;
+            if (mask) {
+                mv &= mask[at];
+                mask[at] = mv;
+            }
+            good = (mv != 0);
+        }
+        good_cnt += __popcll(__ballot(good));
+    }
+    if (lane == 0 && good_cnt) atomicAdd(&n_good[b], good_cnt);
 }
 
 }  // namespace
@@ -585,4 +631,106 @@ static int recover_pose_impl(mlpl_ctx *ctx, const double *E, const double *t_onl
         }
     }
     return ret;
+}
+
+// ---- mlpl_triang_pts3d* ---------------------------------------------------------------------------------------------------------------------------
+// P1 = [R|t] per problem (host) -> WS_AUX2: [B][12] doubles, counts [B], n_good [B]; one launch for the whole batch; the counts come back.
+static int triang_pts3d_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                            const double *R, const double *t, double dist, uint8_t *d_masks, double *d_Q, int32_t *n_good, hipStream_t s) {
+    if (B < 1 || stride < 1 || !d_p1 || !d_p2 || !counts || !R || !t || !n_good) {
+        set_error("%s: bad arguments", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    int max_n = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > stride) {
+            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
+            return MLPL_E_BAD_INPUT;
+        }
+        max_n = std::max(max_n, counts[b]);
+    }
+    if (B > 65535) {
+        set_error("%s: at most 65535 problems per call", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t off_P = 0, off_counts = (size_t)B * 96, off_good = off_counts + (size_t)B * 4, bytes = off_good + (size_t)B * 4;
+    void *d_small;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX2, bytes, &d_small))) return rc;
+    std::vector<char> h(bytes, 0);
+    double *hP = (double *)(h.data() + off_P);
+    for (int b = 0; b < B; ++b)
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) hP[b * 12 + r * 4 + k] = R[b * 9 + r * 3 + k];
+            hP[b * 12 + r * 4 + 3] = t[b * 3 + r];
+        }
+    std::memcpy(h.data() + off_counts, counts, (size_t)B * 4);
+    MLPL_HIP_TRY(hipMemcpyAsync(d_small, h.data(), bytes, hipMemcpyHostToDevice, s));  // (n_good starts at zero)
+    char *sm = (char *)d_small;
+    if (max_n > 0) {
+        const int per_block = 4 * kTriPointsPerWave;
+        hipLaunchKernelGGL(triang_pts3d_kernel, dim3((max_n + per_block - 1) / per_block, B), dim3(256), 0, s, (const double *)(sm + off_P), d_p1, d_p2,
+                           (const int32_t *)(sm + off_counts), stride, dist, d_masks, d_Q, (int32_t *)(sm + off_good));
+        MLPL_HIP_TRY(hipGetLastError());
+    }
+    MLPL_HIP_TRY(hipMemcpyAsync(n_good, sm + off_good, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipStreamSynchronize(s));
+    return MLPL_OK;
+}
+
+extern "C" int mlpl_triang_pts3d_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride,
+                                           const int32_t *counts, const double *R, const double *t, double dist, uint8_t *d_masks,
+                                           double *d_Q, int32_t *n_good, void *stream) {
+    if (!ctx) {
+        set_error("mlpl_triang_pts3d_batch_dev: ctx is mandatory");
+        return MLPL_E_BAD_INPUT;
+    }
+    return triang_pts3d_run(ctx, "mlpl_triang_pts3d_batch_dev", n_problems, d_p1, d_p2, stride, counts, R, t, dist, d_masks, d_Q, n_good,
+                            pick_stream(ctx, stream));
+}
+
+extern "C" int mlpl_triang_pts3d_dev(mlpl_ctx *ctx, const double R[9], const double t[3], const double *d_p1, const double *d_p2, int n,
+                                     double dist, double *d_Q, uint8_t *d_mask_inout, void *stream) {
+    if (!ctx || n < 0) {
+        set_error("mlpl_triang_pts3d_dev: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    const int32_t count = n;
+    int32_t good = 0;
+    const int rc = triang_pts3d_run(ctx, "mlpl_triang_pts3d_dev", 1, d_p1, d_p2, std::max(n, 1), &count, R, t, dist, d_mask_inout, d_Q, &good,
+                                    pick_stream(ctx, stream));
+    return rc ? rc : good;
+}
+
+extern "C" int mlpl_triang_pts3d(mlpl_ctx *ctx, const double R[9], const double t[3], const double *p1, const double *p2, int n, double dist,
+                                 double *Q, uint8_t *mask_inout) {
+    if (!ctx || !p1 || !p2 || n < 0) {
+        set_error("mlpl_triang_pts3d: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nn = (size_t)std::max(n, 1);
+    void *dp1, *dp2, *dQ = nullptr, *dmask = nullptr;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
+    if (Q && (rc = ws_get(ctx, WS_AUX5, nn * 24, &dQ))) return rc;
+    if (mask_inout && (rc = ws_get(ctx, WS_AUX6, nn, &dmask))) return rc;
+    if (n > 0) {
+        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        if (mask_inout) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask_inout, (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    const int32_t count = n;
+    int32_t good = 0;
+    if ((rc = triang_pts3d_run(ctx, "mlpl_triang_pts3d", 1, (const double *)dp1, (const double *)dp2, (int)nn, &count, R, t, dist, (uint8_t *)dmask,
+                               (double *)dQ, &good, s)))
+        return rc;
+    if (n > 0) {
+        if (Q) MLPL_HIP_TRY(hipMemcpy(Q, dQ, (size_t)n * 24, hipMemcpyDeviceToHost));
+        if (mask_inout) MLPL_HIP_TRY(hipMemcpy(mask_inout, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return good;
 }

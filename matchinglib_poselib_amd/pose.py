@@ -551,6 +551,74 @@ def getPoseTriangPts_device(E, p1, p2, mask=None, dist: float = 50.0, Q_out=None
     return rc, R, t
 
 
+def triangPts3D(R, t, p1, p2, mask=None, dist: float = 50.0, ctx: Optional[Context] = None):
+    """poselib::triangPts3D (pose_estim.h:202, pose_estim.cpp:964-1044): triangulation with the given pose -> (n_good, Q, mask).  Q holds
+    every point (inf / NaN where the homogeneous w is zero); mask is None when none was passed."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    if p2.shape[0] != n:
+        raise ValueError("p1 and p2 differ in length")
+    Rh = np.ascontiguousarray(R, np.float64).reshape(3, 3)
+    th = np.ascontiguousarray(t, np.float64).reshape(3)
+    Q = np.zeros((n, 3))
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1).copy()
+    if m is not None and m.shape[0] != n:
+        raise ValueError("the mask must hold one byte per correspondence")
+    rc = ctx.lib.mlpl_triang_pts3d(ctx.handle, Rh.ctypes.data, th.ctypes.data, p1.ctypes.data, p2.ctypes.data, n, float(dist), Q.ctypes.data,
+                                   None if m is None else m.ctypes.data)
+    if rc < 0:
+        raise MlplError(rc, "mlpl_triang_pts3d", _lib.last_error())
+    return rc, Q, m
+
+
+def triangPts3D_device(R, t, p1, p2, mask=None, dist: float = 50.0, Q_out=None, ctx: Optional[Context] = None, stream: Optional[int] = None):
+    """triangPts3D on device-resident torch tensors (float64 [n,2]; mask uint8 [n] or None, rewritten in place; Q_out float64 [n,3] or
+    None) -> n_good.  Only the count is read back."""
+    import torch
+
+    assert p1.is_cuda and p2.is_cuda and p1.dtype == torch.float64 and p1.shape == p2.shape and p1.is_contiguous() and p2.is_contiguous()
+    n = p1.shape[0]
+    if mask is not None:
+        assert mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (n,) and mask.is_contiguous()
+    if Q_out is not None:
+        assert Q_out.is_cuda and Q_out.dtype == torch.float64 and Q_out.shape == (n, 3) and Q_out.is_contiguous()
+    ctx = ctx or default_context(p1.device.index or 0)
+    Rh = np.ascontiguousarray(R, np.float64).reshape(3, 3)
+    th = np.ascontiguousarray(t, np.float64).reshape(3)
+    st = torch.cuda.current_stream(p1.device).cuda_stream if stream is None else stream
+    rc = ctx.lib.mlpl_triang_pts3d_dev(ctx.handle, Rh.ctypes.data, th.ctypes.data, p1.data_ptr(), p2.data_ptr(), n, float(dist),
+                                       None if Q_out is None else Q_out.data_ptr(), None if mask is None else mask.data_ptr(), st)
+    if rc < 0:
+        raise MlplError(rc, "mlpl_triang_pts3d_dev", _lib.last_error())
+    return rc
+
+
+def triang_pts3d_batch(d_p1, d_p2, counts, R, t, d_masks=None, d_Q=None, dist: float = 50.0, ctx: Optional[Context] = None) -> np.ndarray:
+    """mlpl_triang_pts3d_batch_dev in the layout of recover_pose_batch: R [B, 3, 3], t [B, 3] (host); d_masks (uint8 CUDA tensor [B, stride]
+    or None = all points) is rewritten in place up to counts[b]; d_Q (float64 CUDA tensor [B, stride, 3] or None) receives every point.
+    Returns n_good [B]."""
+    import torch
+
+    B, stride = d_p1.shape[0], d_p1.shape[1]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (B, stride, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    if d_masks is not None:
+        assert d_masks.is_cuda and d_masks.dtype == torch.uint8 and d_masks.shape == (B, stride) and d_masks.is_contiguous()
+    if d_Q is not None:
+        assert d_Q.is_cuda and d_Q.dtype == torch.float64 and d_Q.shape == (B, stride, 3) and d_Q.is_contiguous()
+    ctx = ctx or default_context(d_p1.device.index or 0)
+    cn = np.ascontiguousarray(counts, np.int32).reshape(B)
+    Rh = np.ascontiguousarray(np.asarray(R, np.float64).reshape(B, 9))
+    th = np.ascontiguousarray(np.asarray(t, np.float64).reshape(B, 3))
+    n_good = np.zeros(B, np.int32)
+    rc = ctx.lib.mlpl_triang_pts3d_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, Rh.ctypes.data, th.ctypes.data,
+                                             float(dist), None if d_masks is None else d_masks.data_ptr(), None if d_Q is None else d_Q.data_ptr(),
+                                             n_good.ctypes.data, torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_triang_pts3d_batch_dev", _lib.last_error())
+    return n_good
+
+
 def ImgToCamCoordTrans(points, K, ctx: Optional[Context] = None) -> np.ndarray:
     """poselib::ImgToCamCoordTrans (pose_helper.cpp:1100-1109): float32 n x 2 pixel points -> camera coordinates."""
     ctx = ctx or default_context()

@@ -79,6 +79,10 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *       "hamming_expand_fine" (default 1) = small launches expand the train set with one thread per (tile, K-step, lane).
  *       "hamming_expand_inkernel" 1 = the eight-wave LDS-ring kernel reads the raw 32-byte train rows and expands each tile in its own
  *       workgroup (no expansion launch, no expanded copy of the train set in the workspace); 0 = the separate expansion kernel.
+ *       "hamming_block_top2" 4 (default) | 0 = block size of the running top-2 update of that in-kernel-expansion kernel: 0 folds every
+ *       candidate into a lane's running pair, 4 folds only the maxima of aligned groups of four train rows and re-scores the rows of the one
+ *       group that holds a query's best row from the raw descriptors in the epilogue (same results bit for bit, measured faster; ignored by
+ *       every other kernel, mlpl_debug_last_hamming_top2 reports what ran).
  *   L2: "l2_mfma_waves" 0|4|8 and "l2_mfma_blocks_per_cu" shape the int8 matrix-core kernel of the forced mode (see mlpl_set_l2_path);
  *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0);
  *     "l2_fold_counts" (default 1) = mlpl_match_l2_dev's fold over the train splits evaluates the ratio predicate and writes the pass

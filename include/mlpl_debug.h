@@ -92,6 +92,11 @@ int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, lo
  *   out[12] 1 = the static ring kernel expanded the raw train tiles itself (option "hamming_expand_inkernel"; no expansion launch). */
 int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]);
 
+/* Diagnostics: the block size of the running top-2 update the last knn_hamming call really used (option "hamming_block_top2"): 4 = the
+ * in-kernel-expansion instance of the static ring kernel folded the maxima of blocks of four and re-scored the best row's block in its epilogue,
+ * 0 = the per-candidate update (every other kernel, and every call the option does not apply to). */
+int mlpl_debug_last_hamming_top2(mlpl_ctx *ctx);
+
 /* Diagnostics: what the last float knn / match call of this context (mlpl_knn2_l2sq_f32*, mlpl_match_l2_dev, the float pair entries)
  * chose.  Writes 4 ints and returns 4: out[0] path -- 1 exact fp32 kernel, 2 int8 matrix-core path (forced), 3 the auto path's fused
  * kernel (int8 or exact by the device flag), 4 fp16 candidate path, 0 nothing launched (nq = 0); out[1] train splits the fold reads

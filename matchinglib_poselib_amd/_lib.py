@@ -128,6 +128,7 @@ _SIGNATURES = {
     "mlpl_debug_hamming_clock": (c_int, [c_void_p, c_void_p, c_int]),
     "mlpl_debug_hop_trace": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "mlpl_debug_last_kernels": (c_int, [c_void_p, c_void_p]),
+    "mlpl_debug_last_hamming_top2": (c_int, [c_void_p]),
     "mlpl_debug_count_pass": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_int,
                                       c_void_p]),
     "mlpl_pair_pose_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
@@ -297,6 +298,13 @@ class Context:
         if n < 0:
             raise MlplError(n, "mlpl_debug_last_kernels", last_error())
         return list(out[:n])
+
+    def last_hamming_top2(self) -> int:
+        """mlpl_debug_last_hamming_top2 (include/mlpl_debug.h): block size of the top-2 update the last Hamming launch used (0 = per candidate)."""
+        n = self._lib.mlpl_debug_last_hamming_top2(self._h)
+        if n < 0:
+            raise MlplError(n, "mlpl_debug_last_hamming_top2", last_error())
+        return n
 
     def last_l2_match(self) -> list:
         """mlpl_debug_last_l2_match (include/mlpl_debug.h): {path, train splits, counts by the fold, launches} of the last float match."""

@@ -206,6 +206,23 @@ __device__ __forceinline__ void top2_update4(float &m1, float &m2, float a0, flo
     m2 = __builtin_fmaxf(__builtin_fmaxf(m2, s0), s1);
 }
 
+// The BLOCK form of the update (option hamming_block_top2, the in-kernel-expansion instances of the LDS-ring kernel): only the MAXIMUM of a
+// fixed block of the lane's 16 candidates is folded into the running pair.  m1 is then still the exact maximum of every row the lane has
+// seen, and m2 is at least the maximum of every block but the one that holds m1's row: a candidate missing from m2 can only be a
+// non-maximal member of that one block, which the epilogue re-scores from the raw descriptors (block_rescan).
+// A block = accumulator registers 4 j .. 4 j + 3 = an aligned group of four consecutive train rows: four times max(max3(..), a) and one
+// top2_update4 over the four maxima (spelt out in its order, two maxima at a time), 13 VALU ops against 20.
+__device__ __forceinline__ void top2_update_blocks4(float &m1, float &m2, const v16f &acc) {
+    auto max4 = [&](int j) { return __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(acc[4 * j], acc[4 * j + 1]), acc[4 * j + 2]), acc[4 * j + 3]); };
+    const float g0 = max4(0), g1 = max4(1);
+    const float s0 = __builtin_amdgcn_fmed3f(m1, g0, g1);
+    const float t0 = __builtin_fmaxf(__builtin_fmaxf(m1, g0), g1);
+    const float g2 = max4(2), g3 = max4(3);
+    const float s1 = __builtin_amdgcn_fmed3f(t0, g2, g3);
+    m1 = __builtin_fmaxf(__builtin_fmaxf(t0, g2), g3);
+    m2 = __builtin_fmaxf(__builtin_fmaxf(m2, s0), s1);
+}
+
 // the train tile's row that accumulator register `reg` holds in a lane of half h
 __device__ __forceinline__ int acc_local_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 // C of the first MFMA of every tile: minus the local row of accumulator register `reg` in this lane, times eps
@@ -252,6 +269,35 @@ __device__ __forceinline__ uint2 top2_across_halves(const uint32_t (&k)[2]) {
     k1 = umed3(k0, k1, o1);
     k0 = min(k0, o1);
     return make_uint2(k0, k1);
+}
+
+// Epilogue of the block update (top2_update_blocks4): the exact second of a query.  After top2_across_halves k0 is the
+// query's exact best key; the merged second can only be short of the non-maximal rows of the ONE block that holds the best row (the other
+// lane half's m1 is the exact maximum of its rows).  Those rows are re-scored here from the raw descriptors -- xor + popcount over the eight
+// words, the key (distance << dshift | local row) the decode forms -- and the smallest of them is returned (0xFFFFFFFF: none), in both lanes
+// of the query, for the caller's min() with the merged second.  The block is the aligned group of four rows around the best, 128 contiguous
+// bytes; the two lanes of the query (he = 0, 1) take two rows each.
+// `q8` = the query's eight raw words; `rbase` = the first row of the split (local row 0), `rows` = the image pair's train rows from there on
+// (>= 1).  The best row itself and rows >= `rows` (the ragged last tile) do not count; every address is clamped to the pair's last row, so
+// nothing behind the train set is read, and k0 = 0xFFFFFFFF (no candidate at all) yields none.  Branch-free: every lane of the wave loads.
+struct __attribute__((packed, aligned(4))) RawRow {   // (a train row is word-aligned, not more: the in-kernel expansion asks for no more)
+    uint32_t w[8];
+};
+__device__ __forceinline__ uint32_t block_rescan(uint32_t k0, const uint32_t (&q8)[8], const char *rbase, int rows, int dshift, int he) {
+    const uint32_t lmask = (1u << dshift) - 1u;
+    const int best = (int)(k0 & lmask);
+    uint32_t res = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = (best & ~3) + 2 * he + i;
+        const RawRow t = *reinterpret_cast<const RawRow *>(rbase + (size_t)min(r, rows - 1) * 32);
+        int d = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d += __popc(t.w[j] ^ q8[j]);
+        const uint32_t key = ((uint32_t)d << dshift) | (uint32_t)r;
+        res = (r != best && r < rows && k0 != 0xFFFFFFFFu) ? min(res, key) : res;
+    }
+    return min(res, (uint32_t)__shfl_xor(res, 32));
 }
 
 // XCD-aware work assignment.  Workgroups go round-robin to the 8 XCDs (each with its own L2), so workgroup L runs on XCD L % 8.  The
@@ -461,7 +507,10 @@ struct HammingFuse {
 //     vmcnt(0) waits of the last two iterations, the clamp of the copy -- which can bind in the last tile only, never inside a pair -- and the
 //     stale-slot expansion; the ragged tile follows as before.
 //   * ST (option hamming_stamps = 1) = the instance with the per-tile clock stamp; it keeps the rolled loop throughout.
-template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false, bool ST = false>
+//   * BT (option hamming_block_top2; 0 or 4, non-zero with XP only: the epilogue needs the raw train rows) = the running top-2 folds the maxima
+//     of blocks of four candidates instead of the candidates (top2_update_blocks4: 13 VALU ops per unit against 20) and the epilogue re-scores the
+//     best row's block (block_rescan) before any store, so the partials of a split are its exact top-2 and everything behind them is unchanged.
+template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false, bool ST = false, int BT = 0>
 __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     const uint32_t *__restrict__ qw, size_t q_batch_words, const void *__restrict__ tsrc, size_t t_batch, int nq, int nt,
     int rows_per_split, int nsplit, int dshift, int qblocks, int n_items, uint2 *__restrict__ part,
@@ -469,6 +518,7 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     constexpr int KS = 4, NB = XP ? 2 : PD == 2 ? 4 : 8, NR = 4;
     static_assert(PD == 2 || PD == 4 || PD == 6, "prefetch distance");
     static_assert(!XP || (NW == 8 && PD == 2), "the in-kernel expansion exists for eight waves and a prefetch distance of 2");
+    static_assert(BT == 0 || (XP && PRIO == 0 && BT == 4), "the block update needs the raw train rows of the in-kernel expansion");
     __shared__ __attribute__((aligned(16))) uint4 ring[NB][KS * 64];
     __shared__ __attribute__((aligned(16))) uint32_t raw_ring[XP ? NR * 256 : 1];   // (unused, hence not allocated, without XP)
     const int l = threadIdx.x & 63;
@@ -556,6 +606,13 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
             for (int s = 1; s < KS; ++s) acc = mfma_fp4(a[s], bq[t][s], acc);
             m1[t] += 32.0f * kEps;
             m2[t] += 32.0f * kEps;
+            if constexpr (BT == 4) {
+                top2_update_blocks4(m1[t], m2[t], acc);
+                // (one accumulator tile alive at a time, as in the dynamic kernel below: without this tie the instance takes 128 registers and
+                // 16 bytes of scratch around the loops; with it 126 and none, in the same order of MFMAs and updates)
+                asm volatile("" : "+v"(m1[t]), "+v"(m2[t]), "+v"(a[0].x));
+                continue;
+            }
 #pragma unroll
             for (int reg = 0; reg < 16; reg += 4) {
                 if constexpr (PRIO == 3) {
@@ -785,8 +842,20 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         for (int j = 0; j < 2; ++j)  // (-inf: no candidate)
             k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key(mm[j], frame, dshift, DistRule{64 * KS, fuse.train01, qpop});
         const uint2 kk = top2_across_halves(k);
-        const uint32_t k0 = kk.x, k1 = kk.y;
         const int q = (qt0e + t) * 32 + (le & 31);
+        const uint32_t k0 = kk.x;
+        uint32_t k1 = kk.y;
+        if constexpr (BT != 0) {
+            if (fuse.k != 1) {   // (one neighbour: m1 is exact as it is)
+                uint32_t q8[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+                if (q < nq) {
+                    const uint4 *qp = reinterpret_cast<const uint4 *>(qw + (size_t)b * q_batch_words + (size_t)q * (2 * KS));
+                    const uint4 v0 = qp[0], v1 = qp[1];
+                    q8[0] = v0.x, q8[1] = v0.y, q8[2] = v0.z, q8[3] = v0.w, q8[4] = v1.x, q8[5] = v1.y, q8[6] = v1.z, q8[7] = v1.w;
+                }
+                k1 = min(k1, block_rescan(k0, q8, rbase, nt - row0, dshift, he));
+            }
+        }
         if (fuse.idx && nsplit == 1) {  // the final top-2 of the query: outputs straight from the registers
             const uint32_t lmask = (1u << dshift) - 1u;
             bool pass = false;
@@ -1074,9 +1143,9 @@ struct RingLaunch {
     const int32_t *split_tab;
     HammingFuse fuse;
 };
-template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false, bool ST = false>
+template <int QT, int PRIO, int NW = 4, int PD = 2, bool XP = false, bool ST = false, int BT = 0>
 void launch_ring(const RingLaunch &a) {
-    hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT, PRIO, NW, PD, XP, ST>), a.grid, dim3(64 * NW), 0, a.s, a.qw, a.q_batch_words, a.tsrc,
+    hipLaunchKernelGGL((knn_hamming_mfma_lds_kernel<QT, PRIO, NW, PD, XP, ST, BT>), a.grid, dim3(64 * NW), 0, a.s, a.qw, a.q_batch_words, a.tsrc,
                        a.t_batch, a.nq, a.nt, a.rps, a.nsplit, a.dshift, a.qblocks, a.n_items, a.part, a.stamps, a.split_tab, a.fuse);
 }
 
@@ -1205,6 +1274,10 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     const bool inkernel = ctx->opt_hamming_expand_inkernel && lds_ring && !dyn && nwv == 8 && pd == 2 && prio == 0 && nw == 8 && !train01 &&
                           ((uintptr_t)tw & 3u) == 0;
 
+    // block size of the running top-2 update (option hamming_block_top2): the instances that have the raw train rows
+    const int block_top2 = inkernel ? ctx->opt_hamming_block_top2 : 0;
+    ctx->dbg_hamming_top2 = block_top2;
+
     void *qf = nullptr, *tf = nullptr, *part = nullptr;
     int rc;
     const size_t q_u4 = (size_t)q_tiles_padded * ks * 64, t_u4 = (size_t)t_tiles * ks * 64;
@@ -1308,8 +1381,10 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     } else if (lds_ring) {
         const RingLaunch ra{grid, s, qw, q_batch_words, inkernel ? (const void *)tw : (const void *)tf, inkernel ? t_batch_words : t_u4, nq, nt, rps, nsplit,
                             dshift, qblocks, (int)items, (uint2 *)part, stamps, split_tab, fuse};
-        if (inkernel && stamps) launch_ring<4, 0, 8, 2, true, true>(ra);   // (hamming_stamps = 1: the rolled loop with the per-tile clock trace)
-        else if (inkernel) launch_ring<4, 0, 8, 2, true>(ra);
+        if (inkernel && stamps)   // (hamming_stamps = 1: the rolled loop with the per-tile clock trace)
+            block_top2 == 4 ? launch_ring<4, 0, 8, 2, true, true, 4>(ra) : launch_ring<4, 0, 8, 2, true, true>(ra);
+        else if (inkernel)
+            block_top2 == 4 ? launch_ring<4, 0, 8, 2, true, false, 4>(ra) : launch_ring<4, 0, 8, 2, true>(ra);
         else if (nwv == 16) launch_ring<4, 0, 16>(ra);
         else if (nwv == 8 && pd == 4) launch_ring<4, 0, 8, 4>(ra);
         else if (nwv == 8 && pd == 6) launch_ring<4, 0, 8, 6>(ra);

@@ -138,6 +138,8 @@ struct mlpl_ctx {
     int opt_hamming_train01;        // 1 = {0, +1} train fragments in the static LDS-ring kernel (accumulator = pop(query) - distance), 0 = +-1
     int opt_vfc_store_u;            // 1 = the VFC kernel keeps the m x n kernel matrix U in the workspace; 0 (default, unmeasured: DESIGN section 8) = it recomputes U in both passes of an iteration
     int opt_hamming_expand_inkernel;   // 1 = the static LDS-ring kernel's throughput instance expands the raw train tiles itself (no expansion launch, no WS_FRAG_T)
+    int opt_hamming_block_top2;        // 0 = the ring kernel folds every candidate into its running top-2; 4 = the in-kernel-expansion instances fold the maxima of blocks of four candidates and re-score the best row's block in the epilogue (same results)
+    int dbg_hamming_top2;              // block size the last Hamming launch really used (mlpl_debug_last_hamming_top2)
     void *subpix_sep_mask_ptr;      // the WS_SUBPIX_SEP_MASK block that holds the mask profiles of subpix_separate.hip
     int dbg_stamp_items;
     // diagnostics (mlpl_debug_last_kernels): what the last launches chose -- {count instance code, its point splits} of the last

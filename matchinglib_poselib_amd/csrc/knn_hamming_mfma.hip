@@ -45,6 +45,20 @@ constexpr float kEps = 1.0f / 16384.0f;  // 2^-14: row weight in the accumulator
 // (-1/2, 1/2) -- rint() recovers I -- and a multiple of 2^-14 below 512 is exact in fp32.  (Up to round 4 the cap was 4096, which cut every
 // 8192-row train set of a full batch in two although the chip was already full: partials, tickets and a fold for nothing.)
 constexpr int kMaxRowsPerSplit = 8192;
+// Accumulator bias of the in-kernel-expansion instances of the LDS-ring kernel (XP): their chains start at kAccBias - row * 2^-14 instead of
+// -row * 2^-14, so a value is kAccBias + I - (row - frame) * 2^-14.  Around zero a random pair's I = 0 +- 16 flips the float's sign and moves
+// its exponent from one register write to the next, which re-aligns the whole mantissa, the constant row fraction included; with the bias
+// every typical value stays inside the binade [512, 1024): sign and exponent never change, the fraction keeps its 14 low mantissa bits and
+// only the integer part's 7-9 bits move -- fewer bits switching per MFMA in a launch whose clock is power-limited.  Same
+// instruction stream; the decode removes the bias before a key is formed, so every byte that leaves the kernel is what it was.
+// Exactness: every value, final or partial sum of a chain, is kAccBias + I + f * 2^-14 with |I| <= 256 (KS = 4: 256 bits) and f in
+// [-31, kMaxRowsPerSplit - 32]; it must be a multiple of 2^-14 of magnitude below 1024 (24-bit significand), and its fraction stays inside
+// (-1/2, 1/2) as before, so rint() returns kAccBias + I.  tests/test_hamming_acc_bias_rule.py restates this over every (I, f).
+constexpr float kAccBias = 704.0f;
+static_assert(kAccBias == (float)(int)kAccBias, "the bias is an integer: rint() of a value is kAccBias + I");
+static_assert(kAccBias + 256.0f + (float)(kMaxRowsPerSplit - 32) / 16384.0f < 1024.0f, "largest value (identical rows, last tile) below 2^10: 2^-14 is exact");
+static_assert(kAccBias - 256.0f - 31.0f / 16384.0f > -1024.0f, "smallest value (complementary rows) above -2^10");
+static_assert(kAccBias - 64.0f >= 512.0f && kAccBias + 64.0f < 1024.0f, "typical data (|I| <= 64) stay inside the binade [512, 1024)");
 
 __device__ __forceinline__ float fmax_raw(float a, float b) {
     float r;
@@ -258,6 +272,13 @@ __device__ __forceinline__ uint32_t decode_key(float v, float frame, int dshift,
     const float ip = rintf(v);
     const int d = dist((int)ip);
     const int lrow = (int)(frame - (v - ip) * 16384.0f);
+    return ((uint32_t)d << dshift) | (uint32_t)lrow;
+}
+// the same for a value of a chain that started at kAccBias: rint() returns kAccBias + ip; the fraction is read as above
+__device__ __forceinline__ uint32_t decode_key_biased(float v, float frame, int dshift, DistRule dist) {
+    const float ipb = rintf(v);
+    const int d = dist((int)(ipb - kAccBias));
+    const int lrow = (int)(frame - (v - ipb) * 16384.0f);
     return ((uint32_t)d << dshift) | (uint32_t)lrow;
 }
 // the two lane halves hold disjoint rows of the same query: top-2 of the four keys, in both halves
@@ -535,9 +556,13 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
 
     uint4 bq[QT][KS];   // the wave's query fragments (filled below, behind the first tile copies)
     // (row_weights(h) spelt out: through the helper the scalar prologue of twelve of the fourteen instances comes out in another order)
+    // (XP: every chain starts at kAccBias, see the constant)
     v16f cinit;
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) cinit[reg] = -(float)acc_local_row(reg, h) * kEps;
+    for (int reg = 0; reg < 16; ++reg) {
+        if constexpr (XP) cinit[reg] = kAccBias - (float)acc_local_row(reg, h) * kEps;
+        else cinit[reg] = -(float)acc_local_row(reg, h) * kEps;
+    }
 
     // split geometry: equal splits, or the age-aware table of the launcher (tiles [tab[s], tab[s + 1]) per image pair)
     int row0 = split * rows_per_split;
@@ -813,7 +838,15 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
     }
     if (ragged) {
         arrive(nfull);
-        cinit = row_weights_ragged(h_end, row0 + nfull * 32, nt);
+        if constexpr (XP) {   // (row_weights_ragged with the bias; rows >= nt still start at -inf and stay there)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int lr = acc_local_row(reg, h_end);
+                cinit[reg] = (row0 + nfull * 32 + lr < nt) ? kAccBias - (float)lr * kEps : -INFINITY;
+            }
+        } else {
+            cinit = row_weights_ragged(h_end, row0 + nfull * 32, nt);
+        }
         tile_body(nfull, cinit);
     }
 
@@ -839,8 +872,11 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
         uint32_t k[2];
         const float mm[2] = {m1[t], m2[t]};
 #pragma unroll
-        for (int j = 0; j < 2; ++j)  // (-inf: no candidate)
-            k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key(mm[j], frame, dshift, DistRule{64 * KS, fuse.train01, qpop});
+        for (int j = 0; j < 2; ++j) {  // (-inf: no candidate)
+            const DistRule rule{64 * KS, fuse.train01, qpop};
+            if constexpr (XP) k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key_biased(mm[j], frame, dshift, rule);
+            else k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key(mm[j], frame, dshift, rule);
+        }
         const uint2 kk = top2_across_halves(k);
         const int q = (qt0e + t) * 32 + (le & 31);
         const uint32_t k0 = kk.x;

@@ -83,6 +83,10 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
  *       candidate into a lane's running pair, 4 folds only the maxima of aligned groups of four train rows and re-scores the rows of the one
  *       group that holds a query's best row from the raw descriptors in the epilogue (same results bit for bit, measured faster; ignored by
  *       every other kernel, mlpl_debug_last_hamming_top2 reports what ran).
+ *       "hamming_mfma_shape" 32 | 16 = matrix-core instruction of that kernel with the block update of four (and without the stamps trace of
+ *       "hamming_stamps" 1): v_mfma_f32_32x32x64_f8f6f4, or v_mfma_f32_16x16x128_f8f6f4 with two chains of two per 16 queries and one
+ *       re-base of the running pairs per two tiles (same results bit for bit; ignored by every other kernel,
+ *       mlpl_debug_last_hamming_shape reports what ran).
  *   L2: "l2_mfma_waves" 0|4|8 and "l2_mfma_blocks_per_cu" shape the int8 matrix-core kernel of the forced mode (see mlpl_set_l2_path);
  *     "l2_float_mfma" 0|1|2 decides when the fp16 candidate path serves non-integer float descriptors (mlpl_set_l2_path, mode 0);
  *     "l2_fold_counts" (default 1) = mlpl_match_l2_dev's fold over the train splits evaluates the ratio predicate and writes the pass

@@ -97,6 +97,11 @@ int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]);
  * 0 = the per-candidate update (every other kernel, and every call the option does not apply to). */
 int mlpl_debug_last_hamming_top2(mlpl_ctx *ctx);
 
+/* Diagnostics: the matrix-core shape the last knn_hamming call really used (option "hamming_mfma_shape"): 16 = the 16x16x128 form of the
+ * throughput instance of the static ring kernel, 32 = every other matrix-core kernel (and every call the option does not apply to), 0 = a
+ * VALU kernel. */
+int mlpl_debug_last_hamming_shape(mlpl_ctx *ctx);
+
 /* Diagnostics: what the last float knn / match call of this context (mlpl_knn2_l2sq_f32*, mlpl_match_l2_dev, the float pair entries)
  * chose.  Writes 4 ints and returns 4: out[0] path -- 1 exact fp32 kernel, 2 int8 matrix-core path (forced), 3 the auto path's fused
  * kernel (int8 or exact by the device flag), 4 fp16 candidate path, 0 nothing launched (nq = 0); out[1] train splits the fold reads

@@ -129,6 +129,7 @@ _SIGNATURES = {
     "mlpl_debug_hop_trace": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "mlpl_debug_last_kernels": (c_int, [c_void_p, c_void_p]),
     "mlpl_debug_last_hamming_top2": (c_int, [c_void_p]),
+    "mlpl_debug_last_hamming_shape": (c_int, [c_void_p]),
     "mlpl_debug_count_pass": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_int,
                                       c_void_p]),
     "mlpl_pair_pose_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
@@ -304,6 +305,13 @@ class Context:
         n = self._lib.mlpl_debug_last_hamming_top2(self._h)
         if n < 0:
             raise MlplError(n, "mlpl_debug_last_hamming_top2", last_error())
+        return n
+
+    def last_hamming_shape(self) -> int:
+        """mlpl_debug_last_hamming_shape (include/mlpl_debug.h): matrix-core shape of the last Hamming launch (16 | 32; 0 = a VALU kernel)."""
+        n = self._lib.mlpl_debug_last_hamming_shape(self._h)
+        if n < 0:
+            raise MlplError(n, "mlpl_debug_last_hamming_shape", last_error())
         return n
 
     def last_l2_match(self) -> list:

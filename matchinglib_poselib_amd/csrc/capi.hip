@@ -141,6 +141,7 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
     ctx->opt_hamming_expand_fine = 1;
     ctx->opt_hamming_expand_inkernel = 1;  // measured (tools/hamming_opt_ab.py, profiles/README.md): the step loses the expansion pass, the ring kernel gains less
     ctx->opt_hamming_block_top2 = 4;   // measured (tools/hamming_opt_ab.py, profiles/README.md): the step of 64 C2 pairs loses 15-27 us of 366-380
+    ctx->opt_hamming_mfma_shape = 16;   // (16 = the 16x16x128 form of the throughput instance: DESIGN 4.1 for the measurement behind the default)
     ctx->opt_hamming_merge_emit = 0;  // measured (tools/single_pair_probe.py): the launch it saves is what the chained look-back costs -- 21.2-22.2 against 20.8-21.4 us
     ctx->opt_ransac_lazy_sums = 1;
     ctx->opt_ransac_overlap = 1;
@@ -230,6 +231,7 @@ static const struct {
     {"l2_fold_counts", &mlpl_ctx::opt_l2_fold_counts, 0, 1},
     {"hamming_expand_inkernel", &mlpl_ctx::opt_hamming_expand_inkernel, 0, 1},
     {"hamming_block_top2", &mlpl_ctx::opt_hamming_block_top2, 0, 4},   // (0 or 4: checked below)
+    {"hamming_mfma_shape", &mlpl_ctx::opt_hamming_mfma_shape, 16, 32},   // (16 or 32: checked below)
     {"vfc_store_u", &mlpl_ctx::opt_vfc_store_u, 0, 1},
 };
 
@@ -238,7 +240,8 @@ int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
     for (const auto &o : kRangeOptions)
         if (!std::strcmp(name, o.name)) {
             const bool bad_block = o.field == &mlpl_ctx::opt_hamming_block_top2 && value != 0 && value != 4;
-            if (value < o.lo || value > o.hi || bad_block) {
+            const bool bad_shape = o.field == &mlpl_ctx::opt_hamming_mfma_shape && value != 16 && value != 32;
+            if (value < o.lo || value > o.hi || bad_block || bad_shape) {
                 set_error("mlpl_set_option: unknown option or bad value: %s=%d", name, value);
                 return MLPL_E_BAD_INPUT;
             }
@@ -377,6 +380,7 @@ int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]) {
 }
 
 int mlpl_debug_last_hamming_top2(mlpl_ctx *ctx) { return ctx ? ctx->dbg_hamming_top2 : MLPL_E_BAD_INPUT; }
+int mlpl_debug_last_hamming_shape(mlpl_ctx *ctx) { return ctx ? ctx->dbg_hamming_shape : MLPL_E_BAD_INPUT; }
 
 int mlpl_debug_last_l2_match(mlpl_ctx *ctx, int out[4]) {
     if (!ctx || !out) return MLPL_E_BAD_INPUT;

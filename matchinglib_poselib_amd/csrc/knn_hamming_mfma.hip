@@ -988,6 +988,418 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The throughput instance of the LDS-ring kernel (<4, 0, 8, 2, true, false, 4>: eight waves, 128 queries per wave, in-kernel expansion, block
+// update of four) on v_mfma_f32_16x16x128_f8f6f4 instead of 32x32x64 (option hamming_mfma_shape = 16).  Work-item mapping, raw ring, LDS-DMA
+// copies, barrier protocol, the unrolled pairs with a rolled tail, HammingFuse, tickets, partial table and clock record are those of the
+// kernel above; what differs is the tile arithmetic, where a fragment's lanes sit and the epilogue's lane bookkeeping.
+//   * Operands: only the symmetric structure of the opcode is used -- for A and B alike lane l holds row / column l & 15 and the 32
+//     K-elements of lane group g = l >> 4; D puts column l & 15, rows 4 g + 0..3 into a lane's four registers.  K-half kh covers descriptor
+//     words 4 kh .. 4 kh + 3, lane group g takes word 4 kh + g, and a lane's four operand registers are that word's planes 0, 2, 1, 3 (the
+//     rule of expand_plane, in both operands).
+//   * Fragment ring: same size, and the four ds_read_b128 of a tile keep their addresses; fragment s = 2 rh + kh now holds rows 16 rh + 0..15
+//     (row half rh) of K-half kh.  Expansion wave w (word w: kh = w >> 2, g = w & 3) still reads row l >> 1 and forms the plane pair l & 1; it
+//     writes two contiguous 256-byte runs (rh = 0, 1) instead of one of 512.
+//   * Queries: group u = 0..7 of a wave is queries 32 qt0 + 16 u + (l & 15); bq[u][kh] = the planes of word 4 kh + g.  64 registers as above.
+//   * Tile arithmetic per group: two chains of two (one per row half) on 4-register accumulators, interleaved; a lane's four registers of
+//     chain rh are rows 16 rh + 4 g + 0..3 = one aligned block of four of the block rule, so g_rh = max4(c_rh), s = med3(m1, g0, g1),
+//     m1 = max3(m1, g0, g1), m2 = max(m2, s): 7 ops per group, one (c0, c1) pair alive at a time.
+//   * Period of two tiles: the unrolled pair re-bases the running pair ONCE, by 64 eps in front of its first tile, and the chains of its
+//     two tiles start 32 eps apart (cinit[0] = kAccBias + (32 - lr) eps, cinit[1] = kAccBias - lr eps): every value then reads
+//     kAccBias + I + (frame - row) eps with frame = the first row of the pair's SECOND tile, which is what the decode expects.  The rolled tail
+//     re-bases by 32 eps per tile and uses cinit[1].  Fractions and magnitudes are those of the kernel above (static_asserts at kAccBias).
+//   * Epilogue: a query's keys sit in four lanes (l & 15 equal): top-2 across xor 16 and xor 32; the best row's block is re-scored with one
+//     row per lane; lanes of group 0 write; a group of 64 queries = four groups u.
+// The MFMAs of a group are written out (the compiler's scheduler puts a chain's two dependent MFMAs back to back); s_nop 7 is the wait the
+// compiler itself inserts between this opcode and a VALU read of its result.  The fold keeps the running pair tied to its registers: left
+// to the compiler the pair's two folds merge into a v_max3 over both tiles and the re-base adds into v_pk_add_f32 over neighbouring groups,
+// and the copies that needs do not fit in 128 registers (tools/hamming_unit_probe6.hip).
+// ---------------------------------------------------------------------------------------------------------------------------------
+typedef float v4f __attribute__((ext_vector_type(4)));
+static_assert(kAccBias + 256.0f + 32.0f / 16384.0f < 1024.0f, "a chain of a pair's first tile starts 32 eps higher: still below 2^10");
+
+// The fused merge of the kernel above (HammingFuse with nsplit > 1: its text, as a function), called by every thread of a workgroup behind
+// its partial stores.  QPB = the queries of a workgroup's block, THREADS = its threads; tid_end = the thread's index, le = its lane.
+template <int QPB, int THREADS>
+__device__ __forceinline__ void fold_splits_by_ticket(const HammingFuse &fuse, uint2 *__restrict__ part, const int32_t *__restrict__ split_tile0, int b, int qb,
+                                                      int qblocks, int nsplit, int rows_per_split, int nq, int dshift, unsigned tid_end, int le) {
+        // The last workgroup of this (pair, query block) folds the splits.  No fences: an agent-scope release / acquire pair writes back
+    // and INVALIDATES the XCD's L2 -- with a workgroup finishing every few microseconds the train fragments the other workgroups
+    // stream would never stay cached (measured: 431 -> 633 us per 64-pair launch).  Instead the partials themselves are relaxed
+    // agent-scope atomics (written through / read from the coherence point), every wave waits for its own stores to be acknowledged
+    // (vmcnt(0)) before the workgroup's barrier, and only then does thread 0 draw the ticket.
+    __shared__ int s_last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid_end == 0) {
+        const int old = __hip_atomic_fetch_add(&fuse.tickets[(size_t)b * qblocks + qb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = old == nsplit - 1;
+        if (s_last) __hip_atomic_store(&fuse.tickets[(size_t)b * qblocks + qb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (s_last) {
+        const uint32_t lmask = (1u << dshift) - 1u;
+        const int q_first = qb * QPB;
+#pragma unroll 1
+        for (int rr = 0; rr * THREADS < QPB; ++rr) {  // (QT = 1: the first half of the threads)
+            const int ql = rr * THREADS + (int)tid_end;
+            const int q = ql < QPB ? q_first + ql : nq;
+            unsigned long long b0 = ~0ull, b1 = ~0ull;
+            auto upd = [&](unsigned long long g) {
+                const bool lt0 = g < b0, lt1 = g < b1;
+                b1 = lt0 ? b0 : (lt1 ? g : b1);
+                b0 = lt0 ? g : b0;
+            };
+            bool pass = false;
+            if (q < nq) {
+                for (int sp = 0; sp < nsplit; ++sp) {
+                    const unsigned long long pw = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(&part[((size_t)b * nsplit + sp) * nq + q]),
+                                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint2 pv = make_uint2((uint32_t)pw, (uint32_t)(pw >> 32));
+                    const unsigned long long base = split_tile0 ? 32ull * (unsigned long long)split_tile0[(size_t)b * (nsplit + 1) + sp]
+                                                                : (unsigned long long)sp * rows_per_split;
+                    if (pv.x != 0xFFFFFFFFu) upd(((unsigned long long)(pv.x >> dshift) << 32) | (base + (pv.x & lmask)));
+                    if (pv.y != 0xFFFFFFFFu) upd(((unsigned long long)(pv.y >> dshift) << 32) | (base + (pv.y & lmask)));
+                }
+                const size_t o = ((size_t)b * nq + q) * fuse.k;
+                const int d0 = (int32_t)(b0 >> 32);
+                fuse.idx[o] = (int32_t)(b0 & 0xFFFFFFFFull);
+                fuse.dist[o] = d0;
+                if (fuse.k == 2) {
+                    const int d1 = (int32_t)(b1 >> 32);
+                    fuse.idx[o + 1] = (int32_t)(b1 & 0xFFFFFFFFull);
+                    fuse.dist[o + 1] = d1;
+                    pass = (float)d0 < __fmul_rn(fuse.ratio, (float)d1);
+                } else {
+                    pass = true;
+                }
+            }
+            const int c = __popcll(__ballot(pass));
+            const int q_wave = q_first + rr * THREADS + (int)(tid_end & ~63u);   // first query of this wave's 64
+            if (fuse.group_counts && le == 0 && q_wave < nq && rr * THREADS + (int)(tid_end & ~63u) < QPB) fuse.group_counts[(size_t)b * ((nq + 63) >> 6) + (q_wave >> 6)] = c;
+        }
+    }
+}
+
+__device__ __forceinline__ void mfma16_group(const u32x4 (&a)[4], const u32x4 &q0, const u32x4 &q1, const v4f &ci0, const v4f &ci1, v4f &c0, v4f &c1) {
+    asm volatile("v_mfma_f32_16x16x128_f8f6f4 %0, %2, %6, %8 cbsz:4 blgp:4\n\t"
+                 "v_mfma_f32_16x16x128_f8f6f4 %1, %4, %6, %9 cbsz:4 blgp:4\n\t"
+                 "v_mfma_f32_16x16x128_f8f6f4 %0, %3, %7, %0 cbsz:4 blgp:4\n\t"
+                 "v_mfma_f32_16x16x128_f8f6f4 %1, %5, %7, %1 cbsz:4 blgp:4\n\t"
+                 "s_nop 7"
+                 : "=&v"(c0), "=&v"(c1)
+                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(q0), "v"(q1), "v"(ci0), "v"(ci1));
+}
+// the block maxima of a group's two row halves folded into its running pair, re-based by `step` first (REBASE)
+template <bool REBASE>
+__device__ __forceinline__ void top2_update_halves(float &m1, float &m2, const v4f &c0, const v4f &c1, float step) {
+    const float g0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(c0[0], c0[1]), c0[2]), c0[3]);
+    const float g1 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(c1[0], c1[1]), c1[2]), c1[3]);
+    float sec;
+    if constexpr (REBASE)
+        asm volatile("v_add_f32 %0, %5, %0\n\tv_add_f32 %1, %5, %1\n\tv_med3_f32 %2, %0, %3, %4\n\tv_max3_f32 %0, %0, %3, %4\n\tv_max_f32 %1, %1, %2"
+                     : "+v"(m1), "+v"(m2), "=&v"(sec) : "v"(g0), "v"(g1), "s"(step));
+    else
+        asm volatile("v_med3_f32 %2, %0, %3, %4\n\tv_max3_f32 %0, %0, %3, %4\n\tv_max_f32 %1, %1, %2" : "+v"(m1), "+v"(m2), "=&v"(sec) : "v"(g0), "v"(g1));
+}
+// a query's keys sit in the four lanes with equal l & 15 (disjoint rows): top-2 of the eight keys, in all four lanes
+__device__ __forceinline__ uint2 top2_across_groups(const uint32_t (&k)[2]) {
+    uint32_t k0 = k[0], k1 = k[1];
+#pragma unroll
+    for (int x = 16; x <= 32; x <<= 1) {
+        const uint32_t o0 = __shfl_xor(k0, x), o1 = __shfl_xor(k1, x);
+        k1 = umed3(k0, k1, o0);
+        k0 = min(k0, o0);
+        k1 = umed3(k0, k1, o1);
+        k0 = min(k0, o1);
+    }
+    return make_uint2(k0, k1);
+}
+// block_rescan with the four lanes of a query taking one row each (g = the lane's group)
+__device__ __forceinline__ uint32_t block_rescan4(uint32_t k0, const uint32_t (&q8)[8], const char *rbase, int rows, int dshift, int g) {
+    const uint32_t lmask = (1u << dshift) - 1u;
+    const int best = (int)(k0 & lmask);
+    const int r = (best & ~3) + g;
+    const RawRow t = *reinterpret_cast<const RawRow *>(rbase + (size_t)min(r, rows - 1) * 32);
+    int d = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d += __popc(t.w[j] ^ q8[j]);
+    const uint32_t key = ((uint32_t)d << dshift) | (uint32_t)r;
+    uint32_t res = (r != best && r < rows && k0 != 0xFFFFFFFFu) ? key : 0xFFFFFFFFu;
+    res = min(res, (uint32_t)__shfl_xor(res, 16));
+    return min(res, (uint32_t)__shfl_xor(res, 32));
+}
+
+__global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
+    const uint32_t *__restrict__ qw, size_t q_batch_words, const void *__restrict__ tsrc, size_t t_batch, int nq, int nt,
+    int rows_per_split, int nsplit, int dshift, int qblocks, int n_items, uint2 *__restrict__ part,
+    unsigned long long *__restrict__ stamps, const int32_t *__restrict__ split_tile0, HammingFuse fuse) {
+    constexpr int QT = 4, NG = 2 * QT, NW = 8, PD = 2, KS = 4, NR = 4;
+    __shared__ __attribute__((aligned(16))) uint4 ring[2][KS * 64];
+    __shared__ __attribute__((aligned(16))) uint32_t raw_ring[NR * 256];
+    const int l = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    unsigned long long st_c = 0, st_r = 0;
+    clock_start(stamps || fuse.clk, st_c, st_r);
+    const int item = xcd_block_item();
+    if (item >= n_items) return;  // workgroup-uniform: no wave of this workgroup reaches a barrier
+    const int qb = item % qblocks;
+    const int split = (item / qblocks) % nsplit;
+    const int b = item / (qblocks * nsplit);
+    const int qt0 = (qb * NW + w) * QT;
+
+    u32x4 bq[NG][2];   // the wave's query fragments (filled below, behind the first tile copies)
+    v4f cinit[2][2];   // [tile of a pair][row half]
+#pragma unroll
+    for (int J = 0; J < 2; ++J)
+#pragma unroll
+        for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cinit[J][rh][i] = kAccBias + (float)((J == 0 ? 32 : 0) - (16 * rh + 4 * (l >> 4) + i)) * kEps;
+
+    int row0 = split * rows_per_split;
+    int row1 = min(nt, row0 + rows_per_split);
+    if (split_tile0) {
+        row0 = 32 * split_tile0[(size_t)b * (nsplit + 1) + split];
+        row1 = min(nt, 32 * split_tile0[(size_t)b * (nsplit + 1) + split + 1]);
+    }
+    const int tile0 = row0 >> 5;
+    const int ntiles = (row1 - row0 + 31) >> 5;
+
+    float m1[NG], m2[NG];
+#pragma unroll
+    for (int u = 0; u < NG; ++u) m1[u] = m2[u] = -INFINITY;
+
+    const char *rbase = (const char *)tsrc + ((size_t)b * t_batch + (size_t)tile0 * 32 * (2 * KS)) * 4;   // wave-uniform
+    const uint32_t raw_last = (uint32_t)(nt - row0) * (8u * KS) - 4u;   // byte offset of the pair's last train word behind rbase
+    // the lane parts of every address of the tile loop, formed once (see the kernel above)
+    // (the plane shift l & 1 is bit 3 of xp_plane: with a register of its own the loop takes one more than there are)
+    uint32_t xp_frag, xp_raw, xp_plane, xp_voff;
+    int xp_it0 = 0;
+    auto copy_tile = [&](int t_rel) {
+        if (w >= KS) return;  // (wave-uniform: the raw tile is copied by the first KS waves, a quarter each)
+        const uint32_t off = min(xp_voff + (uint32_t)(t_rel - PD - xp_it0) * 1024u, raw_last);
+        __builtin_amdgcn_global_load_lds((const void *)(rbase + off),
+                                         (__attribute__((address_space(3))) void *)&raw_ring[((t_rel + NR - 1) & (NR - 1)) * 256 + w * 64], 4, 0, 0);
+    };
+    const uint32_t raw_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&raw_ring[0];
+    const uint32_t frag_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)&ring[0][0];
+    {
+        const uint32_t lx = (uint32_t)l;
+        xp_frag = frag_lds + lx * 16u;
+        xp_raw = raw_lds + (uint32_t)w * 4u + (lx >> 1) * 32u;
+        // row l >> 1 of word w -> fragment 2 (row >> 4) + (w >> 2), lane 16 (w & 3) + (row & 15), plane pair l & 1
+        xp_plane = frag_lds + (lx >> 5) * 2048u + (uint32_t)(w >> 2) * 1024u + (uint32_t)(w & 3) * 256u + (lx & 31u) * 8u;
+        xp_voff = PD * 1024u + (uint32_t)w * 256u + lx * 4u;
+        asm volatile("" : "+v"(xp_frag), "+v"(xp_raw), "+v"(xp_plane), "+v"(xp_voff));
+    }
+    auto raw_addr = [&](int t_rel) { return xp_raw + (uint32_t)((t_rel + NR - 1) & (NR - 1)) * 1024u; };   // (raw tile t in slot (t + 3) & 3)
+    auto plane_addr = [&](int t_rel) { return xp_plane + (uint32_t)(t_rel & 1) * (KS * 1024u); };
+    auto expand_pair = [&](uint32_t x) {
+        const uint32_t y = x >> __builtin_amdgcn_ubfe(xp_plane, 3u, 1u);   // dwords 0, 1 = planes 0, 2; dwords 2, 3 = planes 1, 3
+        return u32x2{expand_plane0(y, 0x22222222u), expand_plane2(y, 0x22222222u)};
+    };
+    // the arithmetic of one tile: r[] = the tile's four fragments; rebase = what the running pairs are re-based by first (0: not at all)
+    auto tile_math = [&](const u32x4 (&r)[KS], const v4f (&c)[2], auto rebase) {
+        constexpr int RB = decltype(rebase)::value;
+#pragma unroll
+        for (int u = 0; u < NG; ++u) {
+            v4f c0, c1;
+            mfma16_group(r, bq[u][0], bq[u][1], c[0], c[1], c0, c1);
+            top2_update_halves<RB != 0>(m1[u], m2[u], c0, c1, (float)RB * kEps);
+            __builtin_amdgcn_sched_barrier(0);   // (one (c0, c1) pair alive at a time)
+        }
+    };
+    auto tile_body = [&](int it, const v4f (&c)[2]) {
+        u32x4 r[KS];
+        uint32_t x;
+        const uint32_t addr = xp_frag + (uint32_t)(it & 1) * (KS * 1024u);
+        const uint32_t ra = raw_addr(it + 1), wa = plane_addr(it + 1);
+        asm volatile(
+            "ds_read_b32 %4, %6\n\tds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:1024\n\tds_read_b128 %2, %5 offset:2048\n\t"
+            "ds_read_b128 %3, %5 offset:3072"
+            : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(x)
+            : "v"(addr), "v"(ra)
+            : "memory");
+        asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x));
+        const u32x2 o = expand_pair(x);
+        asm volatile("ds_write_b64 %0, %1" ::"v"(wa), "v"(o) : "memory");
+        // (in order behind the four fragment reads: fragment s is complete once at most 4 - s operations are outstanding)
+        asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r[0]));
+        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
+        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
+        asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
+        tile_math(r, c, std::integral_constant<int, 32>{});
+    };
+
+#pragma unroll
+    for (int t = 0; t < PD; ++t)
+        if (t < ntiles) copy_tile(t);
+    // the query operand, expanded once per wave from the raw descriptors: lane (l & 15, g) owns words g and 4 + g of its row.  Rows >= nq
+    // read as zero bits.
+#pragma unroll
+    for (int u = 0; u < NG; ++u) {
+        const int row = qt0 * 32 + 16 * u + (l & 15);
+        uint32_t v0 = 0u, v1 = 0u;
+        if (row < nq) {
+            const uint32_t *qp = qw + (size_t)b * q_batch_words + (size_t)row * (2 * KS) + (size_t)(l >> 4);
+            v0 = qp[0], v1 = qp[KS];
+        }
+        bq[u][0] = u32x4{expand_plane(v0, 0), expand_plane(v0, 2), expand_plane(v0, 1), expand_plane(v0, 3)};
+        bq[u][1] = u32x4{expand_plane(v1, 0), expand_plane(v1, 2), expand_plane(v1, 1), expand_plane(v1, 3)};
+    }
+    {
+        // tile 0: the query loads' wait has covered the first copies; one barrier makes the four quarters visible, then every wave expands
+        // its word of the tile into fragment slot 0
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        uint32_t x;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(x) : "v"(raw_addr(0)) : "memory");
+        const u32x2 o = expand_pair(x);
+        asm volatile("ds_write_b64 %0, %1" ::"v"(plane_addr(0)), "v"(o) : "memory");
+    }
+
+    // only the last tile of the train set can be ragged; it runs after the loop with its own C (rows >= nt start at -inf and stay there)
+    const bool ragged = row0 + ntiles * 32 > nt;
+    const int nfull = ragged ? ntiles - 1 : ntiles;
+    auto arrive = [&](int it) {
+        // own quarter of raw tile it + 1 landed; own planes of tile `it` (written in the previous iteration, or the prologue) complete
+        if (it + PD < ntiles) {
+            copy_tile(it + PD);
+            asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+    };
+    int it = 0;
+    {
+        // steady state, unrolled by the period of the fragment ring: the protocol and the addresses of the kernel above, pair by pair
+        const uint32_t dma_lds = raw_lds + (uint32_t)w * 256u;
+        int raw_step = 2 * 1024;   // +2 KiB, -2 KiB, ...: the raw slots 0, 1 <-> 2, 3 (scalar)
+        auto tile_fixed = [&](auto jc, auto copier) {
+            constexpr int J = decltype(jc)::value;
+            __builtin_amdgcn_sched_barrier(0);   // (a tile's instructions stay inside the tile, as the back edge of the rolled loop keeps them)
+            if constexpr (decltype(copier)::value) {
+                const uint32_t m0 = dma_lds + (uint32_t)((it + J + PD + NR - 1) & (NR - 1)) * 1024u - (uint32_t)J * 1024u;
+                __builtin_amdgcn_global_load_lds((const void *)(rbase + xp_voff), (__attribute__((address_space(3))) void *)(uintptr_t)m0, 4, J * 1024, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            u32x4 r[KS];
+            uint32_t x;
+            asm volatile(
+                "ds_read_b32 %4, %6 offset:%7\n\tds_read_b128 %0, %5 offset:%8\n\tds_read_b128 %1, %5 offset:%8+1024\n\t"
+                "ds_read_b128 %2, %5 offset:%8+2048\n\tds_read_b128 %3, %5 offset:%8+3072"
+                : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(x)
+                : "v"(xp_frag), "v"(xp_raw), "i"(J * 1024), "i"((J & 1) * (KS * 1024))
+                : "memory");
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x));
+            const u32x2 o = expand_pair(x);
+            asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(xp_plane), "v"(o), "i"(((J + 1) & 1) * (KS * 1024)) : "memory");
+            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r[0]));
+            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
+            asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
+            tile_math(r, cinit[J], std::integral_constant<int, J == 0 ? 64 : 0>{});
+        };
+        auto run_pairs = [&](auto copier) {
+            while (it + 3 < nfull) {
+                tile_fixed(std::integral_constant<int, 0>{}, copier);
+                tile_fixed(std::integral_constant<int, 1>{}, copier);
+                if constexpr (decltype(copier)::value) xp_voff += 2 * 1024, xp_it0 += 2;
+                xp_raw += (uint32_t)raw_step;
+                raw_step = -raw_step;
+                it += 2;
+            }
+        };
+        if (w < KS) run_pairs(std::true_type{});
+        else run_pairs(std::false_type{});
+        if (raw_step < 0) xp_raw -= 2 * 1024;   // (back to raw slot 0 for the rolled tail)
+    }
+    for (; it < nfull; ++it) {
+        arrive(it);
+        tile_body(it, cinit[1]);
+    }
+    // what follows the tile loop forms the lane and thread indices anew (see the kernel above)
+    const int l_end = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const unsigned tid_end = (unsigned)(w * 64 + l_end);
+    if (ragged) {
+        arrive(nfull);
+#pragma unroll
+        for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int lr = 16 * rh + 4 * (l_end >> 4) + i;
+                cinit[1][rh][i] = (row0 + nfull * 32 + lr < nt) ? kAccBias - (float)lr * kEps : -INFINITY;
+            }
+        tile_body(nfull, cinit[1]);
+    }
+
+    int le = l_end, qt0e = qt0;
+    asm volatile("" : "+v"(le), "+s"(qt0e));
+    const int ge = le >> 4;
+    const float frame = (float)(32 * (ntiles - 1));
+    int pass_acc = 0;
+#pragma unroll
+    for (int u = 0; u < NG; ++u) {
+        uint32_t k[2];
+        const float mm[2] = {m1[u], m2[u]};
+#pragma unroll
+        for (int j = 0; j < 2; ++j)   // (-inf: no candidate)
+            k[j] = mm[j] == -INFINITY ? 0xFFFFFFFFu : decode_key_biased(mm[j], frame, dshift, DistRule{64 * KS, 0, 0});
+        const uint2 kk = top2_across_groups(k);
+        const int q = qt0e * 32 + 16 * u + (le & 15);
+        const uint32_t k0 = kk.x;
+        uint32_t k1 = kk.y;
+        if (fuse.k != 1) {   // (one neighbour: m1 is exact as it is)
+            uint32_t q8[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            if (q < nq) {
+                const uint4 *qp = reinterpret_cast<const uint4 *>(qw + (size_t)b * q_batch_words + (size_t)q * (2 * KS));
+                const uint4 v0 = qp[0], v1 = qp[1];
+                q8[0] = v0.x, q8[1] = v0.y, q8[2] = v0.z, q8[3] = v0.w, q8[4] = v1.x, q8[5] = v1.y, q8[6] = v1.z, q8[7] = v1.w;
+            }
+            k1 = min(k1, block_rescan4(k0, q8, rbase, nt - row0, dshift, ge));
+        }
+        if (fuse.idx && nsplit == 1) {  // the final top-2 of the query: outputs straight from the registers
+            const uint32_t lmask = (1u << dshift) - 1u;
+            bool pass = false;
+            if (ge == 0 && q < nq) {
+                const size_t o = ((size_t)b * nq + q) * fuse.k;
+                const int d0 = k0 == 0xFFFFFFFFu ? -1 : (int)(k0 >> dshift);
+                fuse.idx[o] = k0 == 0xFFFFFFFFu ? -1 : (int)(row0 + (k0 & lmask));
+                fuse.dist[o] = d0;
+                if (fuse.k == 2) {
+                    const int d1 = k1 == 0xFFFFFFFFu ? -1 : (int)(k1 >> dshift);
+                    fuse.idx[o + 1] = k1 == 0xFFFFFFFFu ? -1 : (int)(row0 + (k1 & lmask));
+                    fuse.dist[o + 1] = d1;
+                    pass = (float)d0 < __fmul_rn(fuse.ratio, (float)d1);
+                } else {
+                    pass = true;
+                }
+            }
+            const int c = __popcll(__ballot(pass));
+            pass_acc = (u & 3) ? pass_acc + c : c;   // a group of 64 queries = groups 4 j .. 4 j + 3 of this wave (32 qt0 is a multiple of 64)
+            if (fuse.group_counts && (u & 3) == 3 && le == 0 && qt0e * 32 + 16 * (u - 3) < nq)
+                fuse.group_counts[(size_t)b * ((nq + 63) >> 6) + ((qt0e * 32 + 16 * u) >> 6)] = pass_acc;
+        } else if (ge == 0 && q < nq) {
+            if (fuse.idx)  // read back by another workgroup of THIS launch: written through to the coherence point
+                __hip_atomic_store(reinterpret_cast<unsigned long long *>(&part[((size_t)b * nsplit + split) * nq + q]),
+                                   (unsigned long long)k0 | ((unsigned long long)k1 << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                part[((size_t)b * nsplit + split) * nq + q] = make_uint2(k0, k1);
+        }
+    }
+    if (fuse.idx && nsplit > 1) fold_splits_by_ticket<NW * QT * 32, 64 * NW>(fuse, part, split_tile0, b, qb, qblocks, nsplit, rows_per_split, nq, dshift, tid_end, le);
+    if (stamps && l_end == 0) clock_stamp(stamps + ((size_t)item * NW + w) * 4, st_c, st_r, ntiles, QT);
+    if (fuse.clk && item == 0 && tid_end == 0) {
+        fuse.clk[0] = __builtin_amdgcn_s_memtime() - st_c;
+        fuse.clk[1] = __builtin_amdgcn_s_memrealtime() - st_r;
+        fuse.clk[2] = st_r;
+        fuse.clk[3] = fuse.launch_no;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // The LDS-ring kernel with DYNAMIC train splits.  With fixed, equal work items the hardware's oldest-first arbitration lets the four
 // workgroups of a CU finish one after the other (28 ... 50 us for identical items) and the CU runs the second half of the launch
 // under-occupied.  Here the workgroups that serve one (image pair, block of 4 query groups, row span) form a TEAM and draw chunks of
@@ -1185,6 +1597,11 @@ void launch_ring(const RingLaunch &a) {
                        a.t_batch, a.nq, a.nt, a.rps, a.nsplit, a.dshift, a.qblocks, a.n_items, a.part, a.stamps, a.split_tab, a.fuse);
 }
 
+void launch_ring16(const RingLaunch &a) {
+    hipLaunchKernelGGL(knn_hamming_mfma_lds16_kernel, a.grid, dim3(64 * 8), 0, a.s, a.qw, a.q_batch_words, a.tsrc, a.t_batch, a.nq, a.nt, a.rps, a.nsplit, a.dshift,
+                       a.qblocks, a.n_items, a.part, a.stamps, a.split_tab, a.fuse);
+}
+
 // Age-aware split sizes (static LDS-ring kernel).  With exactly R = 4 workgroups per CU the dispatcher deals workgroups breadth
 // first, so workgroup L is the (L / num_cus)-th oldest wave set on its CU, and the SIMD arbitrates oldest-first: measured per-tile
 // costs with all four ranks active are 1700 / 2100 / 3200 / 5300 cycles (tools/hamming_trace.py), i.e. equal splits finish at
@@ -1313,6 +1730,9 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     // block size of the running top-2 update (option hamming_block_top2): the instances that have the raw train rows
     const int block_top2 = inkernel ? ctx->opt_hamming_block_top2 : 0;
     ctx->dbg_hamming_top2 = block_top2;
+    // matrix-core shape (option hamming_mfma_shape): the 16x16x128 form exists for the throughput instance without the stamps trace only
+    const int shape = (inkernel && block_top2 == 4 && ctx->opt_hamming_stamps != 1 && ctx->opt_hamming_mfma_shape == 16) ? 16 : 32;
+    ctx->dbg_hamming_shape = shape;
 
     void *qf = nullptr, *tf = nullptr, *part = nullptr;
     int rc;
@@ -1420,7 +1840,7 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
         if (inkernel && stamps)   // (hamming_stamps = 1: the rolled loop with the per-tile clock trace)
             block_top2 == 4 ? launch_ring<4, 0, 8, 2, true, true, 4>(ra) : launch_ring<4, 0, 8, 2, true, true>(ra);
         else if (inkernel)
-            block_top2 == 4 ? launch_ring<4, 0, 8, 2, true, false, 4>(ra) : launch_ring<4, 0, 8, 2, true>(ra);
+            block_top2 != 4 ? launch_ring<4, 0, 8, 2, true>(ra) : shape == 16 ? launch_ring16(ra) : launch_ring<4, 0, 8, 2, true, false, 4>(ra);
         else if (nwv == 16) launch_ring<4, 0, 16>(ra);
         else if (nwv == 8 && pd == 4) launch_ring<4, 0, 8, 4>(ra);
         else if (nwv == 8 && pd == 6) launch_ring<4, 0, 8, 6>(ra);

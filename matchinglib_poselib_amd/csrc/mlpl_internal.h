@@ -139,6 +139,8 @@ struct mlpl_ctx {
     int opt_vfc_store_u;            // 1 = the VFC kernel keeps the m x n kernel matrix U in the workspace; 0 (default, unmeasured: DESIGN section 8) = it recomputes U in both passes of an iteration
     int opt_hamming_expand_inkernel;   // 1 = the static LDS-ring kernel's throughput instance expands the raw train tiles itself (no expansion launch, no WS_FRAG_T)
     int opt_hamming_block_top2;        // 0 = the ring kernel folds every candidate into its running top-2; 4 = the in-kernel-expansion instances fold the maxima of blocks of four candidates and re-score the best row's block in the epilogue (same results)
+    int opt_hamming_mfma_shape;        // 32 = v_mfma_f32_32x32x64_f8f6f4 everywhere; 16 = the throughput instance of the static ring kernel (eight waves, in-kernel expansion, block update, no stamps trace) runs on 16x16x128 (same results)
+    int dbg_hamming_shape;             // MFMA shape the last Hamming launch really used (mlpl_debug_last_hamming_shape; 0 = a VALU kernel)
     int dbg_hamming_top2;              // block size the last Hamming launch really used (mlpl_debug_last_hamming_top2)
     void *subpix_sep_mask_ptr;      // the WS_SUBPIX_SEP_MASK block that holds the mask profiles of subpix_separate.hip
     int dbg_stamp_items;

@@ -180,6 +180,21 @@ int getPoseTriangPts(cv::InputArray E, cv::InputArray p1, cv::InputArray p2, cv:
 int triangPts3D(cv::InputArray R, cv::InputArray t, cv::InputArray points1, cv::InputArray points2, cv::OutputArray Q3D,
                 cv::InputOutputArray mask = cv::noArray(), const double dist = 50.0);
 
+// poselib::refineStereoBA (pose_estim.h:230-246, pose_estim.cpp:1083-1348): bundle adjustment of motion and structure with the first camera
+// fixed and the pseudo-Huber cost.  Built: pointsInImgCoords == false -- p1, p2 n x 2 CV_64F in CAMERA coordinates, R 3 x 3, t 3 x 1, Q n x 3
+// (all CV_64F, refined in place), K1, K2 only read (the Huber threshold in pixels, 0.005 for a negative huber_thresh, is converted with
+// K(1,1) + K(2,2) of both, the reference's indices), mask 1 x n CV_8U or absent.  Returns false with R and Q untouched and t restored when the
+// optimiser fails (fewer than 12 valid points among them), when the refined rotation differs by more than angleThresh degrees or the
+// translation by more than t_norm_tresh, or when the optimiser stopped for reason > 5; false without touching anything for empty or
+// mismatched inputs.  NOT built, refused with one line on std::cout and false, every argument untouched: pointsInImgCoords == true,
+// optimFocalOnly, optimMotionOnly, fixCamMat, dist1 / dist2.  The arithmetic is a float64 restatement (tests/ba_oracle.py) that is not
+// pinned against a build of the reference's SBA.
+bool refineStereoBA(cv::InputArray p1, cv::InputArray p2, cv::InputOutputArray R, cv::InputOutputArray t, cv::InputOutputArray Q,
+                    cv::InputOutputArray K1, cv::InputOutputArray K2, bool pointsInImgCoords = false, cv::InputArray mask = cv::noArray(),
+                    const double angleThresh = 1.25, const double t_norm_tresh = 0.05, const double huber_thresh = -1.0,
+                    const bool optimFocalOnly = false, const bool optimMotionOnly = false, const bool fixCamMat = false,
+                    cv::InputOutputArray dist1 = cv::noArray(), cv::InputOutputArray dist2 = cv::noArray());
+
 // Convenience named in BASELINE.json: estimateEssentialMat(..., "RANSAC", ...) followed by getPoseTriangPts, the
 // sequence the reference's README prescribes (README.md:497-521).
 bool estimateRelativePose(cv::InputArray p1, cv::InputArray p2, cv::OutputArray E, cv::OutputArray R, cv::OutputArray t,

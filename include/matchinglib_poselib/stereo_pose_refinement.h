@@ -16,13 +16,17 @@
 // (checkPoolPoseRobust != 1, :680-716) the pool pose is refined by refinePoseFromPool (:1767-2074) with refineRTold_CorrPool,
 // refineMethod_CorrPool or kneipInsteadBA_CorrPool in the same way, starting from R_new / t_new.  All of it on the device.
 //
-// Not built (outside the hot path): homography alignment (Halign), bundle adjustment (BART, BART_CorrPool)
-// and, inside USAC, Kneip's estimator and refinements.  Consequences:
+// Bundle adjustment of motion and structure (BART = 1, BART_CorrPool = 1: poselib::refineStereoBA on camera coordinates) runs where the
+// reference runs it (:1695-1702, :2034-2041), a failure prints "Bundle adjustment failed!" and the estimation goes on, E is rebuilt from R
+// and t (:1721, :2052); a failed Kneip-instead-of-BA step goes to bundle adjustment as there (:1650-1658, :1987-1994).
+//
+// Not built (outside the hot path): homography alignment (Halign), bundle adjustment with the intrinsics in
+// the parameter vector (BART = 2, BART_CorrPool = 2) and, inside USAC, Kneip's estimator and refinements.  Consequences:
 //   * RobMethod is "USAC" (the reference's default; estimateEssentialOrPoseUSAC with the ConfigUSAC handed to addNewCorrespondences, a
 //     degenerate pair -> -2, :1355-1413), "RANSAC", "LMEDS" or "ARRSAC"; Halign makes addNewCorrespondences() return -1; autoTH (ARRSAC
 //     with poselib::AutoThEpi's threshold estimation, :1330-1342) is built;
-//   * BART / BART_CorrPool are ignored (reported once on std::cout); where the reference would hand a failed Kneip-instead-of-BA step to
-//     bundle adjustment it takes its other path, Stewenius with pseudo-Huber weights;
+//   * BART / BART_CorrPool = 2 are ignored (reported once on std::cout); where the reference would hand a failed Kneip-instead-of-BA step to
+//     that bundle adjustment the library takes the reference's other path, Stewenius with pseudo-Huber weights;
 //   * no estimator hands a pose over, so the refinement after the robust estimation never starts from one (`availableRT` starts false,
 //     :1429-1449): Kneip's solver there starts from up to 12 perturbed identities drawn from setRansacSeed's seed;
 //   * a configuration without a linear refinement keeps the estimator's E as it is, where the reference rebuilds it from R and t
@@ -152,6 +156,13 @@ class StereoRefine {
     size_t skipCounter() const;
     size_t poseHistorySize() const;
     const cv::Mat &maskENew() const;
+    // what the last bundle adjustment (BART = 1, BART_CorrPool = 1) was called with, and its verdict; calls counts them since construction
+    struct BundleAdjustRecord {
+        int calls = 0;
+        bool accepted = false;
+        cv::Mat p1, p2, R, t, Q, mask;
+    };
+    const BundleAdjustRecord &lastBundleAdjust() const;
 
    private:
     struct Impl;

@@ -132,7 +132,7 @@ int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value);
  * When enabled, the launches of the dominant kernel of each path are bracketed with hipEvents on the stream
  * they run on.  mlpl_profile_read() synchronises those events and returns the summed duration and the
  * launch count since the last reset.  kernel_id: 0 = Hamming partial top-2 (matrix-core or VALU kernel), 1 = knn_l2 (exact or
- * MFMA), 2 = 5-point solver, 3 = Sampson scoring, 4 = recover_pose.  mlpl_profile_enable(ctx, N): 0 = off, 1 = every launch,
+ * MFMA), 2 = 5-point solver, 3 = Sampson scoring, 4 = recover_pose, 6 = bundle adjustment.  mlpl_profile_enable(ctx, N): 0 = off, 1 = every launch,
  * N > 1 = every Nth launch (sampling: the two event records cost ~10 us of stream time per bracketed launch). */
 #define MLPL_PROF_KNN_HAMMING 0
 #define MLPL_PROF_KNN_L2 1
@@ -140,7 +140,8 @@ int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value);
 #define MLPL_PROF_SCORE 3
 #define MLPL_PROF_RECOVER_POSE 4
 #define MLPL_PROF_COUNT 5         /* the inlier-counting kernel of a RANSAC pass alone (MLPL_PROF_SCORE brackets the whole scoring pass: it, the candidate selection and the candidates' error sums) */
-#define MLPL_PROF_NUM 6
+#define MLPL_PROF_BUNDLE_ADJUST 6 /* the bundle-adjustment kernel (mlpl_refine_stereo_ba*): one launch per call */
+#define MLPL_PROF_NUM 7
 int mlpl_profile_enable(mlpl_ctx *ctx, int on);
 int mlpl_profile_reset(mlpl_ctx *ctx);
 int mlpl_profile_read(mlpl_ctx *ctx, int kernel_id, double *total_ms, int *launches);
@@ -833,6 +834,29 @@ int mlpl_triang_pts3d_dev(mlpl_ctx *ctx, const double R[9], const double t[3], c
  * n_good[b] (host).  One launch for the whole batch; every problem's mask, count and points are bit-identical to mlpl_triang_pts3d's. */
 int mlpl_triang_pts3d_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                                 const double *R, const double *t, double dist, uint8_t *d_masks, double *d_Q, int32_t *n_good, void *stream);
+
+/* Bundle adjustment of one stereo pair: poselib::refineStereoBA with pointsInImgCoords == false (P/source/pose_estim.cpp:1083-1206, :1294-1348) --
+ * motion and structure, calibrated cameras, the first camera fixed, the pseudo-Huber cost, no covariances; SBAdriver::perform_sba
+ * (P/source/BA_driver.cpp:1878-2260) around sba_motstr_levmar_x (sba-1.6/sba_levmar.c:449-1400) restated in float64 (tests/ba_oracle.py is
+ * the restatement; it is not pinned against an SBA build).  p1, p2: n x 2 in CAMERA coordinates; mask: NULL or n bytes (nonzero = use);
+ * R[9], t[3]: in / out; Q: n x 3, in / out; th: the Huber threshold in CAMERA units, ALREADY converted
+ * (4 th_px / (sqrt(2) (K1(1,1) + K1(2,2) + K2(1,1) + K2(2,2))), the reference's indices; the C++ drop-in converts); info: NULL or the
+ * optimiser's info[0..9] (sba_levmar.c:1377-1400; all zero when the optimiser refuses the problem: fewer than 12 valid points, i.e. fewer
+ * measurements than unknowns, or its "almost singular" return).  Returns 1 = accepted (R, t -- normalised when | |t| - 1 | > 1e-4 -- and the
+ * valid rows of Q refined), 0 = rejected (|rotation change| > angle_thresh degrees, translation change > t_norm_thresh, stop reason > 5) or
+ * failed: R, t and Q untouched; negative: an MLPL_E_* error.  One launch: the whole Levenberg-Marquardt iteration runs in one workgroup. */
+int mlpl_refine_stereo_ba(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask, double R[9], double t[3], double *Q,
+                          double th, double angle_thresh, double t_norm_thresh, double info[10]);
+/* The same on device-resident d_p1, d_p2 (n x 2), d_Q (n x 3, in / out), d_mask (n bytes or NULL); only the pose and info are read back. */
+int mlpl_refine_stereo_ba_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const uint8_t *d_mask, double R[9], double t[3],
+                              double *d_Q, double th, double angle_thresh, double t_norm_thresh, double info[10], void *stream);
+/* A batch in the layout of mlpl_triang_pts3d_batch_dev, behind which it chains: d_p1 / d_p2 + b stride 2, counts[b], d_masks NULL or
+ * [n_problems][stride], d_Q [n_problems][stride][3] (in / out; rows outside the mask and beyond counts[b] untouched), host R + 9 b, t + 3 b
+ * (in / out), th[b], accepted[b] (1 / 0 as above; a problem without a valid point gives 0), info + 10 b (or NULL).  One launch, one workgroup
+ * per problem; every problem's result is bit-identical to mlpl_refine_stereo_ba's.  Returns 0 or a negative error. */
+int mlpl_refine_stereo_ba_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
+                                    const uint8_t *d_masks, double *d_Q, double *R, double *t, const double *th, double angle_thresh,
+                                    double t_norm_thresh, int32_t *accepted, double *info, void *stream);
 
 
 /* The diagnostics entry points (mlpl_debug_*: traces, clock stamps, solver statistics, self-tests -- exported by the same library, used by

@@ -126,6 +126,10 @@ int mlpl_debug_l2_fold_counts(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_
 int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_live, int n_bound,
                           const int32_t *ids, int table_len, double thresh2, int point_splits, int32_t *table_inout);
 
+/* Tests: the damping term mu at exit of every problem of the calling thread's last mlpl_refine_stereo_ba* call (0 for a problem the optimiser
+ * refused).  Writes min(problems, max_items) doubles and returns that number. */
+int mlpl_debug_ba_last_mu(double *mu, int max_items);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,13 @@ _SIGNATURES = {
     "mlpl_triang_pts3d_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "mlpl_triang_pts3d_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
+    "mlpl_refine_stereo_ba": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
+                                      c_void_p]),
+    "mlpl_refine_stereo_ba_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                          c_double, c_void_p, c_void_p]),
+    "mlpl_refine_stereo_ba_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_debug_ba_last_mu": (c_int, [c_void_p, c_int]),
 }
 
 

@@ -249,6 +249,14 @@ struct StereoRefine::Impl {
     int refinePoseFromPool();
     size_t failed_refinements = 0;  // function-local static in the reference (:678): process-wide there, per object here
     int last_pose_source = 0;  // lastPoseSource()
+    StereoRefine::BundleAdjustRecord ba_rec;  // lastBundleAdjust()
+    // poselib::refineStereoBA as StereoRefine calls it (:1699, :2038): camera coordinates, the defaults; a failure is reported and goes on
+    void bundleAdjust(const cv::Mat &P1, const cv::Mat &P2, cv::Mat &R, cv::Mat &t, cv::Mat &Q3, const cv::Mat &mask) {
+        ba_rec.calls++;
+        ba_rec.p1 = P1.clone(), ba_rec.p2 = P2.clone(), ba_rec.R = R.clone(), ba_rec.t = t.clone(), ba_rec.Q = Q3.clone(), ba_rec.mask = mask.clone();
+        ba_rec.accepted = refineStereoBA(P1, P2, R, t, Q3, *cfg_pose.K0, *cfg_pose.K1, false, mask);
+        if (!ba_rec.accepted) std::cout << "Bundle adjustment failed!" << std::endl;
+    }
     // refineEssentialLinear as StereoRefine always calls it: th, 4 steps, 2.0, 0.1, 0.15; nr_inliers_new follows an accepted refinement
     bool refineLinear(const cv::Mat &P1, const cv::Mat &P2, cv::Mat &E, cv::Mat &mask, int method, cv::Mat *R, cv::Mat *t) {
         if (R && t) return refineEssentialLinear(P1, P2, E, mask, method, nr_inliers_new, *R, *t, th, 4, 2.0, 0.1, 0.15);
@@ -313,8 +321,9 @@ void StereoRefine::Impl::checkInputParamters() {  // :187-400 (values only; the 
     if (c.absThRankingStable < 0.01) c.absThRankingStable = 0.01;
     else if (c.absThRankingStable > 0.9) c.absThRankingStable = 0.6;
     // Built: the linear refinement solvers after the robust estimation (refineMethod, kneipInsteadBA) and on the pool between robust
-    // estimations (refineMethod_CorrPool, kneipInsteadBA_CorrPool, checkPoolPoseRobust != 1).  Not built: bundle adjustment.
-    if (c.BART || c.BART_CorrPool) notice("bundle adjustment (BART, BART_CorrPool) is not built and is skipped");
+    // estimations (refineMethod_CorrPool, kneipInsteadBA_CorrPool, checkPoolPoseRobust != 1), bundle adjustment of motion and structure
+    // (BART = 1, BART_CorrPool = 1).  Not built: bundle adjustment with the intrinsics in the parameter vector (value 2).
+    if (c.BART == 2 || c.BART_CorrPool == 2) notice("bundle adjustment with intrinsics (BART = 2, BART_CorrPool = 2) is not built and is skipped");
     noticed = true;
 }
 
@@ -457,28 +466,38 @@ int StereoRefine::Impl::robustPoseEstimation() {
         }
         if (!kneipSuccess) {
             std::cout << "Refinement using Kneips Eigen solver instead of bundle adjustment (BA) failed!" << std::endl;
-            // BART is not built: the reference's path without it
-            std::cout << "Trying refinement with weighted (Pseudo-Huber) Stewenius instead!" << std::endl;
-            const int refineMethod_save = cfg_pose.refineMethod;
-            cfg_pose.refineMethod = PR_STEWENIUS | PR_PSEUDOHUBER_WEIGHTS;
-            // (sic) :1665-1689: the test is inverted -- a refinement that SUCCEEDS is reported as failed and ends the estimation (with
-            // refineMethod left at the fallback's value), only a failing one goes on to the triangulation
-            if (!refineLinear(P1, P2, E, mask, cfg_pose.refineMethod, nullptr, nullptr)) {
-                mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
+            if (cfg_pose.BART == 1) {  // :1650-1658 (the reference takes this path for BART = 2 as well; that adjustment is not built)
+                std::cout << "Trying bundle adjustment instead!" << std::endl;
                 Q3 = cv::Mat();
-                if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+                if (triangPts3D(R, t, P1, P2, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
                     std::cout << "Unable to triangulate 3D points" << std::endl;
                     return -1;
                 }
-                last_pose_source = 1;
             } else {
-                std::cout << "Refinement failed!" << std::endl;
-                return -1;
+                std::cout << "Trying refinement with weighted (Pseudo-Huber) Stewenius instead!" << std::endl;
+                const int refineMethod_save = cfg_pose.refineMethod;
+                cfg_pose.refineMethod = PR_STEWENIUS | PR_PSEUDOHUBER_WEIGHTS;
+                // (sic) :1665-1689: the test is inverted -- a refinement that SUCCEEDS is reported as failed and ends the estimation (with
+                // refineMethod left at the fallback's value), only a failing one goes on to the triangulation
+                if (!refineLinear(P1, P2, E, mask, cfg_pose.refineMethod, nullptr, nullptr)) {
+                    mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
+                    Q3 = cv::Mat();
+                    if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+                        std::cout << "Unable to triangulate 3D points" << std::endl;
+                        return -1;
+                    }
+                    last_pose_source = 1;
+                } else {
+                    std::cout << "Refinement failed!" << std::endl;
+                    return -1;
+                }
+                cfg_pose.refineMethod = refineMethod_save;
             }
-            cfg_pose.refineMethod = refineMethod_save;
         }
     }
-    storePose(E, R, t, useBA && rebuild, mask, Q3);
+    const bool adjust = useBA && cfg_pose.BART == 1;  // :1695-1702, then E = getEfromRT(R, t) (:1721)
+    if (adjust) bundleAdjust(P1, P2, R, t, Q3, mask);
+    storePose(E, R, t, (useBA && rebuild) || adjust, mask, Q3);
     return 0;
 }
 
@@ -657,22 +676,32 @@ int StereoRefine::Impl::refinePoseFromPool() {
         }
         if (!kneipSuccess) {
             std::cout << "Refinement using Kneips Eigen solver instead of bundle adjustment (BA) failed!" << std::endl;
-            std::cout << "Trying refinement with weighted (Pseudo-Huber) Stewenius instead!" << std::endl;  // BART_CorrPool is not built
-            const int method = PR_STEWENIUS | PR_PSEUDOHUBER_WEIGHTS;
-            // (sic) :2001-2028: inverted as in robustPoseEstimation; here refineMethod_CorrPool is restored on every path
-            if (refineLinear(P1, P2, E, mask, method, &R_tmp, &t_tmp)) {
-                std::cout << "Refinement failed!" << std::endl;
-                return -1;
+            if (cfg_pose.BART_CorrPool == 1) {  // :1987-1994 (value 2 takes this path in the reference as well; that adjustment is not built)
+                std::cout << "Trying bundle adjustment instead!" << std::endl;
+                if (triangPts3D(R, t, P1, P2, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+                    std::cout << "No 3D points left after triangulation!" << std::endl;
+                    return -1;
+                }
+            } else {
+                std::cout << "Trying refinement with weighted (Pseudo-Huber) Stewenius instead!" << std::endl;
+                const int method = PR_STEWENIUS | PR_PSEUDOHUBER_WEIGHTS;
+                // (sic) :2001-2028: inverted as in robustPoseEstimation; here refineMethod_CorrPool is restored on every path
+                if (refineLinear(P1, P2, E, mask, method, &R_tmp, &t_tmp)) {
+                    std::cout << "Refinement failed!" << std::endl;
+                    return -1;
+                }
+                mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
+                Q3 = cv::Mat();
+                if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
+                    std::cout << "No 3D points left after triangulation!" << std::endl;
+                    return -1;
+                }
+                last_pose_source = 1;
             }
-            mask_E_new.assign(mask.ptr<uint8_t>(0), mask.ptr<uint8_t>(0) + n);
-            Q3 = cv::Mat();
-            if (getPoseTriangPts(E, P1, P2, R, t, Q3, mask, cfg_pose.maxDist3DPtsZ) <= 0) {
-                std::cout << "No 3D points left after triangulation!" << std::endl;
-                return -1;
-            }
-            last_pose_source = 1;
         }
     }
+    // :2034-2041, then E = getEfromRT(R_new, t_new) (:2052), which this path does whenever useBA holds
+    if (useBA && cfg_pose.BART_CorrPool == 1) bundleAdjust(P1, P2, R, t, Q3, mask);
     storePose(E, R, t, useBA, mask, Q3);
     return 0;
 }
@@ -1708,5 +1737,6 @@ size_t StereoRefine::nrEstimations() const { return d->nrEstimation; }
 size_t StereoRefine::skipCounter() const { return d->skipCount; }
 size_t StereoRefine::poseHistorySize() const { return d->pose_history.size(); }
 const cv::Mat &StereoRefine::maskENew() const { return d->mask_E_new_mat; }
+const StereoRefine::BundleAdjustRecord &StereoRefine::lastBundleAdjust() const { return d->ba_rec; }
 
 }  // namespace poselib

@@ -67,6 +67,7 @@ enum WsSlot {
     WS_SUBPIX,    // sub-pixel refinement (subpix.hip): per-match records and positions, per-keypoint winners, per-list results and tickets
     WS_SUBPIX_SEP,      // cornerSubPix refinement (subpix_separate.hip): per-match records and positions, per-keypoint winners, per-list results and tickets
     WS_SUBPIX_SEP_MASK, // ... its eight mask profiles (uploaded when the context is created)
+    WS_BA,              // bundle adjustment (bundle_adjust.hip): per-point state of every problem, then the compacted row lists
     WS_NUM_SLOTS
 };
 

@@ -619,6 +619,100 @@ def triang_pts3d_batch(d_p1, d_p2, counts, R, t, d_masks=None, d_Q=None, dist: f
     return n_good
 
 
+ROBUST_THRESH = 0.005  # BA_driver.h: the pseudo-Huber threshold in pixels that a negative huber_thresh selects
+
+
+def ba_threshold(K1, K2, huber_thresh: float = -1.0) -> float:
+    """The Huber threshold in camera units as poselib::refineStereoBA converts it (pose_estim.cpp:1132-1136, :1195): the sum reads
+    K(1,1) and K(2,2) -- fy and the 1.0 --, as the reference indexes."""
+    th = huber_thresh if huber_thresh >= 0 else ROBUST_THRESH
+    K1, K2 = np.asarray(K1, np.float64), np.asarray(K2, np.float64)
+    return float(4.0 * th / (np.sqrt(2.0) * (K1[1, 1] + K1[2, 2] + K2[1, 1] + K2[2, 2])))
+
+
+def _ba_last_mu(ctx, n):
+    mu = np.zeros(n)
+    got = ctx.lib.mlpl_debug_ba_last_mu(mu.ctypes.data, n)
+    return mu if got == n else None
+
+
+def refine_stereo_ba(p1, p2, R, t, Q, th: float, mask=None, angle_thresh: float = 1.25, t_norm_thresh: float = 0.05,
+                     ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_stereo_ba: bundle adjustment of one stereo pair (motion and structure, first camera fixed, pseudo-Huber cost) on
+    camera-coordinate correspondences; th in CAMERA units (ba_threshold).  -> dict(accepted, R [3, 3], t [3], Q [n, 3], info [10], mu);
+    a rejected or failed run returns R, t and Q as they came."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    Rh = np.array(R, np.float64).reshape(3, 3).copy()
+    tv = np.array(t, np.float64).reshape(3).copy()
+    Qh = np.ascontiguousarray(np.array(Q, np.float64).reshape(-1, 3)).copy()
+    if p2.shape[0] != n or Qh.shape[0] != n:
+        raise ValueError("p1, p2 and Q differ in length")
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    if m is not None and m.shape[0] != n:
+        raise ValueError("the mask must hold one byte per correspondence")
+    info = np.zeros(10)
+    rc = ctx.lib.mlpl_refine_stereo_ba(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, None if m is None else m.ctypes.data, Rh.ctypes.data,
+                                       tv.ctypes.data, Qh.ctypes.data, float(th), float(angle_thresh), float(t_norm_thresh), info.ctypes.data)
+    if rc < 0:
+        raise MlplError(rc, "mlpl_refine_stereo_ba", _lib.last_error())
+    mu = _ba_last_mu(ctx, 1) if n > 0 else None
+    return dict(accepted=bool(rc), R=Rh, t=tv, Q=Qh, info=info, mu=0.0 if mu is None else float(mu[0]))
+
+
+def refine_stereo_ba_device(d_p1, d_p2, R, t, d_Q, th: float, d_mask=None, angle_thresh: float = 1.25, t_norm_thresh: float = 0.05,
+                            ctx: Optional[Context] = None, stream: Optional[int] = None) -> dict:
+    """mlpl_refine_stereo_ba_dev on device-resident torch tensors (float64 [n, 2], d_Q float64 [n, 3] refined in place when accepted, d_mask
+    uint8 [n] or None) -> dict(accepted, R, t, info, mu).  Only the pose and info are read back."""
+    import torch
+
+    n = d_p1.shape[0]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (n, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    assert d_Q.is_cuda and d_Q.dtype == torch.float64 and d_Q.shape == (n, 3) and d_Q.is_contiguous()
+    if d_mask is not None:
+        assert d_mask.is_cuda and d_mask.dtype == torch.uint8 and d_mask.shape == (n,) and d_mask.is_contiguous()
+    ctx = ctx or default_context(d_p1.device.index or 0)
+    Rh = np.array(R, np.float64).reshape(3, 3).copy()
+    tv = np.array(t, np.float64).reshape(3).copy()
+    info = np.zeros(10)
+    st = torch.cuda.current_stream(d_p1.device).cuda_stream if stream is None else stream
+    rc = ctx.lib.mlpl_refine_stereo_ba_dev(ctx.handle, d_p1.data_ptr(), d_p2.data_ptr(), n, None if d_mask is None else d_mask.data_ptr(),
+                                           Rh.ctypes.data, tv.ctypes.data, d_Q.data_ptr(), float(th), float(angle_thresh), float(t_norm_thresh),
+                                           info.ctypes.data, st)
+    if rc < 0:
+        raise MlplError(rc, "mlpl_refine_stereo_ba_dev", _lib.last_error())
+    mu = _ba_last_mu(ctx, 1) if n > 0 else None
+    return dict(accepted=bool(rc), R=Rh, t=tv, info=info, mu=0.0 if mu is None else float(mu[0]))
+
+
+def refine_stereo_ba_batch(d_p1, d_p2, counts, R, t, d_Q, th, d_masks=None, angle_thresh: float = 1.25, t_norm_thresh: float = 0.05,
+                           ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_stereo_ba_batch_dev in the layout of triang_pts3d_batch, behind which it chains: R [B, 3, 3], t [B, 3] (host), th a scalar
+    or [B]; d_Q (float64 CUDA tensor [B, stride, 3]) is refined in place for the accepted problems, rows outside the mask and beyond
+    counts[b] untouched.  One launch.  -> dict(accepted [B], R [B, 3, 3], t [B, 3], info [B, 10], mu [B])."""
+    import torch
+
+    B, stride = d_p1.shape[0], d_p1.shape[1]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (B, stride, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    assert d_Q.is_cuda and d_Q.dtype == torch.float64 and d_Q.shape == (B, stride, 3) and d_Q.is_contiguous()
+    if d_masks is not None:
+        assert d_masks.is_cuda and d_masks.dtype == torch.uint8 and d_masks.shape == (B, stride) and d_masks.is_contiguous()
+    ctx = ctx or default_context(d_p1.device.index or 0)
+    cn = np.ascontiguousarray(counts, np.int32).reshape(B)
+    Rh = np.ascontiguousarray(np.array(R, np.float64).reshape(B, 9)).copy()
+    tv = np.ascontiguousarray(np.array(t, np.float64).reshape(B, 3)).copy()
+    thv = np.ascontiguousarray(np.broadcast_to(np.asarray(th, np.float64), (B,))).copy()
+    acc, info = np.zeros(B, np.int32), np.zeros((B, 10))
+    rc = ctx.lib.mlpl_refine_stereo_ba_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data,
+                                                 None if d_masks is None else d_masks.data_ptr(), d_Q.data_ptr(), Rh.ctypes.data, tv.ctypes.data,
+                                                 thv.ctypes.data, float(angle_thresh), float(t_norm_thresh), acc.ctypes.data, info.ctypes.data,
+                                                 torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_refine_stereo_ba_batch_dev", _lib.last_error())
+    return dict(accepted=acc.astype(bool), R=Rh.reshape(B, 3, 3), t=tv, info=info, mu=_ba_last_mu(ctx, B))
+
+
 def ImgToCamCoordTrans(points, K, ctx: Optional[Context] = None) -> np.ndarray:
     """poselib::ImgToCamCoordTrans (pose_helper.cpp:1100-1109): float32 n x 2 pixel points -> camera coordinates."""
     ctx = ctx or default_context()

@@ -527,6 +527,68 @@ int mlpl_arrsac_sample_models(mlpl_ctx *ctx, const double *p1, const double *p2,
 int mlpl_arrsac_last_stats(mlpl_ctx *ctx, long long stats[12]);
 
 /*
+ * poselib::computeHomographyArrsac (pose_homography.h, pose_homography.cpp:478-555): a robust plane-induced homography p2 ~ H p1.
+ * n < 4 fails; n == 4 is one call of the normalised DLT kernel (runHomogrophyKernel, :674-744; mask all ones); n > 4 runs
+ * theia::Arrsac(4, th^2, 500 hypotheses, blocks of 100, inner RANSAC on at most 12 points) (:505) -- the template mlpl_arrsac_essential
+ * runs for E, with the 4-point DLT as the minimal estimator, cv::findHomography(m1, m2, 0) (float32 points, DLT, 10 Levenberg-Marquardt
+ * turns) as the non-minimal one and the one-way transfer error (:642-663, strict < th^2 inside ARRSAC) -- then findHomographyInliers
+ * (:785-813, err <= th^2 over all n) and refineHomography on those inliers (:825-885, CvLevMarq, 10 iterations).  H is the refined matrix
+ * (H(2,2) as the DLT scaled it: 1 to rounding), the mask is the one from before the refinement, as in the reference.  Estimators, error
+ * evaluations, mask, compaction and refinement run on the device; the sequential decisions are taken on the host.
+ * rng_state: in/out, the SAME two cv::RNG streams mlpl_arrsac_essential uses (function-local statics of the reference's samplers, shared
+ * by every theia::Arrsac instantiation of a process); they advance whenever ARRSAC ran, also when it found nothing.
+ * stats (may be NULL): [0..7] as mlpl_arrsac_last_stats -- {k of the initial hypothesis set, hypotheses after it, PROSAC samples,
+ * inner-RANSAC samples, inner-RANSAC restarts, samples of the preemptive stage, correspondence index where that stage ended, hypotheses
+ * left there} --, [8] device batches, [9] samples solved on the device, [10] samples the control flow consumed, [11] outliers.
+ * Returns 0; MLPL_E_FAILED for the reference's `false` (n < 4, a degenerate quadruple, no hypothesis passed the sequential test: a
+ * result, not an error -- H, mask and *n_inliers are not written); MLPL_E_BAD_INPUT for a malformed call (null pointers, n < 1, th not
+ * positive and finite; nothing is launched); MLPL_E_INTERNAL if more than 8192 samples had to be solved in one call (rng_state untouched).
+ * Every model is tested on the first 1024 correspondences up front; at inlier ratios above ~0.9 the preemptive stage keeps generating
+ * hypotheses and runs past them (its first halving comes at correspondence 1100), and the survivors' bits over all n are then computed
+ * on demand.  The _dev form takes device pointers and leaves the mask on the device.
+ */
+int mlpl_homography_arrsac(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, uint64_t rng_state[2], double H[9], uint8_t *mask,
+                           int *n_inliers, long long stats[12]);
+int mlpl_homography_arrsac_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, uint64_t rng_state[2], double H[9],
+                               uint8_t *d_mask, int *n_inliers, long long stats[12], void *stream);
+/* findHomographyInliers (pose_homography.cpp:785-813): mask[i] = 0 iff the transfer error of correspondence i under H exceeds th^2
+ * (H(2,2) is taken as 1, as the reference's error does); *n_inliers (may be NULL) = the count. */
+int mlpl_homography_inliers(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double H[9], double th, uint8_t *mask, int *n_inliers);
+int mlpl_homography_inliers_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const double H[9], double th, uint8_t *d_mask,
+                                int *n_inliers, void *stream);
+/*
+ * poselib::estimateMultHomographys (pose_homography.cpp:291-463): plane after plane with mlpl_homography_arrsac at 1.5 th (with var_th:
+ * times 1.5 per failed try while below 6 th), the outliers of a round are the next round's input in their original order, while more than
+ * 3 correspondences remain, the last plane had at least min_pts_per_plane inliers and (max_planes == 0 or fewer than max_planes rounds
+ * ran).  A plane is reported only with at least min_pts_per_plane inliers.  The correspondences stay on the device between rounds.
+ * Outputs for plane k < *n_planes, in the reference's output order (by inlier count, descending, std::sort, when more than one plane was
+ * found): H + 9 k, num_inl[k], strength[k] = 1.5 th num_inl / (th_used n), th_used[k] = the threshold of the successful try, masks + k n
+ * (n bytes in the ORIGINAL indexing; masks may be NULL).  cap = planes the output arrays hold; finding more is MLPL_E_BAD_INPUT.
+ * *n_planes = -1 is the reference's return value -1 (the first plane was not found); the call itself returns 0 then.  rng_state as above.
+ */
+int mlpl_mult_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, int var_th, unsigned max_planes, unsigned min_pts_per_plane,
+                           uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, double *th_used, uint8_t *masks);
+int mlpl_mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
+                               unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength,
+                               double *th_used, uint8_t *d_masks, void *stream);
+/* The same with one LABEL per correspondence instead of -- or beside -- the masks: the planes' inlier sets are disjoint, so labels (n
+ * int32: output plane index, -1 = none) hold what cap masks hold, and cap may be the worst case n / max(min_pts_per_plane, 1) + 1 at the
+ * cost of a few words per plane.  found_at[k] (cap int32) = the round that found output plane k: ascending found_at is the order of
+ * discovery, which the reference keeps when its caller does not ask for num_inl.  found_at, labels and masks may each be NULL; masks are
+ * written for the planes found only.  Finding more than cap planes returns MLPL_E_BAD_INPUT with rng_state put back (both forms, and the
+ * entries above), so the call can be repeated with larger arrays. */
+int mlpl_mult_homographies_labels(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, int var_th, unsigned max_planes,
+                                  unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength,
+                                  double *th_used, int32_t *found_at, int32_t *labels, uint8_t *masks);
+int mlpl_mult_homographies_labels_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
+                                      unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl,
+                                      double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, uint8_t *d_masks, void *stream);
+/* The homography estimators on `count` samples of m indices each (idx [count][m], 4 <= m <= 12), a building block exposed for parity
+ * tests (the twin of mlpl_arrsac_sample_models): m == 4 the minimal DLT, m > 4 findHomography(., ., 0) with the reference's rejection.
+ * H [count][9], ok [count] (0 = the normalisation refused the sample or the model was rejected). */
+int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *idx, int m, int count, double *H, int32_t *ok);
+
+/*
  * USAC essential-matrix estimation with the Nister minimal solver -- poselib::estimateEssentialOrPoseUSAC (pose_estim.h:212-223,
  * pose_estim.cpp:1737-2244) -> estimateEssentialMatUsac (source/usac/usac_estimations.cpp:283-735) -> USAC<EssentialMatEstimator>::solve
  * (include/usac/estimators/USAC.h:335-620, EssentialMatEstimator.h): PROSAC or uniform sampling, sample pre-validation, the oriented

@@ -102,6 +102,19 @@ _SIGNATURES = {
                                                 c_void_p, c_void_p]),
     "mlpl_arrsac_last_stats": (c_int, [c_void_p, c_void_p]),
     "mlpl_arrsac_sample_models": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_homography_arrsac": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_homography_arrsac_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_homography_inliers": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
+    "mlpl_homography_inliers_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_mult_homographies": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_u32, c_u32, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "mlpl_mult_homographies_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_u32, c_u32, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_mult_homographies_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_u32, c_u32, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_mult_homographies_labels_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_u32, c_u32, c_void_p, c_int, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_debug_homography_models": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "mlpl_robust_essential_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "mlpl_debug_arrsac_trace": (c_int, [c_void_p, c_void_p, c_int]),
     "mlpl_usac_default_params": (None, [c_void_p, c_double]),

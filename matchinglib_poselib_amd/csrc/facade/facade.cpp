@@ -168,6 +168,11 @@ std::mutex g_arrsac_mutex;
 uint64_t g_arrsac_rng[2] = {0xffffffffull, 0xffffffffull};  // cv::RNG's default state
 }  // namespace
 
+}  // namespace poselib
+mlpl_facade_arrsac_rng_lock::mlpl_facade_arrsac_rng_lock() : state(poselib::g_arrsac_rng) { poselib::g_arrsac_mutex.lock(); }
+mlpl_facade_arrsac_rng_lock::~mlpl_facade_arrsac_rng_lock() { poselib::g_arrsac_mutex.unlock(); }
+namespace poselib {
+
 void setArrsacRngState(uint64_t prosac_state, uint64_t uniform_state) {
     std::lock_guard<std::mutex> lock(g_arrsac_mutex);
     g_arrsac_rng[0] = prosac_state, g_arrsac_rng[1] = uniform_state;

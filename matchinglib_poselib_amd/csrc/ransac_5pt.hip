@@ -3315,6 +3315,7 @@ void hub_streams_free(void *p) {
     delete h;
 }
 #include "arrsac_impl.h"
+#include "homography_impl.h"
 #include "usac_impl.h"
 #include "pair_batch_impl.h"
 #include "pair_batch_usac.h"
@@ -4079,6 +4080,163 @@ int mlpl_arrsac_sample_models(mlpl_ctx *ctx, const double *p1, const double *p2,
     MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
     MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
     return arrsac_sample_models(ctx, (const double *)dp1, (const double *)dp2, n, idx, m, kind, thresh, E_out, n_models, valid, ctx->stream);
+}
+
+// ---- plane-induced homographies (homography_impl.h) ----
+static int homography_upload(mlpl_ctx *ctx, const double *p1, const double *p2, int n, void **dp1, void **dp2, void **dmask) {
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, dp1))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, dp2))) return rc;
+    if (dmask && (rc = ws_get(ctx, WS_MATCH, (size_t)n, dmask))) return rc;
+    MLPL_HIP_TRY(hipMemcpyAsync(*dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    MLPL_HIP_TRY(hipMemcpyAsync(*dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    return MLPL_OK;
+}
+
+int mlpl_homography_arrsac_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, uint64_t rng_state[2], double H[9],
+                               uint8_t *d_mask, int *n_inliers, long long stats[12], void *stream) {
+    if (!ctx || !d_p1 || !d_p2 || !H || !d_mask || !rng_state || n < 1 || !(th > 0) || !std::isfinite(th)) {
+        set_error("mlpl_homography_arrsac_dev: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    try {
+        return homography_arrsac_dev(ctx, d_p1, d_p2, n, th, rng_state, H, d_mask, n_inliers, stats, pick_stream(ctx, stream));
+    } catch (const std::bad_alloc &) {
+        set_error("mlpl_homography_arrsac_dev: out of host memory");
+        return MLPL_E_NOMEM;
+    }
+}
+
+int mlpl_homography_arrsac(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, uint64_t rng_state[2], double H[9], uint8_t *mask,
+                           int *n_inliers, long long stats[12]) {
+    if (!ctx || !p1 || !p2 || !H || !mask || !rng_state || n < 1 || !(th > 0) || !std::isfinite(th)) {
+        set_error("mlpl_homography_arrsac: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    void *dp1, *dp2, *dmask;
+    int rc;
+    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, &dmask))) return rc;
+    try {
+        rc = homography_arrsac_dev(ctx, (const double *)dp1, (const double *)dp2, n, th, rng_state, H, (uint8_t *)dmask, n_inliers, stats, ctx->stream);
+    } catch (const std::bad_alloc &) {
+        set_error("mlpl_homography_arrsac: out of host memory");
+        return MLPL_E_NOMEM;
+    }
+    if (rc) return rc;
+    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int mlpl_homography_inliers_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const double H[9], double th, uint8_t *d_mask,
+                                int *n_inliers, void *stream) {
+    if (!ctx || !d_p1 || !d_p2 || !H || !d_mask || n < 1 || !(th > 0)) {
+        set_error("mlpl_homography_inliers_dev: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    return homography_inliers_dev(ctx, d_p1, d_p2, n, H, th, d_mask, n_inliers, pick_stream(ctx, stream));
+}
+
+int mlpl_homography_inliers(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double H[9], double th, uint8_t *mask, int *n_inliers) {
+    if (!ctx || !p1 || !p2 || !H || !mask || n < 1 || !(th > 0)) {
+        set_error("mlpl_homography_inliers: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    void *dp1, *dp2, *dmask;
+    int rc;
+    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, &dmask))) return rc;
+    if ((rc = homography_inliers_dev(ctx, (const double *)dp1, (const double *)dp2, n, H, th, (uint8_t *)dmask, n_inliers, ctx->stream))) return rc;
+    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    return MLPL_OK;
+}
+
+static bool mult_homographies_args_ok(mlpl_ctx *ctx, const void *p1, const void *p2, int n, double th, const uint64_t *rng_state, int cap,
+                                      const int *n_planes, const double *H, const int32_t *num_inl, const double *strength, const double *th_used) {
+    return ctx && p1 && p2 && rng_state && n_planes && H && num_inl && strength && th_used && n >= 4 && cap >= 1 && th > 0 && std::isfinite(th);
+}
+
+int mlpl_mult_homographies_labels_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
+                                      unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl,
+                                      double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, uint8_t *d_masks, void *stream) {
+    if (!mult_homographies_args_ok(ctx, d_p1, d_p2, n, th, rng_state, cap, n_planes, H, num_inl, strength, th_used)) {
+        set_error("mlpl_mult_homographies_dev: bad arguments (n must exceed 3, cap 0)");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    try {
+        return mult_homographies_dev(ctx, d_p1, d_p2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H, num_inl, strength, th_used,
+                                     d_masks, d_labels, found_at, pick_stream(ctx, stream));
+    } catch (const std::bad_alloc &) {
+        set_error("mlpl_mult_homographies_dev: out of host memory");
+        return MLPL_E_NOMEM;
+    }
+}
+
+int mlpl_mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
+                               unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength,
+                               double *th_used, uint8_t *d_masks, void *stream) {
+    return mlpl_mult_homographies_labels_dev(ctx, d_p1, d_p2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H, num_inl, strength,
+                                             th_used, nullptr, nullptr, d_masks, stream);
+}
+
+// host pointers: the labels come back (n int32) and the masks of the planes FOUND are written from them -- no cap x n block anywhere
+int mlpl_mult_homographies_labels(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, int var_th, unsigned max_planes,
+                                  unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength,
+                                  double *th_used, int32_t *found_at, int32_t *labels, uint8_t *masks) {
+    if (!mult_homographies_args_ok(ctx, p1, p2, n, th, rng_state, cap, n_planes, H, num_inl, strength, th_used)) {
+        set_error("mlpl_mult_homographies: bad arguments (n must exceed 3, cap 0)");
+        return MLPL_E_BAD_INPUT;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    void *dp1, *dp2, *dlabels = nullptr;
+    int rc;
+    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
+    const bool want = labels || masks;
+    if (want && (rc = ws_get(ctx, WS_MATCH, (size_t)n * 4, &dlabels))) return rc;
+    try {
+        rc = mult_homographies_dev(ctx, (const double *)dp1, (const double *)dp2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H,
+                                   num_inl, strength, th_used, nullptr, (int32_t *)dlabels, found_at, ctx->stream);
+        if (rc || !want || *n_planes <= 0) return rc;
+        std::vector<int32_t> tmp;
+        int32_t *lab = labels;
+        if (!lab) tmp.resize((size_t)n), lab = tmp.data();
+        MLPL_HIP_TRY(hipMemcpy(lab, dlabels, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (masks) {
+            std::memset(masks, 0, (size_t)*n_planes * n);
+            for (int j = 0; j < n; ++j)
+                if (lab[j] >= 0 && lab[j] < *n_planes) masks[(size_t)lab[j] * n + j] = 1;
+        }
+    } catch (const std::bad_alloc &) {
+        set_error("mlpl_mult_homographies: out of host memory");
+        return MLPL_E_NOMEM;
+    }
+    return MLPL_OK;
+}
+
+int mlpl_mult_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, int var_th, unsigned max_planes, unsigned min_pts_per_plane,
+                           uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, double *th_used, uint8_t *masks) {
+    return mlpl_mult_homographies_labels(ctx, p1, p2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H, num_inl, strength, th_used,
+                                         nullptr, nullptr, masks);
+}
+
+int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *idx, int m, int count, double *H, int32_t *ok) {
+    if (!ctx || !p1 || !p2 || !idx || !H || !ok || n < 4 || m < 4 || m > 12 || count < 1 || count > 512) {
+        set_error("mlpl_debug_homography_models: bad arguments (4 <= m <= 12, 1 <= count <= 512)");
+        return MLPL_E_BAD_INPUT;
+    }
+    for (size_t i = 0; i < (size_t)m * count; ++i)
+        if (idx[i] < 0 || idx[i] >= n) {
+            set_error("mlpl_debug_homography_models: sample index out of range");
+            return MLPL_E_BAD_INPUT;
+        }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    void *dp1, *dp2;
+    int rc;
+    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
+    return homography_sample_models(ctx, (const double *)dp1, (const double *)dp2, n, idx, m, count, H, ok, ctx->stream);
 }
 
 int mlpl_robust_essential_refine(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask, const double E_init[9],

@@ -472,6 +472,151 @@ def arrsac_essential_device(p1, p2, thresh: float, refine: bool = True, rng_stat
     return dict(ok=(rc == 0), E=E, mask=mask_out, n_inliers=ninl.value)
 
 
+def _rng_pair(rng_state):
+    st = _arrsac_rng_state if rng_state is None else rng_state
+    assert st.dtype == np.uint64 and st.shape == (2,) and st.flags.c_contiguous
+    return st
+
+
+def homography_arrsac(p1, p2, th: float, rng_state=None, ctx: Optional[Context] = None) -> dict:
+    """poselib::computeHomographyArrsac (pose_homography.cpp:478-555): ARRSAC over the 4-point DLT, findHomographyInliers, refineHomography.
+    rng_state as in arrsac_essential: the SAME two cv::RNG streams (the reference's samplers are shared by both estimators).
+    ok = False is the reference's `false`."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    st = _rng_pair(rng_state)
+    H, mask, ninl, stats = np.zeros((3, 3)), np.zeros(max(n, 1), np.uint8), C.c_int(0), np.zeros(12, np.int64)
+    rc = ctx.lib.mlpl_homography_arrsac(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, float(th), st.ctypes.data, H.ctypes.data, mask.ctypes.data,
+                                        C.addressof(ninl), stats.ctypes.data)
+    if rc not in (0, _lib.MLPL_E_FAILED):
+        raise MlplError(rc, "mlpl_homography_arrsac", _lib.last_error())
+    return dict(ok=(rc == 0), H=H, mask=mask[:n], n_inliers=ninl.value, stats=stats)
+
+
+def homography_arrsac_device(p1, p2, th: float, rng_state=None, ctx: Optional[Context] = None, mask_out=None, stream: Optional[int] = None) -> dict:
+    """homography_arrsac on device-resident torch tensors (float64 [n,2]); the mask stays on the device."""
+    import torch
+
+    assert p1.is_cuda and p2.is_cuda and p1.dtype == torch.float64 and p1.is_contiguous() and p2.is_contiguous()
+    ctx = ctx or default_context(p1.device.index or 0)
+    n = p1.shape[0]
+    if mask_out is None:
+        mask_out = torch.empty(max(n, 1), dtype=torch.uint8, device=p1.device)
+    st = _rng_pair(rng_state)
+    H, ninl, stats = np.zeros((3, 3)), C.c_int(0), np.zeros(12, np.int64)
+    sm = torch.cuda.current_stream(p1.device).cuda_stream if stream is None else stream
+    rc = ctx.lib.mlpl_homography_arrsac_dev(ctx.handle, p1.data_ptr(), p2.data_ptr(), n, float(th), st.ctypes.data, H.ctypes.data,
+                                            mask_out.data_ptr(), C.addressof(ninl), stats.ctypes.data, sm)
+    if rc not in (0, _lib.MLPL_E_FAILED):
+        raise MlplError(rc, "mlpl_homography_arrsac_dev", _lib.last_error())
+    return dict(ok=(rc == 0), H=H, mask=mask_out[:n], n_inliers=ninl.value, stats=stats)
+
+
+def homography_inliers(p1, p2, H, th: float, ctx: Optional[Context] = None):
+    """findHomographyInliers (pose_homography.cpp:785-813): (mask, count) with mask[i] = transfer error <= th^2."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    H = np.ascontiguousarray(H, np.float64).reshape(3, 3)
+    mask, ninl = np.zeros(n, np.uint8), C.c_int(0)
+    check(ctx.lib.mlpl_homography_inliers(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, H.ctypes.data, float(th), mask.ctypes.data,
+                                          C.addressof(ninl)), "mlpl_homography_inliers")
+    return mask, ninl.value
+
+
+def _plane_cap(n: int, min_pts_per_plane: int, max_planes: int) -> int:
+    """The most planes a call can report: every one holds at least max(min_pts_per_plane, 1) correspondences of its own."""
+    cap = n // max(int(min_pts_per_plane), 1) + 1
+    return min(cap, int(max_planes)) if max_planes else cap
+
+
+def mult_homographies(p1, p2, th: float, var_th: bool = True, max_planes: int = 0, min_pts_per_plane: int = 4, rng_state=None, cap=None,
+                      want_masks: bool = True, ctx: Optional[Context] = None) -> dict:
+    """poselib::estimateMultHomographys (pose_homography.cpp:291-463): rc = 0 / -1 as the reference; the planes in its output order
+    (by inlier count, descending, when more than one was found); masks in the original indexing, built from one label per
+    correspondence (labels: output plane or -1); found_at: the round that found each plane (ascending = order of discovery).
+    cap (planes the arrays hold) defaults to the most a call can report."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    st = _rng_pair(rng_state)
+    cap = _plane_cap(n, min_pts_per_plane, max_planes) if cap is None else int(cap)
+    npl = C.c_int(0)
+    H, num, strength, thu = np.zeros((max(cap, 1), 3, 3)), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+    found, labels = np.zeros(max(cap, 1), np.int32), np.full(max(n, 1), -1, np.int32)
+    check(ctx.lib.mlpl_mult_homographies_labels(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, float(th), 1 if var_th else 0, int(max_planes),
+                                                int(min_pts_per_plane), st.ctypes.data, cap, C.addressof(npl), H.ctypes.data, num.ctypes.data,
+                                                strength.ctypes.data, thu.ctypes.data, found.ctypes.data,
+                                                labels.ctypes.data if want_masks else None, None), "mlpl_mult_homographies_labels")
+    k = max(npl.value, 0)
+    out = dict(rc=-1 if npl.value < 0 else 0, n_planes=k, H=H[:k].copy(), num_inl=num[:k].copy(), strength=strength[:k].copy(),
+               th_used=thu[:k].copy(), found_at=found[:k].copy())
+    if want_masks:
+        out["labels"] = labels[:n]
+        out["masks"] = (labels[None, :n] == np.arange(k, dtype=np.int32)[:, None]).astype(np.uint8)
+    return out
+
+
+def mult_homographies_device(p1, p2, th: float, var_th: bool = True, max_planes: int = 0, min_pts_per_plane: int = 4, rng_state=None, cap=None,
+                             ctx: Optional[Context] = None, stream: Optional[int] = None) -> dict:
+    """mult_homographies on device-resident torch tensors (float64 [n,2]); the labels ([n] int32) and the masks ([n_planes, n] uint8)
+    stay on the device."""
+    import torch
+
+    assert p1.is_cuda and p2.is_cuda and p1.dtype == torch.float64 and p1.is_contiguous() and p2.is_contiguous()
+    ctx = ctx or default_context(p1.device.index or 0)
+    n = p1.shape[0]
+    st = _rng_pair(rng_state)
+    cap = _plane_cap(n, min_pts_per_plane, max_planes) if cap is None else int(cap)
+    npl = C.c_int(0)
+    H, num, strength, thu = np.zeros((max(cap, 1), 3, 3)), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+    found = np.zeros(max(cap, 1), np.int32)
+    labels = torch.full((max(n, 1),), -1, dtype=torch.int32, device=p1.device)
+    sm = torch.cuda.current_stream(p1.device).cuda_stream if stream is None else stream
+    check(ctx.lib.mlpl_mult_homographies_labels_dev(ctx.handle, p1.data_ptr(), p2.data_ptr(), n, float(th), 1 if var_th else 0, int(max_planes),
+                                                    int(min_pts_per_plane), st.ctypes.data, cap, C.addressof(npl), H.ctypes.data, num.ctypes.data,
+                                                    strength.ctypes.data, thu.ctypes.data, found.ctypes.data, labels.data_ptr(), None, sm),
+          "mlpl_mult_homographies_labels_dev")
+    k = max(npl.value, 0)
+    masks = (labels[None, :n] == torch.arange(k, dtype=torch.int32, device=p1.device)[:, None]).to(torch.uint8)
+    return dict(rc=-1 if npl.value < 0 else 0, n_planes=k, H=H[:k].copy(), num_inl=num[:k].copy(), strength=strength[:k].copy(),
+                th_used=thu[:k].copy(), found_at=found[:k].copy(), labels=labels[:n], masks=masks)
+
+
+def homography_sample_models(p1, p2, idx, ctx: Optional[Context] = None):
+    """mlpl_debug_homography_models: the device's estimator on index lists idx [count, m] -> (H [count,3,3], ok [count])."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    idx = np.ascontiguousarray(np.atleast_2d(idx), np.int32)
+    count, m = idx.shape
+    H, ok = np.zeros((count, 3, 3)), np.zeros(count, np.int32)
+    check(ctx.lib.mlpl_debug_homography_models(ctx.handle, p1.ctypes.data, p2.ctypes.data, p1.shape[0], idx.ctypes.data, m, count, H.ctypes.data,
+                                               ok.ctypes.data), "mlpl_debug_homography_models")
+    return H, ok
+
+
+def computeHomographyArrsac(points1, points2, th: float, ctx: Optional[Context] = None):
+    """The reference's signature in Python: (ok, H, mask, p_filtered1, p_filtered2); the process-wide stream pair, as its statics."""
+    p1, p2 = _pts(points1), _pts(points2)
+    r = homography_arrsac(p1, p2, th, ctx=ctx)
+    if not r["ok"]:
+        return False, None, None, None, None
+    keep = r["mask"].astype(bool)
+    return True, r["H"], r["mask"], p1[keep], p2[keep]
+
+
+def estimateMultHomographys(p1, p2, th: float, varTh: bool = True, maxPlanes: int = 0, minPtsPerPlane: int = 4, ctx: Optional[Context] = None):
+    """The reference's signature in Python: (rc, inl_mask, inl_points, Hs, num_inl, planeStrength) as lists, rc = 0 / -1."""
+    p1, p2 = _pts(p1), _pts(p2)
+    r = mult_homographies(p1, p2, th, var_th=varTh, max_planes=maxPlanes, min_pts_per_plane=minPtsPerPlane, ctx=ctx)
+    if r["rc"]:
+        return -1, [], [], [], [], []
+    masks = [m for m in r["masks"]]
+    pts = [(p1[m.astype(bool)], p2[m.astype(bool)]) for m in masks]
+    return 0, masks, pts, [h for h in r["H"]], [int(v) for v in r["num_inl"]], [float(v) for v in r["strength"]]
+
+
 def estimateEssentialMat(p1, p2, method: str = "ARRSAC", threshold: float = PIX_MIN_GOOD_TH, refine: bool = True,
                          seed: Optional[int] = None, ctx: Optional[Context] = None):
     """poselib::estimateEssentialMat (pose_estim.h:204-210, pose_estim.cpp:857-890) -> (ok, E, mask).

@@ -97,6 +97,12 @@ int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]);
  * 0 = the per-candidate update (every other kernel, and every call the option does not apply to). */
 int mlpl_debug_last_hamming_top2(mlpl_ctx *ctx);
 
+/* Diagnostics: the train rows per block of the instance the last knn_hamming call really ran: 8 = the 16x16x128 form of the throughput instance
+ * (a block is a lane's eight accumulator registers of a tile: rows T + 16 h + 4 g + i, h < 2, i < 4), 4 = the 32x32x64 in-kernel-expansion
+ * instances with "hamming_block_top2" = 4 (aligned groups of four rows), 0 = the per-candidate update.  The option and
+ * mlpl_debug_last_hamming_top2 keep their values (0 | 4) and their meaning: block maxima in the loop. */
+int mlpl_debug_last_hamming_block_rows(mlpl_ctx *ctx);
+
 /* Diagnostics: the matrix-core shape the last knn_hamming call really used (option "hamming_mfma_shape"): 16 = the 16x16x128 form of the
  * throughput instance of the static ring kernel, 32 = every other matrix-core kernel (and every call the option does not apply to), 0 = a
  * VALU kernel. */

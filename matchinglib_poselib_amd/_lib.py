@@ -143,6 +143,7 @@ _SIGNATURES = {
     "mlpl_debug_last_kernels": (c_int, [c_void_p, c_void_p]),
     "mlpl_debug_last_hamming_top2": (c_int, [c_void_p]),
     "mlpl_debug_last_hamming_shape": (c_int, [c_void_p]),
+    "mlpl_debug_last_hamming_block_rows": (c_int, [c_void_p]),
     "mlpl_debug_count_pass": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_int,
                                       c_void_p]),
     "mlpl_pair_pose_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
@@ -332,6 +333,13 @@ class Context:
         n = self._lib.mlpl_debug_last_hamming_shape(self._h)
         if n < 0:
             raise MlplError(n, "mlpl_debug_last_hamming_shape", last_error())
+        return n
+
+    def last_hamming_block_rows(self) -> int:
+        """mlpl_debug_last_hamming_block_rows (include/mlpl_debug.h): train rows per block of the Hamming instance that ran last (0, 4 or 8)."""
+        n = self._lib.mlpl_debug_last_hamming_block_rows(self._h)
+        if n < 0:
+            raise MlplError(n, "mlpl_debug_last_hamming_block_rows", last_error())
         return n
 
     def last_l2_match(self) -> list:

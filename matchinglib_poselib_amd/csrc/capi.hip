@@ -381,6 +381,7 @@ int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]) {
 
 int mlpl_debug_last_hamming_top2(mlpl_ctx *ctx) { return ctx ? ctx->dbg_hamming_top2 : MLPL_E_BAD_INPUT; }
 int mlpl_debug_last_hamming_shape(mlpl_ctx *ctx) { return ctx ? ctx->dbg_hamming_shape : MLPL_E_BAD_INPUT; }
+int mlpl_debug_last_hamming_block_rows(mlpl_ctx *ctx) { return ctx ? ctx->dbg_hamming_block_rows : MLPL_E_BAD_INPUT; }
 
 int mlpl_debug_last_l2_match(mlpl_ctx *ctx, int out[4]) {
     if (!ctx || !out) return MLPL_E_BAD_INPUT;

@@ -524,6 +524,7 @@ int launch_knn_hamming(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_strid
         rec[0] = variant, rec[1] = (variant == 1 && nw <= 16) ? qpl : 1, rec[2] = 0, rec[3] = 0, rec[4] = 0;
         rec[5] = 0, rec[6] = 0, rec[7] = 0, rec[8] = nsplit, rec[9] = 0, rec[10] = 0;
         ctx->dbg_hamming_top2 = 0;
+        ctx->dbg_hamming_block_rows = 0;
         ctx->dbg_hamming_shape = 0;
     }
     prof_mark(ctx, MLPL_PROF_KNN_HAMMING, 0, s);

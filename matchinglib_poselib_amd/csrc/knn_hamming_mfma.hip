@@ -59,6 +59,12 @@ static_assert(kAccBias == (float)(int)kAccBias, "the bias is an integer: rint() 
 static_assert(kAccBias + 256.0f + (float)(kMaxRowsPerSplit - 32) / 16384.0f < 1024.0f, "largest value (identical rows, last tile) below 2^10: 2^-14 is exact");
 static_assert(kAccBias - 256.0f - 31.0f / 16384.0f > -1024.0f, "smallest value (complementary rows) above -2^10");
 static_assert(kAccBias - 64.0f >= 512.0f && kAccBias + 64.0f < 1024.0f, "typical data (|I| <= 64) stay inside the binade [512, 1024)");
+// The 16x16x128 instance carries the ABSOLUTE row of the split in C instead of re-basing its running pairs: a value, final or partial sum of a
+// chain, is kAccBias + I - r * 2^-14 with |I| <= 256 and r in [0, kMaxRowsPerSplit - 1] -- magnitude below 2^10, fraction inside (-1/2, 0], so
+// rint() returns kAccBias + I and the decode reads the row from the fraction with frame 0 (tests/test_hamming_shape16_fit_rule.py: every (I, r)).
+static_assert(kAccBias + 256.0f < 1024.0f && kAccBias - 256.0f - (float)(kMaxRowsPerSplit - 1) / 16384.0f > -1024.0f, "absolute rows: magnitude below 2^10");
+static_assert((float)(kMaxRowsPerSplit - 1) / 16384.0f < 0.5f, "absolute rows: the fraction stays inside (-1/2, 0]");
+static_assert(kAccBias - 64.0f - (float)(kMaxRowsPerSplit - 1) / 16384.0f >= 512.0f, "absolute rows: typical data stay inside the binade [512, 1024)");
 
 __device__ __forceinline__ float fmax_raw(float a, float b) {
     float r;
@@ -1000,22 +1006,20 @@ __global__ __launch_bounds__(64 * NW, 4) void knn_hamming_mfma_lds_kernel(
 //     (row half rh) of K-half kh.  Expansion wave w (word w: kh = w >> 2, g = w & 3) still reads row l >> 1 and forms the plane pair l & 1; it
 //     writes two contiguous 256-byte runs (rh = 0, 1) instead of one of 512.
 //   * Queries: group u = 0..7 of a wave is queries 32 qt0 + 16 u + (l & 15); bq[u][kh] = the planes of word 4 kh + g.  64 registers as above.
-//   * Tile arithmetic per group: two chains of two (one per row half) on 4-register accumulators, interleaved; a lane's four registers of
-//     chain rh are rows 16 rh + 4 g + 0..3 = one aligned block of four of the block rule, so g_rh = max4(c_rh), s = med3(m1, g0, g1),
-//     m1 = max3(m1, g0, g1), m2 = max(m2, s): 7 ops per group, one (c0, c1) pair alive at a time.
-//   * Period of two tiles: the unrolled pair re-bases the running pair ONCE, by 64 eps in front of its first tile, and the chains of its
-//     two tiles start 32 eps apart (cinit[0] = kAccBias + (32 - lr) eps, cinit[1] = kAccBias - lr eps): every value then reads
-//     kAccBias + I + (frame - row) eps with frame = the first row of the pair's SECOND tile, which is what the decode expects.  The rolled tail
-//     re-bases by 32 eps per tile and uses cinit[1].  Fractions and magnitudes are those of the kernel above (static_asserts at kAccBias).
-//   * Epilogue: a query's keys sit in four lanes (l & 15 equal): top-2 across xor 16 and xor 32; the best row's block is re-scored with one
-//     row per lane; lanes of group 0 write; a group of 64 queries = four groups u.
+//   * Tile arithmetic per group: two chains of two (one per row half) on 4-register accumulators, interleaved; a lane's eight registers of
+//     the two chains -- rows 16 rh + 4 g + 0..3, rh = 0, 1 -- are ONE block of the block rule: g = max8(c0, c1) (three v_max3 and a v_max),
+//     m2 = med3(m1, m2, g), m1 = max(m1, g): 6 ops per group, one (c0, c1) pair alive at a time.
+//   * Absolute rows: C carries the row within the split, cinit = kAccBias - (32 t + lr) eps for tile t, advanced by -32 eps per tile with four
+//     v_pk_add_f32 per wave (all eight groups read it); the running pairs are never re-based and the decode reads the row with frame 0.
+//     Magnitudes and fractions: static_asserts at kAccBias.  The ragged tile takes its C from the same running value (rows >= nt: -inf).
+//   * Epilogue: a query's keys sit in four lanes (l & 15 equal): top-2 across xor 16 and xor 32; the seven other rows of the best row's block
+//     are re-scored, two rows per lane (block_rescan8); lanes of group 0 write; a group of 64 queries = four groups u.
 // The MFMAs of a group are written out (the compiler's scheduler puts a chain's two dependent MFMAs back to back); s_nop 7 is the wait the
-// compiler itself inserts between this opcode and a VALU read of its result.  The fold keeps the running pair tied to its registers: left
-// to the compiler the pair's two folds merge into a v_max3 over both tiles and the re-base adds into v_pk_add_f32 over neighbouring groups,
-// and the copies that needs do not fit in 128 registers (tools/hamming_unit_probe6.hip).
+// compiler itself inserts between this opcode and a VALU read of its result.  The fold keeps the running pair tied to its registers
+// (tools/hamming_unit_probe6.hip, tools/hamming_unit_probe7.hip).
 // ---------------------------------------------------------------------------------------------------------------------------------
 typedef float v4f __attribute__((ext_vector_type(4)));
-static_assert(kAccBias + 256.0f + 32.0f / 16384.0f < 1024.0f, "a chain of a pair's first tile starts 32 eps higher: still below 2^10");
+typedef float v2f __attribute__((ext_vector_type(2)));
 
 // The fused merge of the kernel above (HammingFuse with nsplit > 1: its text, as a function), called by every thread of a workgroup behind
 // its partial stores.  QPB = the queries of a workgroup's block, THREADS = its threads; tid_end = the thread's index, le = its lane.
@@ -1089,17 +1093,13 @@ __device__ __forceinline__ void mfma16_group(const u32x4 (&a)[4], const u32x4 &q
                  : "=&v"(c0), "=&v"(c1)
                  : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(q0), "v"(q1), "v"(ci0), "v"(ci1));
 }
-// the block maxima of a group's two row halves folded into its running pair, re-based by `step` first (REBASE)
-template <bool REBASE>
-__device__ __forceinline__ void top2_update_halves(float &m1, float &m2, const v4f &c0, const v4f &c1, float step) {
-    const float g0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(c0[0], c0[1]), c0[2]), c0[3]);
-    const float g1 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(c1[0], c1[1]), c1[2]), c1[3]);
-    float sec;
-    if constexpr (REBASE)
-        asm volatile("v_add_f32 %0, %5, %0\n\tv_add_f32 %1, %5, %1\n\tv_med3_f32 %2, %0, %3, %4\n\tv_max3_f32 %0, %0, %3, %4\n\tv_max_f32 %1, %1, %2"
-                     : "+v"(m1), "+v"(m2), "=&v"(sec) : "v"(g0), "v"(g1), "s"(step));
-    else
-        asm volatile("v_med3_f32 %2, %0, %3, %4\n\tv_max3_f32 %0, %0, %3, %4\n\tv_max_f32 %1, %1, %2" : "+v"(m1), "+v"(m2), "=&v"(sec) : "v"(g0), "v"(g1));
+// the maximum of a group's block -- the lane's eight registers of both row halves: three v_max3 and a v_max -- folded into its running pair
+__device__ __forceinline__ void top2_update_halves(float &m1, float &m2, const v4f &c0, const v4f &c1) {
+    float g = __builtin_fmaxf(__builtin_fmaxf(c0[0], c0[1]), c0[2]);
+    g = __builtin_fmaxf(__builtin_fmaxf(g, c0[3]), c1[0]);
+    g = __builtin_fmaxf(__builtin_fmaxf(g, c1[1]), c1[2]);
+    g = __builtin_fmaxf(g, c1[3]);
+    asm volatile("v_med3_f32 %1, %0, %1, %2\n\tv_max_f32 %0, %0, %2" : "+v"(m1), "+v"(m2) : "v"(g));
 }
 // a query's keys sit in the four lanes with equal l & 15 (disjoint rows): top-2 of the eight keys, in all four lanes
 __device__ __forceinline__ uint2 top2_across_groups(const uint32_t (&k)[2]) {
@@ -1114,17 +1114,30 @@ __device__ __forceinline__ uint2 top2_across_groups(const uint32_t (&k)[2]) {
     }
     return make_uint2(k0, k1);
 }
-// block_rescan with the four lanes of a query taking one row each (g = the lane's group)
-__device__ __forceinline__ uint32_t block_rescan4(uint32_t k0, const uint32_t (&q8)[8], const char *rbase, int rows, int dshift, int g) {
+// block_rescan for the block of eight (a lane's eight accumulator registers of a tile: rows T + 16 h + 4 (lane >> 4) + i, h < 2, i < 4): the
+// four lanes of a query take i = their group g in both row halves, two rows each; same exclusions, same clamp
+__device__ __forceinline__ uint32_t block_rescan8(uint32_t k0, const uint32_t (&q8)[8], const char *rbase, int rows, int dshift, int g) {
     const uint32_t lmask = (1u << dshift) - 1u;
     const int best = (int)(k0 & lmask);
-    const int r = (best & ~3) + g;
-    const RawRow t = *reinterpret_cast<const RawRow *>(rbase + (size_t)min(r, rows - 1) * 32);
-    int d = 0;
+    uint32_t res = 0xFFFFFFFFu;
+    uint32_t t2[2][8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) d += __popc(t.w[j] ^ q8[j]);
-    const uint32_t key = ((uint32_t)d << dshift) | (uint32_t)r;
-    uint32_t res = (r != best && r < rows && k0 != 0xFFFFFFFFu) ? key : 0xFFFFFFFFu;
+    for (int h = 0; h < 2; ++h) {
+        const RawRow t = *reinterpret_cast<const RawRow *>(rbase + (size_t)min((best & ~19) + 16 * h + g, rows - 1) * 32);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t2[h][j] = t.w[j];
+    }
+    // (both rows arrive behind one wait: left alone the compiler sinks each load under its row's own condition)
+    asm volatile("" ::"v"(t2[0][0]), "v"(t2[0][4]), "v"(t2[1][0]), "v"(t2[1][4]));
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int r = (best & ~19) + 16 * h + g;
+        int d = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d += __popc(t2[h][j] ^ q8[j]);
+        const uint32_t key = ((uint32_t)d << dshift) | (uint32_t)r;
+        res = (r != best && r < rows && k0 != 0xFFFFFFFFu) ? min(res, key) : res;
+    }
     res = min(res, (uint32_t)__shfl_xor(res, 16));
     return min(res, (uint32_t)__shfl_xor(res, 32));
 }
@@ -1148,13 +1161,11 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
     const int qt0 = (qb * NW + w) * QT;
 
     u32x4 bq[NG][2];   // the wave's query fragments (filled below, behind the first tile copies)
-    v4f cinit[2][2];   // [tile of a pair][row half]
+    v4f cinit[2];   // [row half]: kAccBias - (row within the split) * eps of the tile to come, advanced by -32 eps per tile
 #pragma unroll
-    for (int J = 0; J < 2; ++J)
+    for (int rh = 0; rh < 2; ++rh)
 #pragma unroll
-        for (int rh = 0; rh < 2; ++rh)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cinit[J][rh][i] = kAccBias + (float)((J == 0 ? 32 : 0) - (16 * rh + 4 * (l >> 4) + i)) * kEps;
+        for (int i = 0; i < 4; ++i) cinit[rh][i] = kAccBias - (float)(16 * rh + 4 * (l >> 4) + i) * kEps;
 
     int row0 = split * rows_per_split;
     int row1 = min(nt, row0 + rows_per_split);
@@ -1168,6 +1179,8 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
     float m1[NG], m2[NG];
 #pragma unroll
     for (int u = 0; u < NG; ++u) m1[u] = m2[u] = -INFINITY;
+    v2f pk_step = {-32.0f * kEps, -32.0f * kEps};   // (in a scalar register pair: v_pk_add_f32 takes no literal)
+    asm volatile("" : "+s"(pk_step));
 
     const char *rbase = (const char *)tsrc + ((size_t)b * t_batch + (size_t)tile0 * 32 * (2 * KS)) * 4;   // wave-uniform
     const uint32_t raw_last = (uint32_t)(nt - row0) * (8u * KS) - 4u;   // byte offset of the pair's last train word behind rbase
@@ -1198,18 +1211,21 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
         const uint32_t y = x >> __builtin_amdgcn_ubfe(xp_plane, 3u, 1u);   // dwords 0, 1 = planes 0, 2; dwords 2, 3 = planes 1, 3
         return u32x2{expand_plane0(y, 0x22222222u), expand_plane2(y, 0x22222222u)};
     };
-    // the arithmetic of one tile: r[] = the tile's four fragments; rebase = what the running pairs are re-based by first (0: not at all)
-    auto tile_math = [&](const u32x4 (&r)[KS], const v4f (&c)[2], auto rebase) {
-        constexpr int RB = decltype(rebase)::value;
+    // the arithmetic of one tile: r[] = the tile's four fragments, c = the tile's C, left as the next tile's
+    auto tile_math = [&](const u32x4 (&r)[KS], v4f (&c)[2]) {
 #pragma unroll
         for (int u = 0; u < NG; ++u) {
             v4f c0, c1;
             mfma16_group(r, bq[u][0], bq[u][1], c[0], c[1], c0, c1);
-            top2_update_halves<RB != 0>(m1[u], m2[u], c0, c1, (float)RB * kEps);
+            top2_update_halves(m1[u], m2[u], c0, c1);
             __builtin_amdgcn_sched_barrier(0);   // (one (c0, c1) pair alive at a time)
         }
+        // the next tile's rows: 32 further into the split (four v_pk_add_f32 per wave and tile, for all eight groups)
+        const v2f st = pk_step;
+        asm volatile("v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %2" : "+v"(c[0].lo), "+v"(c[0].hi) : "s"(st));
+        asm volatile("v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %2" : "+v"(c[1].lo), "+v"(c[1].hi) : "s"(st));
     };
-    auto tile_body = [&](int it, const v4f (&c)[2]) {
+    auto tile_body = [&](int it, v4f (&c)[2]) {
         u32x4 r[KS];
         uint32_t x;
         const uint32_t addr = xp_frag + (uint32_t)(it & 1) * (KS * 1024u);
@@ -1228,7 +1244,7 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
         asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
         asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
         asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
-        tile_math(r, c, std::integral_constant<int, 32>{});
+        tile_math(r, c);
     };
 
 #pragma unroll
@@ -1258,7 +1274,7 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
         asm volatile("ds_write_b64 %0, %1" ::"v"(plane_addr(0)), "v"(o) : "memory");
     }
 
-    // only the last tile of the train set can be ragged; it runs after the loop with its own C (rows >= nt start at -inf and stay there)
+    // only the last tile of the train set can be ragged; it runs after the loop with the running C, rows >= nt set to -inf (they stay there)
     const bool ragged = row0 + ntiles * 32 > nt;
     const int nfull = ragged ? ntiles - 1 : ntiles;
     auto arrive = [&](int it) {
@@ -1300,7 +1316,7 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
             asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r[1]));
             asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r[2]));
             asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r[3]));
-            tile_math(r, cinit[J], std::integral_constant<int, J == 0 ? 64 : 0>{});
+            tile_math(r, cinit);
         };
         auto run_pairs = [&](auto copier) {
             while (it + 3 < nfull) {
@@ -1318,7 +1334,7 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
     }
     for (; it < nfull; ++it) {
         arrive(it);
-        tile_body(it, cinit[1]);
+        tile_body(it, cinit);
     }
     // what follows the tile loop forms the lane and thread indices anew (see the kernel above)
     const int l_end = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -1330,15 +1346,15 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int lr = 16 * rh + 4 * (l_end >> 4) + i;
-                cinit[1][rh][i] = (row0 + nfull * 32 + lr < nt) ? kAccBias - (float)lr * kEps : -INFINITY;
+                cinit[rh][i] = (row0 + nfull * 32 + lr < nt) ? cinit[rh][i] : -INFINITY;
             }
-        tile_body(nfull, cinit[1]);
+        tile_body(nfull, cinit);
     }
 
     int le = l_end, qt0e = qt0;
     asm volatile("" : "+v"(le), "+s"(qt0e));
     const int ge = le >> 4;
-    const float frame = (float)(32 * (ntiles - 1));
+    const float frame = 0.0f;   // (C carries the row within the split)
     int pass_acc = 0;
 #pragma unroll
     for (int u = 0; u < NG; ++u) {
@@ -1358,7 +1374,7 @@ __global__ __launch_bounds__(64 * 8, 4) void knn_hamming_mfma_lds16_kernel(
                 const uint4 v0 = qp[0], v1 = qp[1];
                 q8[0] = v0.x, q8[1] = v0.y, q8[2] = v0.z, q8[3] = v0.w, q8[4] = v1.x, q8[5] = v1.y, q8[6] = v1.z, q8[7] = v1.w;
             }
-            k1 = min(k1, block_rescan4(k0, q8, rbase, nt - row0, dshift, ge));
+            k1 = min(k1, block_rescan8(k0, q8, rbase, nt - row0, dshift, ge));
         }
         if (fuse.idx && nsplit == 1) {  // the final top-2 of the query: outputs straight from the registers
             const uint32_t lmask = (1u << dshift) - 1u;
@@ -1733,6 +1749,7 @@ int launch_knn_hamming_mfma(mlpl_ctx *ctx, const uint32_t *qw, size_t q_batch_wo
     // matrix-core shape (option hamming_mfma_shape): the 16x16x128 form exists for the throughput instance without the stamps trace only
     const int shape = (inkernel && block_top2 == 4 && ctx->opt_hamming_stamps != 1 && ctx->opt_hamming_mfma_shape == 16) ? 16 : 32;
     ctx->dbg_hamming_shape = shape;
+    ctx->dbg_hamming_block_rows = shape == 16 ? 8 : block_top2;   // (the 16 shape folds a lane's eight registers of a tile as one block)
 
     void *qf = nullptr, *tf = nullptr, *part = nullptr;
     int rc;

@@ -145,6 +145,7 @@ struct mlpl_ctx {
     int opt_hamming_mfma_shape;        // 32 = v_mfma_f32_32x32x64_f8f6f4 everywhere; 16 = the throughput instance of the static ring kernel (eight waves, in-kernel expansion, block update, no stamps trace) runs on 16x16x128 (same results)
     int dbg_hamming_shape;             // MFMA shape the last Hamming launch really used (mlpl_debug_last_hamming_shape; 0 = a VALU kernel)
     int dbg_hamming_top2;              // block size the last Hamming launch really used (mlpl_debug_last_hamming_top2)
+    int dbg_hamming_block_rows;        // train rows per block of the instance that ran: 0, 4, or 8 in the 16x16x128 form (mlpl_debug_last_hamming_block_rows)
     void *subpix_sep_mask_ptr;      // the WS_SUBPIX_SEP_MASK block that holds the mask profiles of subpix_separate.hip
     int dbg_stamp_items;
     // diagnostics (mlpl_debug_last_kernels): what the last launches chose -- {count instance code, its point splits} of the last

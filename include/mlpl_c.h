@@ -583,6 +583,29 @@ int mlpl_mult_homographies_labels(mlpl_ctx *ctx, const double *p1, const double 
 int mlpl_mult_homographies_labels_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
                                       unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl,
                                       double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, uint8_t *d_masks, void *stream);
+/* Batches of the two plane estimators in one call, laid out as mlpl_arrsac_essential_batch_dev: problem b = correspondences d_p1 / d_p2 +
+ * b * stride * 2 doubles (device), counts[b] in [0, stride] of them (host), its own pair of cv::RNG states rng_states[2 b], [2 b + 1] (host,
+ * in / out).  Every problem runs the sequential program of the single entry on its own stack (a fiber on a worker thread) and the launches
+ * of all runs that stand at the same point of their control flow are merged into one launch per kernel (csrc/batch_hub.h), 128 problems
+ * at a time; the options hub_cohort, hub_lanes, hub_workers and hub_blocking_sync apply.  Every problem's outputs are byte for byte what
+ * mlpl_homography_arrsac_dev / mlpl_mult_homographies_labels_dev returns for it alone with the same stream states.
+ * mlpl_homography_arrsac_batch_dev: per problem status[b] (0; MLPL_E_FAILED = the reference's `false`, counts[b] < 4 included, with the
+ * stream states as the single entry leaves them), H + 9 b, n_inliers[b], its mask at d_masks + b * stride (device), stats + 12 b (stats may
+ * be NULL).
+ * mlpl_mult_homographies_batch_dev: per problem n_planes[b] (-1 = the reference's -1, with status[b] = 0; counts[b] < 4: -1 with status[b]
+ * = MLPL_E_FAILED and the stream states untouched) and cap planes each of H [b][cap][9], num_inl, strength, th_used, found_at [b][cap]
+ * (found_at may be NULL), labels at d_labels + b * stride (device, may be NULL), plane indices in the reference's output order.
+ * Any other negative status[b] ends the call, which returns the first such code with its message (the message names the problem): finding
+ * more than cap planes in a problem is MLPL_E_BAD_INPUT with that problem's stream states put back.  A malformed call (null required
+ * pointers, n_problems < 0, stride < 1, a counts[b] outside [0, stride], th not positive and finite, cap < 1) is MLPL_E_BAD_INPUT with
+ * nothing launched; n_problems == 0 returns 0.  After a batch mlpl_arrsac_last_stats [8] / [9] hold the hub's rounds / merged launches. */
+int mlpl_homography_arrsac_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                     uint64_t *rng_states, double *H, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, long long *stats,
+                                     void *stream);
+int mlpl_mult_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                     int var_th, unsigned max_planes, unsigned min_pts_per_plane, uint64_t *rng_states, int cap, int32_t *n_planes,
+                                     double *H, int32_t *num_inl, double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, int32_t *status,
+                                     void *stream);
 /* The homography estimators on `count` samples of m indices each (idx [count][m], 4 <= m <= 12), a building block exposed for parity
  * tests (the twin of mlpl_arrsac_sample_models): m == 4 the minimal DLT, m > 4 findHomography(., ., 0) with the reference's rejection.
  * H [count][9], ok [count] (0 = the normalisation refused the sample or the model was rejected). */

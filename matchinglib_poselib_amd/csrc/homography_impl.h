@@ -6,7 +6,11 @@
 // (pose_homography.cpp:505): minimal sample 4, at most 500 hypotheses, blocks of 100, inner RANSAC on min(12, max_inl / 2) points with the
 // non-minimal estimator unless that size is 4.  ONE model per sample.  As for E, the host runs the reference's control flow literally on
 // inlier bit rows and sends the samples it will need to the device in speculative batches (arrsac_impl.h explains why a wrong guess costs a
-// batch and never a result).  All arithmetic is fp64; no matrix cores; direct launches on the caller's stream (no batch hub).
+// batch and never a result).  All arithmetic is fp64; no matrix cores.  Every kernel is a body(const Args &, block x, block y) registered with
+// MLPL_HUB_KERNEL (batch_hub.h): a run issues its launches through a Launcher, which launches on the caller's stream (a call alone) or records
+// them for the hub (mlpl_homography_arrsac_batch_dev / mlpl_mult_homographies_batch_dev: every problem a fiber, the launches of the runs at
+// the same point of their control flow merged, blockIdx.z = the run).  Both instantiations come from the one body, so a problem's results
+// do not depend on how it was launched.  The kernels (homog_<name>_body in the code, HK_HOM_* in hub_kernels.h):
 //   homog_sample_kernel   one wave per sample: runHomogrophyKernel (:674-744) -- centroid / mean absolute deviation, LtL summed in the
 //                         reference's point order, eigenvector of the smallest eigenvalue (jacobi9_wave), denormalise, scale by 1 / H(2,2);
 //                         samples of more than 4 points are cv::findHomography(m1, m2, 0): float32 points, the same DLT, LMSolver's 10
@@ -220,14 +224,26 @@ __device__ __noinline__ void hom_lm_polish(const double (*pts)[4], int m, double
 
 // One wave per sample: smp[b] = {m, idx[1..14], kind} (ArrKey's layout); H_out[b][9], ok_out[b].  The host has checked 4 <= m <= 12 and
 // every index against n.
-__global__ __launch_bounds__(64) void homog_sample_kernel(const double *__restrict__ p1, const double *__restrict__ p2, const int32_t *__restrict__ smp,
-                                                          int n_samples, double *__restrict__ H_out, int32_t *__restrict__ ok_out) {
+struct HomSampleArgs {
+    KHdr hdr;
+    const double *p1, *p2;
+    const int32_t *smp;
+    int n_samples;
+    double *H_out;
+    int32_t *ok_out;
+};
+__device__ __forceinline__ void homog_sample_body(const HomSampleArgs &a, int bx, int) {
+    const double *__restrict__ p1 = a.p1, *__restrict__ p2 = a.p2;
+    const int32_t *__restrict__ smp = a.smp;
+    double *__restrict__ H_out = a.H_out;
+    int32_t *__restrict__ ok_out = a.ok_out;
+    const int n_samples = a.n_samples;
     __shared__ Jacobi9Lds J;
     __shared__ HomLmLds W;
     __shared__ double xs[kHomMaxSample][4];  // {Mx, My, mx, my}
     __shared__ double nrm[8];                // cM, sM, cm, sm (x, y each)
     __shared__ int s_ok;
-    const int lane = threadIdx.x, b = blockIdx.x;
+    const int lane = threadIdx.x, b = bx;
     if (b >= n_samples) return;
     const int32_t *sm = smp + (size_t)b * kArrSmpStride;
     const int m = sm[0];
@@ -295,17 +311,33 @@ __global__ __launch_bounds__(64) void homog_sample_kernel(const double *__restri
         ok_out[b] = ok;
     }
 }
+MLPL_HUB_KERNEL(HK_HOM_SAMPLE, HomSampleArgs, homog_sample_body, 64);
 
-__global__ void homog_pack_kernel(const double *__restrict__ p1, const double *__restrict__ p2, int n, double4 *__restrict__ pts) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) pts[i] = make_double4(p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
+struct HomPackArgs {  // 256 threads per block
+    KHdr hdr;
+    const double *p1, *p2;
+    int n;
+    double4 *pts;
+};
+__device__ __forceinline__ void homog_pack_body(const HomPackArgs &a, int bx, int) {
+    const int i = bx * 256 + threadIdx.x;
+    if (i < a.n) a.pts[i] = make_double4(a.p1[2 * i], a.p1[2 * i + 1], a.p2[2 * i], a.p2[2 * i + 1]);
 }
+MLPL_HUB_KERNEL(HK_HOM_PACK, HomPackArgs, homog_pack_body, 256);
 // the winner's matrix and the counts of the inlier pass, for the host (mapped block)
-__global__ void homog_final_kernel(const double *__restrict__ H, const int32_t *__restrict__ counts, double *__restrict__ H_out, int32_t *__restrict__ counts_out) {
+struct HomFinalArgs {
+    KHdr hdr;
+    const double *H;
+    const int32_t *counts;
+    double *H_out;
+    int32_t *counts_out;
+};
+__device__ __forceinline__ void homog_final_body(const HomFinalArgs &a, int, int) {
     const int t = threadIdx.x;
-    if (t < 9) H_out[t] = H[t];
-    if (t < 2) counts_out[t] = counts[t];
+    if (t < 9) a.H_out[t] = a.H[t];
+    if (t < 2) a.counts_out[t] = a.counts[t];
 }
+MLPL_HUB_KERNEL(HK_HOM_FINAL, HomFinalArgs, homog_final_body, 64);
 
 // ArrHomogrophyEstimator::Error (pose_homography.cpp:642-663)
 __device__ __forceinline__ double hom_transfer_err(const double *H, double Mx, double My, double mx, double my) {
@@ -317,10 +349,26 @@ __device__ __forceinline__ double hom_transfer_err(const double *H, double Mx, d
 
 // One wave per model: bit i of its row = Error(i) < thresh2 for i < flag_points <= 1024 (16 ballot words, the layout of arrsac_check_kernel);
 // the rows and the validity words go straight to the mapped host block.
-__global__ __launch_bounds__(64) void homog_check_kernel(const double4 *__restrict__ pts, int flag_points, const double *__restrict__ H_tab,
-                                                         const int32_t *__restrict__ ok_tab, int n_models, double thresh2,
-                                                         unsigned long long *__restrict__ out_rows, int32_t *__restrict__ out_ok) {
-    const int lane = threadIdx.x, b = blockIdx.x;
+struct HomCheckArgs {
+    KHdr hdr;
+    const double4 *pts;
+    int flag_points;
+    const double *H_tab;
+    const int32_t *ok_tab;
+    int n_models;
+    double thresh2;
+    unsigned long long *out_rows;
+    int32_t *out_ok;
+};
+__device__ __forceinline__ void homog_check_body(const HomCheckArgs &a, int bx, int) {
+    const double4 *__restrict__ pts = a.pts;
+    const double *__restrict__ H_tab = a.H_tab;
+    const int32_t *__restrict__ ok_tab = a.ok_tab;
+    unsigned long long *__restrict__ out_rows = a.out_rows;
+    int32_t *__restrict__ out_ok = a.out_ok;
+    const int flag_points = a.flag_points, n_models = a.n_models;
+    const double thresh2 = a.thresh2;
+    const int lane = threadIdx.x, b = bx;
     if (b >= n_models) return;
     const int ok = ok_tab[b];
     if (lane == 0) out_ok[b] = ok;
@@ -339,14 +387,29 @@ __global__ __launch_bounds__(64) void homog_check_kernel(const double4 *__restri
         if (lane == 0) out_rows[(size_t)b * kArrFlagWords + w] = bal;
     }
 }
+MLPL_HUB_KERNEL(HK_HOM_CHECK, HomCheckArgs, homog_check_body, 64);
 
 // Inlier bits of table models over ALL n correspondences (the preemptive stage past the first 1024: reached when the hypothesis set keeps
 // growing instead of halving -- inlier ratios above ~0.9, where the initial set is tiny and every block of 100 generates half of what is
 // missing to 500, so the first halving comes at correspondence 1100): out[i] = words_full ballot words for table row rows[i].
-__global__ __launch_bounds__(64) void homog_extend_kernel(const int32_t *__restrict__ rows, int n_rows, const double4 *__restrict__ pts, int n,
-                                                          int words_full, const double *__restrict__ H_tab, double thresh2,
-                                                          unsigned long long *__restrict__ out) {
-    const int i = blockIdx.x, lane = threadIdx.x;
+struct HomExtendArgs {
+    KHdr hdr;
+    const int32_t *rows;
+    int n_rows;
+    const double4 *pts;
+    int n, words_full;
+    const double *H_tab;
+    double thresh2;
+    unsigned long long *out;
+};
+__device__ __forceinline__ void homog_extend_body(const HomExtendArgs &a, int bx, int) {
+    const int32_t *__restrict__ rows = a.rows;
+    const double4 *__restrict__ pts = a.pts;
+    const double *__restrict__ H_tab = a.H_tab;
+    unsigned long long *__restrict__ out = a.out;
+    const int n_rows = a.n_rows, n = a.n, words_full = a.words_full;
+    const double thresh2 = a.thresh2;
+    const int i = bx, lane = threadIdx.x;
     if (i >= n_rows) return;
     double h[9];
 #pragma unroll
@@ -362,17 +425,36 @@ __global__ __launch_bounds__(64) void homog_extend_kernel(const int32_t *__restr
         if (lane == 0) out[(size_t)i * words_full + w] = bal;
     }
 }
+MLPL_HUB_KERNEL(HK_HOM_EXTEND, HomExtendArgs, homog_extend_body, 64);
 
 // findHomographyInliers with one model over all n correspondences, one workgroup: mask[i] = !(err > th2) (the reference clears a point when
 // err > th2), the round's label for its inliers in the caller's original indexing (label_orig[orig_in[i]] = label, optional), the inliers compacted in order as
 // {Mx, My, mx, my} rows (in_pts), the outliers compacted in order with their original indices (out_p1 / out_p2 / out_orig, optional), and
 // counts = {inliers, outliers}.  Chunks of 1024 points; positions from ballots and a fixed-order scan over the waves' counts.
-__global__ __launch_bounds__(kHomInlThreads) void homog_inliers_kernel(const double *__restrict__ p1, const double *__restrict__ p2, int n,
-                                                                      const double *__restrict__ H, double th2, int force_all,
-                                                                      uint8_t *__restrict__ mask, const int32_t *__restrict__ orig_in,
-                                                                      int32_t *__restrict__ label_orig, int label, double4 *__restrict__ in_pts,
-                                                                      double *__restrict__ out_p1, double *__restrict__ out_p2,
-                                                                      int32_t *__restrict__ out_orig, int32_t *__restrict__ counts) {
+struct HomInliersArgs {  // one workgroup of kHomInlThreads
+    KHdr hdr;
+    const double *p1, *p2;
+    int n;
+    const double *H;
+    double th2;
+    int force_all;
+    uint8_t *mask;
+    const int32_t *orig_in;
+    int32_t *label_orig;
+    int label;
+    double4 *in_pts;
+    double *out_p1, *out_p2;
+    int32_t *out_orig, *counts;
+};
+__device__ __forceinline__ void homog_inliers_body(const HomInliersArgs &a, int, int) {
+    const double *__restrict__ p1 = a.p1, *__restrict__ p2 = a.p2, *__restrict__ H = a.H;
+    uint8_t *__restrict__ mask = a.mask;
+    const int32_t *__restrict__ orig_in = a.orig_in;
+    int32_t *__restrict__ label_orig = a.label_orig, *__restrict__ out_orig = a.out_orig, *__restrict__ counts = a.counts;
+    double4 *__restrict__ in_pts = a.in_pts;
+    double *__restrict__ out_p1 = a.out_p1, *__restrict__ out_p2 = a.out_p2;
+    const int n = a.n, force_all = a.force_all, label = a.label;
+    const double th2 = a.th2;
     __shared__ int wcount[kHomInlThreads / 64];
     __shared__ int s_base_in, s_base_out;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -424,13 +506,26 @@ __global__ __launch_bounds__(kHomInlThreads) void homog_inliers_kernel(const dou
     }
     if (tid == 0) counts[0] = s_base_in, counts[1] = s_base_out;
 }
+MLPL_HUB_KERNEL(HK_HOM_INLIERS, HomInliersArgs, homog_inliers_body, kHomInlThreads);
 
 // refineHomography (pose_homography.cpp:825-885): CvLevMarq(8, 0, {max_iters, DBL_EPSILON}) driven through updateAlt, all of it in one
 // launch of one workgroup.  Every evaluation adds the 36 + 8 + 1 sums (upper triangle of J^T J, J^T err, |err|^2) over the inliers in a
 // fixed order: a thread walks its points in index order, the wave folds by butterfly, thread k adds the waves' partial sums in wave order.
 // Thread 0 runs the state machine and solves the damped 8 x 8 system.  out[0..8] = the refined matrix (H(2,2) copied from H_in).
-__global__ __launch_bounds__(kHomRefineThreads) void homog_refine_kernel(const double4 *__restrict__ in_pts, const int32_t *__restrict__ count_ptr,
-                                                                         const double *__restrict__ H_in, int max_iters, double *__restrict__ out) {
+struct HomRefineArgs {  // one workgroup of kHomRefineThreads
+    KHdr hdr;
+    const double4 *in_pts;
+    const int32_t *count_ptr;
+    const double *H_in;
+    int max_iters;
+    double *out;
+};
+__device__ __forceinline__ void homog_refine_body(const HomRefineArgs &a, int, int) {
+    const double4 *__restrict__ in_pts = a.in_pts;
+    const int32_t *__restrict__ count_ptr = a.count_ptr;
+    const double *__restrict__ H_in = a.H_in;
+    double *__restrict__ out = a.out;
+    const int max_iters = a.max_iters;
     enum { DONE, STARTED, CALC_J, CHECK_ERR };
     __shared__ double red[kHomRefineThreads / 64][45];
     __shared__ double param[8], prevParam[8], JtJ[64], JtErr[8], N[64], rhs[8], dx[8];
@@ -538,6 +633,7 @@ __global__ __launch_bounds__(kHomRefineThreads) void homog_refine_kernel(const d
     if (tid < 8) out[tid] = param[tid];
     if (tid == 8) out[8] = H_in[8];
 }
+MLPL_HUB_KERNEL(HK_HOM_REFINE, HomRefineArgs, homog_refine_body, kHomRefineThreads);
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // host side
@@ -549,12 +645,18 @@ struct HomModelHost {
 };
 
 // The buffers of one call, sized for its largest problem (the multi-plane loop re-uses them for every plane).
+// A run alone takes the blocks from the context (get); the runs of a batch get one slot each of WS_BATCH_RUNS / the batch's pinned block
+// (carve), laid out for the batch's largest problem.  The blocks of the multi-plane loop follow the estimator's in the same slot.
 struct HomBufs {
     char *dev = nullptr, *pin = nullptr, *pin_dev = nullptr;
+    char *planes = nullptr;  // the multi-plane loop's device block (null: not wanted)
     size_t d_pts, d_H, d_ok, d_final, d_in, d_counts, dev_total;
-    size_t p_smp, p_ok, p_rows, p_final, p_ext, p_ext_bytes, pin_total;
+    size_t p_smp, p_ok, p_rows, p_final, p_ext, p_ext_bytes, p_r2p, pin_total;
+    // multi-plane: the label per correspondence (first: a batch clears all its slots' rows with one strided memset), the round -> plane
+    // table, the round's mask, two point buffers (p1, p2, original index) the compaction alternates between
+    size_t pl_labels, pl_r2p, pl_mask, pl_bufs, pl_pts_b, pl_per_buf, planes_total;
     static size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
-    int get(mlpl_ctx *ctx, int n) {
+    void layout(int n) {
         size_t o = 0;
         d_pts = o, o = up(o + (size_t)std::max(n, 1) * sizeof(double4));
         d_H = o, o = up(o + (size_t)kHomPoolSamples * 72);
@@ -570,11 +672,28 @@ struct HomBufs {
         p_final = o, o = up(o + 256);
         p_ext_bytes = std::max((size_t)65536, (size_t)((std::max(n, 1) + 63) / 64) * 8 + 8192);  // a row list (4096 bytes) + at least one full row
         p_ext = o, o = up(o + p_ext_bytes);
+        p_r2p = o, o = up(o + (size_t)std::max(n, 1) * 4 + 16);  // round -> plane (at most n / 4 rounds; padded for the 16-byte copy kernel)
         pin_total = o + 256;
+        const size_t idx_b = up((size_t)std::max(n, 1) * 4 + 16);
+        pl_pts_b = up((size_t)std::max(n, 1) * 16);
+        pl_per_buf = 2 * pl_pts_b + idx_b;
+        o = 0;
+        pl_labels = o, o += idx_b;
+        pl_r2p = o, o += idx_b;
+        pl_mask = o, o += up((size_t)std::max(n, 1));
+        pl_bufs = o, o += 2 * pl_per_buf;
+        planes_total = o;
+    }
+    int get(mlpl_ctx *ctx, int n, bool want_planes = false) {
+        layout(n);
         void *p;
         int rc;
         if ((rc = ws_get(ctx, WS_HOMOG, dev_total, &p))) return rc;
         dev = (char *)p;
+        if (want_planes) {
+            if ((rc = ws_get(ctx, WS_HOMOG_PLANES, planes_total, &p))) return rc;
+            planes = (char *)p;
+        }
         if ((rc = pinned_get(ctx, pin_total, &p))) return rc;
         pin = (char *)p;
         void *alias = nullptr;
@@ -582,11 +701,16 @@ struct HomBufs {
         pin_dev = (char *)alias;
         return MLPL_OK;
     }
+    void carve(int n_max, char *dev_slot, char *pin_slot, char *pin_dev_slot, bool want_planes) {
+        layout(n_max);
+        dev = dev_slot, pin = pin_slot, pin_dev = pin_dev_slot;
+        planes = want_planes ? dev_slot + dev_total : nullptr;
+    }
 };
 
 struct HomogRun {
     mlpl_ctx *ctx;
-    hipStream_t s;
+    Launcher L;  // launches now (a run alone) or records for the hub (a run of a batch, batch_hub.h)
     const HomBufs *B;
     const double *d_p1, *d_p2;
     int n, flag_points;
@@ -604,14 +728,10 @@ struct HomogRun {
     double rejected_accum = 0.0;
     CvRng prosac_rng, random_rng;
 
-    int sync() {
-        MLPL_HIP_TRY(hipStreamSynchronize(s));
-        return MLPL_OK;
-    }
-    int pack_points() {
-        hipLaunchKernelGGL(homog_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_p1, d_p2, n, (double4 *)(B->dev + B->d_pts));
-        MLPL_HIP_TRY(hipGetLastError());
-        return MLPL_OK;
+    int sync() { return L.sync(); }
+    void pack_points() {
+        HomPackArgs pa{{(n + 255) / 256, 1}, d_p1, d_p2, n, (double4 *)(B->dev + B->d_pts)};
+        L.launch(HK_HOM_PACK, pa);
     }
     // the sample kernel on `keys` (checked here against n and the sample sizes): models into the table rows pool_samples ...
     int launch_samples(const std::vector<ArrKey> &keys) {
@@ -636,8 +756,8 @@ struct HomogRun {
         }
         double *d_H = (double *)(B->dev + B->d_H) + (size_t)pool_samples * 9;
         int32_t *d_ok = (int32_t *)(B->dev + B->d_ok) + pool_samples;
-        hipLaunchKernelGGL(homog_sample_kernel, dim3(nb), dim3(64), 0, s, d_p1, d_p2, (const int32_t *)(B->pin_dev + B->p_smp), nb, d_H, d_ok);
-        MLPL_HIP_TRY(hipGetLastError());
+        HomSampleArgs sa{{nb, 1}, d_p1, d_p2, (const int32_t *)(B->pin_dev + B->p_smp), nb, d_H, d_ok};
+        L.launch(HK_HOM_SAMPLE, sa);
         return MLPL_OK;
     }
     // one device batch: every key gets its cache entry
@@ -648,9 +768,9 @@ struct HomogRun {
         if ((rc = launch_samples(keys))) return rc;
         const double *d_H = (const double *)(B->dev + B->d_H) + (size_t)pool_samples * 9;
         const int32_t *d_ok = (const int32_t *)(B->dev + B->d_ok) + pool_samples;
-        hipLaunchKernelGGL(homog_check_kernel, dim3(nb), dim3(64), 0, s, (const double4 *)(B->dev + B->d_pts), flag_points, d_H, d_ok, nb, thresh2,
-                           (unsigned long long *)(B->pin_dev + B->p_rows), (int32_t *)(B->pin_dev + B->p_ok));
-        MLPL_HIP_TRY(hipGetLastError());
+        HomCheckArgs ca{{nb, 1}, (const double4 *)(B->dev + B->d_pts), flag_points, d_H, d_ok, nb, thresh2,
+                        (unsigned long long *)(B->pin_dev + B->p_rows), (int32_t *)(B->pin_dev + B->p_ok)};
+        L.launch(HK_HOM_CHECK, ca);
         if ((rc = sync())) return rc;  // kernel completion makes its system-scope writes visible
         const int32_t *h_ok = (const int32_t *)(B->pin + B->p_ok);
         const uint64_t *h_rows = (const uint64_t *)(B->pin + B->p_rows);
@@ -685,10 +805,9 @@ struct HomogRun {
         for (size_t at = 0; at < need.size(); at += per) {
             const int cnt = (int)std::min(need.size() - at, per);
             for (int i = 0; i < cnt; ++i) h_rows[i] = pool[need[at + i]].row;
-            hipLaunchKernelGGL(homog_extend_kernel, dim3(cnt), dim3(64), 0, s, (const int32_t *)(B->pin_dev + B->p_ext), cnt,
-                               (const double4 *)(B->dev + B->d_pts), n, wf, (const double *)(B->dev + B->d_H), thresh2,
-                               (unsigned long long *)(B->pin_dev + B->p_ext + 4096));
-            MLPL_HIP_TRY(hipGetLastError());
+            HomExtendArgs ea{{cnt, 1}, (const int32_t *)(B->pin_dev + B->p_ext), cnt, (const double4 *)(B->dev + B->d_pts), n, wf,
+                             (const double *)(B->dev + B->d_H), thresh2, (unsigned long long *)(B->pin_dev + B->p_ext + 4096)};
+            L.launch(HK_HOM_EXTEND, ea);
             int rc;
             if ((rc = sync())) return rc;
             const uint64_t *g = (const uint64_t *)(B->pin + B->p_ext + 4096);
@@ -975,7 +1094,7 @@ struct HomPlaneOut {
 // reference's `false`) or an error; rng_state advances whenever the estimator itself ran through.  *n_outliers (optional): what the
 // compaction of HomPlaneOut holds.
 static int homography_arrsac_run(mlpl_ctx *ctx, const HomBufs &B, const double *d_p1, const double *d_p2, int n, double th, uint64_t *rng_state,
-                                 double *H, uint8_t *d_mask, int *n_inliers, long long *stats12, const HomPlaneOut *po, hipStream_t s) {
+                                 double *H, uint8_t *d_mask, int *n_inliers, long long *stats12, const HomPlaneOut *po, const Launcher &L) {
     if (n_inliers) *n_inliers = 0;
     if (stats12) std::memset(stats12, 0, 12 * sizeof(long long));
     if (n < 4) {
@@ -983,7 +1102,7 @@ static int homography_arrsac_run(mlpl_ctx *ctx, const HomBufs &B, const double *
         return MLPL_E_FAILED;
     }
     HomogRun R;
-    R.ctx = ctx, R.s = s, R.B = &B, R.d_p1 = d_p1, R.d_p2 = d_p2, R.n = n;
+    R.ctx = ctx, R.L = L, R.B = &B, R.d_p1 = d_p1, R.d_p2 = d_p2, R.n = n;
     R.flag_points = std::min(n, kArrFlagPoints);
     R.thresh2 = th * th;
     int rc, row;
@@ -992,9 +1111,9 @@ static int homography_arrsac_run(mlpl_ctx *ctx, const HomBufs &B, const double *
         key.reset(0);
         for (int i = 0; i < 4; ++i) key.push(i);
         if ((rc = R.launch_samples(std::vector<ArrKey>(1, key)))) return rc;
-        int32_t ok = 0;
-        MLPL_HIP_TRY(hipMemcpyAsync(&ok, B.dev + B.d_ok, 4, hipMemcpyDeviceToHost, s));
+        hub_copy_bytes(R.L, B.dev + B.d_ok, B.pin_dev + B.p_ok, 4);  // the verdict, through the mapped block
         if ((rc = R.sync())) return rc;
+        const int32_t ok = *(const int32_t *)(B.pin + B.p_ok);
         if (!ok) {
             set_error("mlpl_homography_arrsac: the four correspondences are degenerate");
             return MLPL_E_FAILED;
@@ -1002,7 +1121,7 @@ static int homography_arrsac_run(mlpl_ctx *ctx, const HomBufs &B, const double *
         row = 0;
     } else {
         R.prosac_rng.state = rng_state[0], R.random_rng.state = rng_state[1];
-        if ((rc = R.pack_points())) return rc;
+        R.pack_points();
         rc = MLPL_OK;
         const int best = R.estimate(&rc);
         if (stats12) std::memcpy(stats12, R.stats, sizeof(R.stats));
@@ -1021,17 +1140,15 @@ static int homography_arrsac_run(mlpl_ctx *ctx, const HomBufs &B, const double *
     int32_t *h_counts = (int32_t *)(h_final + 18), *h_counts_dev = (int32_t *)(h_final_dev + 18);
     int32_t *d_counts = (int32_t *)(B.dev + B.d_counts);
     double4 *d_in = (double4 *)(B.dev + B.d_in);
-    hipLaunchKernelGGL(homog_inliers_kernel, dim3(1), dim3(kHomInlThreads), 0, s, d_p1, d_p2, n, d_Hbest, th * th, n == 4 ? 1 : 0, d_mask,
-                       po ? po->orig_in : nullptr, po ? po->label_orig : nullptr, po ? po->label : 0, d_in, po ? po->out_p1 : nullptr, po ? po->out_p2 : nullptr,
-                       po ? po->out_orig : nullptr, d_counts);
-    MLPL_HIP_TRY(hipGetLastError());
+    HomInliersArgs ia{{1, 1}, d_p1, d_p2, n, d_Hbest, th * th, n == 4 ? 1 : 0, d_mask, po ? po->orig_in : nullptr, po ? po->label_orig : nullptr,
+                      po ? po->label : 0, d_in, po ? po->out_p1 : nullptr, po ? po->out_p2 : nullptr, po ? po->out_orig : nullptr, d_counts};
+    R.L.launch(HK_HOM_INLIERS, ia);
     if (n != 4) {
-        hipLaunchKernelGGL(homog_refine_kernel, dim3(1), dim3(kHomRefineThreads), 0, s, (const double4 *)d_in, (const int32_t *)d_counts, d_Hbest, 10,
-                           h_final_dev);
-        MLPL_HIP_TRY(hipGetLastError());
+        HomRefineArgs ra{{1, 1}, (const double4 *)d_in, (const int32_t *)d_counts, d_Hbest, 10, h_final_dev};
+        R.L.launch(HK_HOM_REFINE, ra);
     }
-    hipLaunchKernelGGL(homog_final_kernel, dim3(1), dim3(64), 0, s, d_Hbest, (const int32_t *)d_counts, h_final_dev + 9, h_counts_dev);
-    MLPL_HIP_TRY(hipGetLastError());
+    HomFinalArgs fa{{1, 1}, d_Hbest, (const int32_t *)d_counts, h_final_dev + 9, h_counts_dev};
+    R.L.launch(HK_HOM_FINAL, fa);
     if ((rc = R.sync())) return rc;
     std::memcpy(H, n == 4 ? h_final + 9 : h_final, 72);
     if (n_inliers) *n_inliers = h_counts[0];
@@ -1046,7 +1163,9 @@ int homography_arrsac_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2,
     HomBufs B;
     int rc;
     if ((rc = B.get(ctx, n))) return rc;
-    return homography_arrsac_run(ctx, B, d_p1, d_p2, n, th, rng_state, H, d_mask, n_inliers, stats12, nullptr, s);
+    Launcher L;
+    L.s = s;
+    return homography_arrsac_run(ctx, B, d_p1, d_p2, n, th, rng_state, H, d_mask, n_inliers, stats12, nullptr, L);
 }
 
 // findHomographyInliers alone: d_mask (n bytes) and the count
@@ -1058,9 +1177,9 @@ int homography_inliers_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2
     double *h_final = (double *)(B.pin + B.p_final);
     std::memcpy(h_final, H, 72);
     int32_t *d_counts = (int32_t *)(B.dev + B.d_counts);
-    hipLaunchKernelGGL(homog_inliers_kernel, dim3(1), dim3(kHomInlThreads), 0, s, d_p1, d_p2, n, (const double *)(B.pin_dev + B.p_final), th * th, 0,
-                       d_mask, (const int32_t *)nullptr, (int32_t *)nullptr, 0, (double4 *)nullptr, (double *)nullptr, (double *)nullptr,
-                       (int32_t *)nullptr, d_counts);
+    HomInliersArgs ia{{1, 1}, d_p1, d_p2, n, (const double *)(B.pin_dev + B.p_final), th * th, 0, d_mask, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                      nullptr, d_counts};
+    hub_kernels()[HK_HOM_INLIERS].single(&ia, s);
     MLPL_HIP_TRY(hipGetLastError());
     int32_t cnt[2] = {0, 0};
     MLPL_HIP_TRY(hipMemcpyAsync(cnt, d_counts, 8, hipMemcpyDeviceToHost, s));
@@ -1076,13 +1195,14 @@ int homography_sample_models(mlpl_ctx *ctx, const double *d_p1, const double *d_
     int rc;
     if ((rc = B.get(ctx, n))) return rc;
     HomogRun R;
-    R.ctx = ctx, R.s = s, R.B = &B, R.d_p1 = d_p1, R.d_p2 = d_p2, R.n = n;
+    R.ctx = ctx, R.L.s = s, R.B = &B, R.d_p1 = d_p1, R.d_p2 = d_p2, R.n = n;
     std::vector<ArrKey> keys((size_t)count);
     for (int b = 0; b < count; ++b) {
         keys[b].reset(HomogRun::sample_kind(m));
         for (int i = 0; i < m; ++i) keys[b].push(idx[(size_t)b * m + i]);
     }
     if ((rc = R.launch_samples(keys))) return rc == MLPL_E_INTERNAL ? MLPL_E_BAD_INPUT : rc;
+    MLPL_HIP_TRY(hipGetLastError());
     MLPL_HIP_TRY(hipMemcpyAsync(H, B.dev + B.d_H, (size_t)count * 72, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipMemcpyAsync(ok, B.dev + B.d_ok, (size_t)count * 4, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
@@ -1092,9 +1212,22 @@ int homography_sample_models(mlpl_ctx *ctx, const double *d_p1, const double *d_
 // The planes of the multi-plane loop for the caller: label_round[j] = the round that took correspondence j (-1 none), round_to_plane[r] =
 // the output index of that round's plane (-1: not reported).  labels_out[j] (optional) = output plane or -1; masks (optional) = n_planes
 // rows of n flags.
-__global__ void homog_planes_out_kernel(const int32_t *__restrict__ label_round, int n, const int32_t *__restrict__ round_to_plane, int n_planes,
-                                        int32_t *__restrict__ labels_out, uint8_t *__restrict__ masks) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+namespace {
+struct HomPlanesOutArgs {  // 256 threads per block
+    KHdr hdr;
+    const int32_t *label_round;
+    int n;
+    const int32_t *round_to_plane;
+    int n_planes;
+    int32_t *labels_out;
+    uint8_t *masks;
+};
+__device__ __forceinline__ void homog_planes_out_body(const HomPlanesOutArgs &a, int bx, int) {
+    const int32_t *__restrict__ label_round = a.label_round, *__restrict__ round_to_plane = a.round_to_plane;
+    int32_t *__restrict__ labels_out = a.labels_out;
+    uint8_t *__restrict__ masks = a.masks;
+    const int n = a.n, n_planes = a.n_planes;
+    const int j = bx * 256 + threadIdx.x;
     if (j >= n) return;
     const int r = label_round[j];
     const int k = r >= 0 ? round_to_plane[r] : -1;
@@ -1102,6 +1235,7 @@ __global__ void homog_planes_out_kernel(const int32_t *__restrict__ label_round,
     if (masks)
         for (int p = 0; p < n_planes; ++p) masks[(size_t)p * n + j] = k == p ? 1 : 0;
 }
+MLPL_HUB_KERNEL(HK_HOM_PLANES_OUT, HomPlanesOutArgs, homog_planes_out_body, 256);
 
 // estimateMultHomographys (pose_homography.cpp:291-463): plane after plane, the outliers of one round are the next round's input in
 // their original order; the correspondences stay on the device between planes (two buffers the compaction alternates between).  The
@@ -1111,24 +1245,19 @@ __global__ void homog_planes_out_kernel(const int32_t *__restrict__ label_round,
 // count, descending (std::sort on the reference's pairs) when more than one plane was found; found_at[k] (optional) = the round that found
 // output plane k (ascending found_at = the order of discovery).  *n_planes = -1: no homography found (the reference's return value -1).
 // Finding more than cap planes is MLPL_E_BAD_INPUT with rng_state put back, so the call can be repeated with larger arrays.
-int mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes, unsigned min_pts,
-                          uint64_t *rng_state, int cap, int *n_planes, double *Hs, int32_t *num_inl, double *strength, double *th_used, uint8_t *d_masks,
-                          int32_t *d_labels, int32_t *found_at, hipStream_t s) {
+// B holds the blocks of the loop (HomBufs::planes); a run of a batch (L.hub set) finds its label row cleared by the batch driver.
+static int mult_homographies_run(mlpl_ctx *ctx, const HomBufs &B, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
+                                 unsigned min_pts, uint64_t *rng_state, int cap, int *n_planes, double *Hs, int32_t *num_inl, double *strength,
+                                 double *th_used, uint8_t *d_masks, int32_t *d_labels, int32_t *found_at, Launcher L) {
     *n_planes = 0;
     const uint64_t rng_in[2] = {rng_state[0], rng_state[1]};
-    HomBufs B;
     int rc;
-    if ((rc = B.get(ctx, n))) return rc;
-    // per-call blocks: two point buffers (p1, p2, original index), the round's mask, the label per correspondence, the round -> plane table
-    const size_t pts_b = HomBufs::up((size_t)n * 16), idx_b = HomBufs::up((size_t)n * 4), mask_b = HomBufs::up((size_t)n);
-    const size_t per_buf = 2 * pts_b + idx_b;
+    const size_t pts_b = B.pl_pts_b, per_buf = B.pl_per_buf;
     const bool want_labels = d_masks || d_labels;
-    void *wp;
-    if ((rc = ws_get(ctx, WS_HOMOG_PLANES, 2 * per_buf + mask_b + 2 * idx_b, &wp))) return rc;
-    char *w = (char *)wp;
-    uint8_t *d_round_mask = (uint8_t *)(w + 2 * per_buf);
-    int32_t *d_label_round = (int32_t *)(w + 2 * per_buf + mask_b), *d_round_to_plane = (int32_t *)(w + 2 * per_buf + mask_b + idx_b);
-    if (want_labels) MLPL_HIP_TRY(hipMemsetAsync(d_label_round, 0xFF, (size_t)n * 4, s));
+    char *w = B.planes + B.pl_bufs;
+    uint8_t *d_round_mask = (uint8_t *)(B.planes + B.pl_mask);
+    int32_t *d_label_round = (int32_t *)(B.planes + B.pl_labels), *d_round_to_plane = (int32_t *)(B.planes + B.pl_r2p);
+    if (want_labels && !L.hub) MLPL_HIP_TRY(hipMemsetAsync(d_label_round, 0xFF, (size_t)n * 4, L.s));
     struct Plane {
         double H[9], strength, th_used;
         unsigned n_inl;
@@ -1150,7 +1279,7 @@ int mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2,
         double th_tmp = th * th_mult_base, H[9];
         int cnt = 0;
         do {
-            rc = homography_arrsac_run(ctx, B, cur_p1, cur_p2, nc, th_tmp, rng_state, H, d_round_mask, &cnt, nullptr, &po, s);
+            rc = homography_arrsac_run(ctx, B, cur_p1, cur_p2, nc, th_tmp, rng_state, H, d_round_mask, &cnt, nullptr, &po, L);
             if (rc && rc != MLPL_E_FAILED) return rc;
             th_tmp *= th_mult;
         } while (var_th && rc == MLPL_E_FAILED && th_tmp < maxTh);
@@ -1185,7 +1314,10 @@ int mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2,
     for (unsigned k = 0; k < planes.size(); ++k) order.push_back(std::make_pair(k, planes[k].n_inl));
     if (planes.size() > 1)
         std::sort(order.begin(), order.end(), [](std::pair<unsigned, unsigned> const &a, std::pair<unsigned, unsigned> const &b) { return a.second > b.second; });
-    std::vector<int32_t> round_to_plane((size_t)std::max(i, 1u), -1);  // i rounds ran (every round took at least 4 correspondences: i <= n / 4)
+    // i rounds ran (every round took at least 4 correspondences: i <= n / 4); the table is built in the run's mapped block
+    int32_t *round_to_plane = (int32_t *)(B.pin + B.p_r2p);
+    const size_t n_rounds = (size_t)std::max(i, 1u);
+    for (size_t r = 0; r < n_rounds; ++r) round_to_plane[r] = -1;
     for (size_t k = 0; k < planes.size(); ++k) {
         const Plane &pl = planes[order[k].first];
         std::memcpy(Hs + 9 * k, pl.H, 72);
@@ -1194,12 +1326,163 @@ int mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2,
         round_to_plane[(size_t)pl.round] = (int32_t)k;
     }
     if (want_labels && !planes.empty()) {
-        MLPL_HIP_TRY(hipMemcpyAsync(d_round_to_plane, round_to_plane.data(), round_to_plane.size() * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(homog_planes_out_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const int32_t *)d_label_round, n,
-                           (const int32_t *)d_round_to_plane, (int)planes.size(), d_labels, d_masks);
-        MLPL_HIP_TRY(hipGetLastError());
-        MLPL_HIP_TRY(hipStreamSynchronize(s));  // round_to_plane leaves scope
+        hub_copy_bytes(L, B.pin_dev + B.p_r2p, d_round_to_plane, n_rounds * 4);
+        HomPlanesOutArgs oa{{(n + 255) / 256, 1}, (const int32_t *)d_label_round, n, (const int32_t *)d_round_to_plane, (int)planes.size(), d_labels, d_masks};
+        L.launch(HK_HOM_PLANES_OUT, oa);
+        if ((rc = L.sync())) return rc;  // the mapped block is the next call's
     }
     *n_planes = (int)planes.size();
     return MLPL_OK;
+}
+}  // namespace
+
+int mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes, unsigned min_pts,
+                          uint64_t *rng_state, int cap, int *n_planes, double *Hs, int32_t *num_inl, double *strength, double *th_used, uint8_t *d_masks,
+                          int32_t *d_labels, int32_t *found_at, hipStream_t s) {
+    HomBufs B;
+    int rc;
+    if ((rc = B.get(ctx, n, true))) return rc;
+    Launcher L;
+    L.s = s;
+    return mult_homographies_run(ctx, B, d_p1, d_p2, n, th, var_th, max_planes, min_pts, rng_state, cap, n_planes, Hs, num_inl, strength, th_used, d_masks,
+                                 d_labels, found_at, L);
+}
+
+// ---- batches of plane problems: every run a fiber on a worker thread, every launch merged over the runs (batch_hub.h) --------------------------------
+// The shape of arrsac_essential_batch_dev: cohorts of at most 128 runs, up to four of them in flight on the lanes' streams; a run's blocks are
+// one slot of WS_BATCH_RUNS / the batch's pinned block, laid out for the largest problem.  job(b, bufs, launcher) is problem b's sequential
+// program -- the one the single entries run -- and returns its status.  Every problem's outputs are those of the single entry on it alone.
+namespace {
+constexpr int kHomBatchRuns = 128;
+
+static int homography_batch_drive(mlpl_ctx *ctx, int B, const int32_t *counts, bool want_planes, bool clear_labels, int32_t *status, hipStream_t s,
+                                  const char *name, const std::function<int(int, const HomBufs &, const Launcher &)> &job) {
+    if (B <= 0) return MLPL_OK;
+    int rc, n_max = 1;
+    for (int b = 0; b < B; ++b) n_max = std::max(n_max, counts[b]);
+    HomBufs Y;
+    Y.layout(n_max);
+    const size_t slot_dev = Y.dev_total + (want_planes ? HomBufs::up(Y.planes_total) : 0), slot_pin = Y.pin_total;
+    int n_cohorts = 0, lanes = 0;
+    const int cohort = hub_cohort_size(ctx, B, kHomBatchRuns, &n_cohorts, &lanes);
+    void *pblk, *dblk;
+    if ((rc = pinned_batch_get(ctx, (size_t)lanes * cohort * slot_pin, &pblk))) return rc;
+    if ((rc = ws_get(ctx, WS_BATCH_RUNS, (size_t)lanes * cohort * slot_dev, &dblk))) return rc;
+    char *pin = (char *)pblk, *pin_dev = nullptr;
+    {
+        void *alias = nullptr;
+        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pin, 0));
+        pin_dev = (char *)alias;
+    }
+    hipStream_t lane_stream[kHubLanes];
+    for (int l = 0; l < lanes; ++l)
+        if ((rc = hub_lane_stream(ctx, l, s, &lane_stream[l]))) return rc;
+    if (lanes > 1) MLPL_HIP_TRY(hipStreamSynchronize(s));  // the correspondences were produced on the caller's stream; a lane's own stream has no other ordering
+    struct LaneOut {
+        long long rounds = 0, merged = 0;
+        int first_err = 0;
+        std::string first_msg;
+    };
+    LaneOut lane_out[kHubLanes];
+    auto serve_lane = [&](int l) {
+        LaneOut &LO = lane_out[l];
+        const hipStream_t ls = lane_stream[l];
+        if (l > 0 && hipSetDevice(ctx->device) != hipSuccess) {  // a lane's own thread starts on device 0
+            LO.first_err = MLPL_E_INTERNAL, LO.first_msg = "batched estimator: hipSetDevice failed on a lane thread";
+            return;
+        }
+        for (int c = l; c < n_cohorts; c += lanes) {
+            const int b0 = c * cohort, nb = std::min(cohort, B - b0);
+            char *dev0 = (char *)dblk + (size_t)l * cohort * slot_dev;
+            if (clear_labels &&  // the label rows of all this cohort's slots: -1 = taken by no round
+                hipMemset2DAsync(dev0 + Y.dev_total + Y.pl_labels, slot_dev, 0xFF, (size_t)n_max * 4, (size_t)nb, ls) != hipSuccess) {
+                LO.first_err = MLPL_E_HIP, LO.first_msg = std::string(name) + ": clearing the label rows failed";
+                break;
+            }
+            BatchHub hub(ctx, ls, nb, l);
+            std::vector<HomBufs> bufs((size_t)nb);
+            std::vector<std::string> msgs((size_t)nb);
+            for (int k = 0; k < nb; ++k) {
+                const size_t slot = (size_t)l * cohort + k;
+                bufs[k].carve(n_max, (char *)dblk + slot * slot_dev, pin + slot * slot_pin, pin_dev + slot * slot_pin, want_planes);
+            }
+            HubThreads &pool = hub_resources(ctx)->lane[l].threads;
+            pool.start(nb, [&](int k) {
+                const int b = b0 + k;
+                HubRun &hr = hub.run(k);
+                int r = MLPL_OK;
+                try {
+                    Launcher L;
+                    L.s = ls, L.hub = &hub, L.run = &hr;
+                    r = job(b, bufs[k], L);
+                } catch (const std::bad_alloc &) {
+                    r = MLPL_E_NOMEM;
+                    set_error("out of host memory");
+                } catch (...) {  // (anything else -- a length_error of a vector, say -- must not unwind off the fiber's makecontext frame)
+                    r = MLPL_E_INTERNAL;
+                    set_error("a run ended with an unexpected C++ exception");
+                }
+                if (r && r != MLPL_E_FAILED) msgs[k] = std::string(name) + ": problem " + std::to_string(b) + ": " + mlpl_last_error();
+                status[b] = r;
+                hub.finish(hr);
+            }, ctx->opt_hub_workers);
+            const int hrc = hub.serve();
+            pool.wait();
+            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches();
+            for (int k = 0; k < nb && !LO.first_err; ++k)
+                if (status[b0 + k] && status[b0 + k] != MLPL_E_FAILED) LO.first_err = status[b0 + k], LO.first_msg = msgs[k];
+            if (hrc && !LO.first_err) LO.first_err = hrc;
+            if (LO.first_err) break;
+        }
+    };
+    {
+        std::vector<std::thread> others;
+        for (int l = 1; l < lanes; ++l) others.emplace_back(serve_lane, l);
+        serve_lane(0);
+        for (auto &t : others) t.join();
+    }
+    int first_err = 0;
+    std::string first_msg;
+    long long rounds = 0, merged = 0;
+    for (int l = 0; l < lanes; ++l) {
+        rounds += lane_out[l].rounds, merged += lane_out[l].merged;
+        if (lane_out[l].first_err && !first_err) first_err = lane_out[l].first_err, first_msg = lane_out[l].first_msg;
+    }
+    ctx->last_arrsac_stats[8] = rounds, ctx->last_arrsac_stats[9] = merged;  // the hub's counters, where the E batch leaves its own
+    if (first_err) {
+        if (!first_msg.empty()) set_error("%s", first_msg.c_str());
+        return first_err;
+    }
+    return MLPL_OK;
+}
+}  // namespace
+
+int homography_arrsac_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                uint64_t *rng_states, double *H, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, long long *stats, hipStream_t s) {
+    return homography_batch_drive(ctx, B, counts, false, false, status, s, "mlpl_homography_arrsac_batch_dev", [&](int b, const HomBufs &Bf, const Launcher &L) {
+        int ninl = 0;  // (fewer than 4 correspondences: MLPL_E_FAILED before anything is touched)
+        const int r = homography_arrsac_run(ctx, Bf, d_p1 + (size_t)b * stride * 2, d_p2 + (size_t)b * stride * 2, counts[b], th, rng_states + 2 * (size_t)b,
+                                            H + (size_t)b * 9, d_masks + (size_t)b * stride, &ninl, stats ? stats + (size_t)b * 12 : nullptr, nullptr, L);
+        if (n_inliers) n_inliers[b] = ninl;
+        return r;
+    });
+}
+
+int mult_homographies_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th, int var_th,
+                                unsigned max_planes, unsigned min_pts, uint64_t *rng_states, int cap, int32_t *n_planes, double *Hs, int32_t *num_inl,
+                                double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, int32_t *status, hipStream_t s) {
+    return homography_batch_drive(ctx, B, counts, true, d_labels != nullptr, status, s, "mlpl_mult_homographies_batch_dev",
+                                  [&](int b, const HomBufs &Bf, const Launcher &L) {
+        if (counts[b] < 4) {
+            n_planes[b] = -1;
+            return (int)MLPL_E_FAILED;
+        }
+        const size_t at = (size_t)b * cap;
+        int np = 0;
+        const int r = mult_homographies_run(ctx, Bf, d_p1 + (size_t)b * stride * 2, d_p2 + (size_t)b * stride * 2, counts[b], th, var_th, max_planes, min_pts,
+                                            rng_states + 2 * (size_t)b, cap, &np, Hs + at * 9, num_inl + at, strength + at, th_used + at, nullptr,
+                                            d_labels ? d_labels + (size_t)b * stride : nullptr, found_at ? found_at + at : nullptr, L);
+        n_planes[b] = np;
+        return r;
+    });
 }

@@ -28,6 +28,14 @@ enum HubKernelId {
     HK_ARR_MASK_COUNT,
     HK_ARR_REFINE,
     HK_PACK_POINTS,
+    HK_HOM_PACK,       // homography_impl.h: the eight kernels of computeHomographyArrsac / estimateMultHomographys
+    HK_HOM_SAMPLE,
+    HK_HOM_CHECK,
+    HK_HOM_EXTEND,
+    HK_HOM_INLIERS,
+    HK_HOM_REFINE,
+    HK_HOM_FINAL,
+    HK_HOM_PLANES_OUT,
     HK_NUM
 };
 static_assert(HK_NUM <= kHubMaxKernels, "kernel table too small");

@@ -4222,6 +4222,55 @@ int mlpl_mult_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, in
                                          nullptr, nullptr, masks);
 }
 
+static bool homography_batch_counts_ok(const char *name, int n_problems, const int32_t *counts, int stride) {
+    for (int b = 0; b < n_problems; ++b)
+        if (counts[b] < 0 || counts[b] > stride) {
+            set_error("%s: problem %d has %d correspondences (0 ... stride %d)", name, b, counts[b], stride);
+            return false;
+        }
+    return true;
+}
+
+int mlpl_homography_arrsac_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                     uint64_t *rng_states, double *H, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, long long *stats, void *stream) {
+    if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || !H || !d_masks || !n_inliers || !status || !(th > 0) ||
+        !std::isfinite(th)) {
+        set_error("mlpl_homography_arrsac_batch_dev: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    if (!homography_batch_counts_ok("mlpl_homography_arrsac_batch_dev", n_problems, counts, stride)) return MLPL_E_BAD_INPUT;
+    if (n_problems == 0) return MLPL_OK;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    try {
+        return homography_arrsac_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, rng_states, H, d_masks, n_inliers, status, stats,
+                                           pick_stream(ctx, stream));
+    } catch (const std::bad_alloc &) {
+        set_error("mlpl_homography_arrsac_batch_dev: out of host memory");
+        return MLPL_E_NOMEM;
+    }
+}
+
+int mlpl_mult_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                     int var_th, unsigned max_planes, unsigned min_pts_per_plane, uint64_t *rng_states, int cap, int32_t *n_planes,
+                                     double *H, int32_t *num_inl, double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, int32_t *status,
+                                     void *stream) {
+    if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || cap < 1 || !n_planes || !H || !num_inl || !strength ||
+        !th_used || !status || !(th > 0) || !std::isfinite(th)) {
+        set_error("mlpl_mult_homographies_batch_dev: bad arguments");
+        return MLPL_E_BAD_INPUT;
+    }
+    if (!homography_batch_counts_ok("mlpl_mult_homographies_batch_dev", n_problems, counts, stride)) return MLPL_E_BAD_INPUT;
+    if (n_problems == 0) return MLPL_OK;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    try {
+        return mult_homographies_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, var_th, max_planes, min_pts_per_plane, rng_states, cap, n_planes,
+                                           H, num_inl, strength, th_used, found_at, d_labels, status, pick_stream(ctx, stream));
+    } catch (const std::bad_alloc &) {
+        set_error("mlpl_mult_homographies_batch_dev: out of host memory");
+        return MLPL_E_NOMEM;
+    }
+}
+
 int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *idx, int m, int count, double *H, int32_t *ok) {
     if (!ctx || !p1 || !p2 || !idx || !H || !ok || n < 4 || m < 4 || m > 12 || count < 1 || count > 512) {
         set_error("mlpl_debug_homography_models: bad arguments (4 <= m <= 12, 1 <= count <= 512)");

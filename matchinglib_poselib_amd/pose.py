@@ -584,6 +584,70 @@ def mult_homographies_device(p1, p2, th: float, var_th: bool = True, max_planes:
                 th_used=thu[:k].copy(), found_at=found[:k].copy(), labels=labels[:n], masks=masks)
 
 
+def _plane_batch_inputs(d_p1, d_p2, counts, rng_states):
+    import torch
+
+    B, stride = d_p1.shape[0], d_p1.shape[1]
+    assert d_p1.is_cuda and d_p1.dtype == torch.float64 and d_p1.shape == d_p2.shape == (B, stride, 2) and d_p1.is_contiguous() and d_p2.is_contiguous()
+    cn = np.ascontiguousarray(counts, np.int32)
+    assert cn.shape == (B,)
+    st = np.tile(np.array(ARRSAC_RNG_FRESH, np.uint64), (B, 1)) if rng_states is None else rng_states
+    assert st.dtype == np.uint64 and st.shape == (B, 2) and st.flags.c_contiguous
+    return B, stride, cn, st
+
+
+def homography_arrsac_batch(d_p1, d_p2, counts, th: float, rng_states=None, masks_out=None, ctx: Optional[Context] = None) -> list:
+    """A batch of computeHomographyArrsac problems in ONE library call (mlpl_homography_arrsac_batch_dev): d_p1, d_p2 float64 CUDA tensors
+    [B, stride, 2], counts[b] valid rows; rng_states: uint64 [B, 2] (default: fresh streams for every problem), advanced in place.  Returns
+    one dict per problem (ok, H, n_inliers, stats, rng_state) -- what homography_arrsac_device returns for it alone; masks through
+    masks_out (uint8 CUDA tensor [B, stride])."""
+    import torch
+
+    ctx = ctx or default_context()
+    B, stride, cn, st = _plane_batch_inputs(d_p1, d_p2, counts, rng_states)
+    if masks_out is None:
+        masks_out = torch.zeros((B, stride), dtype=torch.uint8, device=d_p1.device)
+    assert masks_out.is_cuda and masks_out.dtype == torch.uint8 and masks_out.shape == (B, stride) and masks_out.is_contiguous()
+    H, ninl, status, stats = np.zeros((B, 3, 3)), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 12), np.int64)
+    rc = ctx.lib.mlpl_homography_arrsac_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, float(th), st.ctypes.data,
+                                                  H.ctypes.data, masks_out.data_ptr(), ninl.ctypes.data, status.ctypes.data, stats.ctypes.data,
+                                                  torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_homography_arrsac_batch_dev", _lib.last_error())
+    return [dict(ok=bool(status[b] == 0), H=H[b].copy(), n_inliers=int(ninl[b]), stats=stats[b].copy(), rng_state=st[b].copy()) for b in range(B)]
+
+
+def mult_homographies_batch(d_p1, d_p2, counts, th: float, var_th: bool = True, max_planes: int = 0, min_pts_per_plane: int = 4, rng_states=None,
+                            cap=None, labels_out=None, ctx: Optional[Context] = None) -> list:
+    """A batch of estimateMultHomographys problems in ONE library call (mlpl_mult_homographies_batch_dev), inputs as homography_arrsac_batch.
+    cap (planes the arrays hold per problem) defaults to the most the largest problem can report.  Returns one dict per problem with the
+    keys of mult_homographies_device (rc, n_planes, H, num_inl, strength, th_used, found_at) plus ok (False: fewer than 4 correspondences)
+    and rng_state; labels through labels_out (int32 CUDA tensor [B, stride]: output plane or -1 over counts[b])."""
+    import torch
+
+    ctx = ctx or default_context()
+    B, stride, cn, st = _plane_batch_inputs(d_p1, d_p2, counts, rng_states)
+    cap = max(_plane_cap(int(cn.max()) if B else 0, min_pts_per_plane, max_planes), 1) if cap is None else int(cap)
+    if labels_out is None:
+        labels_out = torch.full((B, stride), -1, dtype=torch.int32, device=d_p1.device)
+    assert labels_out.is_cuda and labels_out.dtype == torch.int32 and labels_out.shape == (B, stride) and labels_out.is_contiguous()
+    c1 = max(cap, 1)
+    npl, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    H, num, strength, thu, found = np.zeros((B, c1, 3, 3)), np.zeros((B, c1), np.int32), np.zeros((B, c1)), np.zeros((B, c1)), np.zeros((B, c1), np.int32)
+    rc = ctx.lib.mlpl_mult_homographies_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, float(th), 1 if var_th else 0,
+                                                  int(max_planes), int(min_pts_per_plane), st.ctypes.data, cap, npl.ctypes.data, H.ctypes.data,
+                                                  num.ctypes.data, strength.ctypes.data, thu.ctypes.data, found.ctypes.data, labels_out.data_ptr(),
+                                                  status.ctypes.data, torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_mult_homographies_batch_dev", _lib.last_error())
+    out = []
+    for b in range(B):
+        k = max(int(npl[b]), 0)
+        out.append(dict(ok=bool(status[b] == 0), rc=-1 if npl[b] < 0 else 0, n_planes=k, H=H[b, :k].copy(), num_inl=num[b, :k].copy(),
+                        strength=strength[b, :k].copy(), th_used=thu[b, :k].copy(), found_at=found[b, :k].copy(), rng_state=st[b].copy()))
+    return out
+
+
 def homography_sample_models(p1, p2, idx, ctx: Optional[Context] = None):
     """mlpl_debug_homography_models: the device's estimator on index lists idx [count, m] -> (H [count,3,3], ok [count])."""
     ctx = ctx or default_context()

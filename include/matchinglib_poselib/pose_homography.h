@@ -1,10 +1,11 @@
-// pose_homography.h -- the two self-contained functions of the reference's poselib/pose_homography.h on the MI355X:
-// computeHomographyArrsac and estimateMultHomographys (P/source/pose_homography.cpp:291-555), with the reference's signatures and
-// defaults.  estimatePoseHomographies (the Halign option) is not provided.
+// pose_homography.h -- the reference's poselib/pose_homography.h on the MI355X: estimatePoseHomographies (the pose of a scene of
+// planes by homography alignment, what the harnesses' --Halign calls), computeHomographyArrsac and estimateMultHomographys
+// (P/source/pose_homography.cpp:127-555), with the reference's signatures and defaults.  StereoRefine's Halign switch is not wired to
+// it yet (it keeps returning -1 with its message).
 //
 // Shapes: without OpenCV (cv_compat.h: single-channel matrices only) the points are n x 2 CV_64F, the single-channel view of the
 // reference's n x 1 CV_64FC2; estimateMultHomographys takes n x 2 CV_64F as in the reference.  A wrong shape throws cv::Exception
-// (the reference's CV_Assert).  Both functions draw from the process-wide pair of cv::RNG streams that estimateEssentialMat's ARRSAC uses
+// (the reference's CV_Assert).  All three functions draw from the process-wide pair of cv::RNG streams that estimateEssentialMat's ARRSAC uses
 // (setArrsacRngState / getArrsacRngState, pose_estim.h): in the reference the samplers' streams are function-local statics shared by
 // every theia::Arrsac instantiation.
 #pragma once
@@ -27,5 +28,15 @@ int estimateMultHomographys(cv::InputArray p1, cv::InputArray p2, double th, std
                             std::vector<std::pair<cv::Mat, cv::Mat>> *inl_points = nullptr, std::vector<cv::Mat> *Hs = nullptr,
                             std::vector<unsigned int> *num_inl = nullptr, bool varTh = true, std::vector<double> *planeStrength = nullptr,
                             unsigned int maxPlanes = 0, unsigned int minPtsPerPlane = 4);
+
+// Return value as in the reference: 0; -1 no plane found; -2 the planes are too weak (checkPlaneStrength: the strengths above 0.1 must sum
+// to more than 0.5); -3 the homography alignment failed (one plane only, a pure rotation, ...: mlpl_c.h lists the cases); -4 R or t was
+// not requested (checked after the alignment, as in the reference).  p1, p2: n x 2 CV_64F in camera coordinates.  R (3 x 3), t (3 x 1),
+// E (3 x 3, optional) CV_64F; inliers and mask (1 x n CV_8U): computeReprojError2 < th^2 over all n rows.  A non-empty mask on entry
+// selects the rows the planes are searched in.  The optional vectors are assigned (not appended to) on success only.
+int estimatePoseHomographies(cv::InputArray p1, cv::InputArray p2, cv::OutputArray R, cv::OutputArray t, cv::OutputArray E, double th, int &inliers,
+                             cv::InputOutputArray mask = cv::noArray(), bool checkPlaneStrength = false, bool varTh = false,
+                             std::vector<std::pair<cv::Mat, cv::Mat>> *inlier_points = nullptr, std::vector<unsigned int> *numbersHinliers = nullptr,
+                             std::vector<cv::Mat> *homographies = nullptr, std::vector<double> *planeStrengths = nullptr);
 
 }  // namespace poselib

@@ -606,6 +606,63 @@ int mlpl_mult_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double
                                      int var_th, unsigned max_planes, unsigned min_pts_per_plane, uint64_t *rng_states, int cap, int32_t *n_planes,
                                      double *H, int32_t *num_inl, double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, int32_t *status,
                                      void *stream);
+/*
+ * Pose from planes: the second half of poselib::estimatePoseHomographies (pose_homography.h, pose_homography.cpp:127-269).
+ *
+ * mlpl_homography_alignment[_dev]: Homographys_Alignment (HomographyAlignment.cpp:197-360) and its caller's part (ComputeHomographyMotion
+ * :82-171, pose_homography.cpp:195-213), the building block without any plane search: n correspondences in camera coordinates with one
+ * label each (the plane, or -1 = none: what mlpl_mult_homographies_labels writes), n_planes planes with num_inl[k] correspondences
+ * (plane 0 the dominant one), H0 = plane 0's homography, tol = the inlier threshold.  One workgroup runs the whole problem in one
+ * launch (csrc/homography_align_impl.h).  Outputs: R (the rotation from camera 1 to camera 2), t (minus the position of camera 2 in
+ * camera 1's frame, unit length), E = [t]x R as the reference forms it, norms [n_planes][3] (plane k: norms_k . P1 = 1 up to the scale
+ * of t), Hs_out [n_planes][9] the planes' homographies R (I - t' n_k^T) / h22 under the common motion, and
+ * info[24]: [0] the code -- 0, or -3 "Homography alignment failed" --, [1] the chosen candidate q, [2..5] / [6..9] the rounds run in each
+ * of the 4 outer turns for q = 0 / 1 (0 = turn not run), [10] [11] the last mean transfer error per q, [12..15] the motion errors (the
+ * two initial candidates, the two results), [16] the sign-candidate choices (bit 4 q + turn), [17] the reason of a -3: 1 a
+ * Longuet-Higgins decomposition refused the matrix, 2 fewer than two of its sign candidates have plane(2) > 0, 3 no ray pair counted in
+ * Check_motion_error, 4 a result is not finite (a pure rotation ends here), 5 fewer than two planes (the reference's defined answer),
+ * 6 a plane without correspondences; 1-4 and 6 are cases in which the reference reads unset memory or divides by zero.
+ * The calls return 0 for the code -3 too, and then write nothing but info.  MLPL_E_BAD_INPUT (nothing launched): null pointers, n < 1,
+ * n_planes outside [0, 64], tol not positive and finite, a label >= n_planes, num_inl not matching the labels.
+ * The _dev form takes d_p1, d_p2, d_labels on the device (the labels are read back once to check them); everything else is host memory.
+ */
+int mlpl_homography_alignment(mlpl_ctx *ctx, const double *p1, const double *p2, const int32_t *labels, int n, int n_planes, const int32_t *num_inl,
+                              const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms, double *Hs_out, double info[24]);
+int mlpl_homography_alignment_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, const int32_t *d_labels, int n, int n_planes,
+                                  const int32_t *num_inl, const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms,
+                                  double *Hs_out, double info[24], void *stream);
+/*
+ * mlpl_pose_homographies[_dev]: the whole of estimatePoseHomographies -- the rows the optional input mask keeps (mask_in may be NULL;
+ * order kept), mlpl_mult_homographies_labels on them with (th, var_th, MAX_PLANES_PER_PAIR = 50, MIN_PTS_PLANE = 15), with
+ * check_plane_strength the gate "the strengths above 0.1 sum to more than 0.5", the alignment above with tol = th, and the mask
+ * computeReprojError2 < th^2 (strict) over ALL n rows.  *result = the reference's return value: 0, -1 (no plane found), -2 (the planes
+ * are too weak), -3 (alignment failed; fewer than 4 kept rows end here or at -2, because the reference's plane loop then reports no
+ * plane); the call itself returns 0 for all four.  R, t, E, *n_inliers and mask_out (n bytes) are written only with *result == 0.
+ * Optional, all NULL or all set with cap >= 1: *n_planes, H [cap][9], num_inl [cap], strength [cap] -- the planes in the reference's
+ * order, written whenever the plane search ran (finding more than cap planes is MLPL_E_BAD_INPUT with rng_state put back).  labels (may be
+ * NULL; n int32): the plane of every KEPT row, in the kept rows' order.  info (may be NULL): the alignment's 24 doubles.  rng_state as in
+ * mlpl_homography_arrsac.  The _dev form takes d_p1, d_p2, d_mask_in, d_mask_out and d_labels on the device.
+ */
+int mlpl_pose_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask_in, double th, int check_plane_strength, int var_th,
+                           uint64_t rng_state[2], int *result, double R[9], double t[3], double E[9], int *n_inliers, uint8_t *mask_out, int cap,
+                           int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *labels, double *info);
+int mlpl_pose_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const uint8_t *d_mask_in, double th, int check_plane_strength,
+                               int var_th, uint64_t rng_state[2], int *result, double R[9], double t[3], double E[9], int *n_inliers, uint8_t *d_mask_out,
+                               int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *d_labels, double *info, void *stream);
+/* A batch of estimatePoseHomographies problems in one call, laid out as mlpl_mult_homographies_batch_dev (no input masks): problem b =
+ * d_p1 / d_p2 + b * stride * 2 doubles (device), counts[b] in [0, stride] rows (host), the stream pair rng_states[2 b], [2 b + 1] (host,
+ * in / out).  Every problem runs the single entry's sequential program as a fiber (csrc/batch_hub.h); the launches of the runs that
+ * stand at the same point are merged -- the alignment, the final mask and the copies of their results are ONE launch each per cohort.
+ * Per problem: results[b] (0 / -1 / -2 / -3), R + 9 b, t + 3 b, E + 9 b, n_inliers[b] and the mask at d_masks + b * stride (device) --
+ * these five written only with results[b] == 0 --, n_planes[b] and cap planes each of H [b][cap][9], num_inl, strength [b][cap], the
+ * labels at d_labels + b * stride (device, may be NULL), info + 24 b (may be NULL), status[b] (0, or the error that ended the call).
+ * Every problem's outputs and stream states are byte for byte what mlpl_pose_homographies_dev returns for it alone.  Malformed calls
+ * (null required pointers, n_problems < 0, stride < 1, a counts[b] outside [0, stride], th not positive and finite, cap < 1) are
+ * MLPL_E_BAD_INPUT with nothing launched; more than cap planes in a problem is MLPL_E_BAD_INPUT with that problem's streams put back. */
+int mlpl_pose_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                     int check_plane_strength, int var_th, uint64_t *rng_states, int32_t *results, double *R, double *t, double *E,
+                                     int32_t *n_inliers, uint8_t *d_masks, int cap, int32_t *n_planes, double *H, int32_t *num_inl, double *strength,
+                                     int32_t *d_labels, double *info, int32_t *status, void *stream);
 /* The homography estimators on `count` samples of m indices each (idx [count][m], 4 <= m <= 12), a building block exposed for parity
  * tests (the twin of mlpl_arrsac_sample_models): m == 4 the minimal DLT, m > 4 findHomography(., ., 0) with the reference's rejection.
  * H [count][9], ok [count] (0 = the normalisation refused the sample or the model was rejected). */

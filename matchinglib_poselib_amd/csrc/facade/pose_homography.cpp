@@ -1,5 +1,5 @@
-// pose_homography.cpp -- poselib::computeHomographyArrsac / estimateMultHomographys (P/source/pose_homography.cpp:291-555) over
-// mlpl_homography_arrsac / mlpl_mult_homographies.  Host glue only: the reference's argument checks, cv::Mat <-> pointer plumbing, its
+// pose_homography.cpp -- poselib::estimatePoseHomographies / computeHomographyArrsac / estimateMultHomographys
+// (P/source/pose_homography.cpp:127-555) over mlpl_pose_homographies / mlpl_homography_arrsac / mlpl_mult_homographies.  Host glue only: the reference's argument checks, cv::Mat <-> pointer plumbing, its
 // output behaviour (assign or append), and the process-wide stream pair shared with estimateEssentialMat.
 #include <algorithm>
 #include <cstring>
@@ -111,6 +111,72 @@ int estimateMultHomographys(cv::InputArray p1, cv::InputArray p2, double th, std
     });
     put(num_inl, [&](int k) { return (unsigned int)num[k]; });
     put(planeStrength, [&](int k) { return strength[k]; });
+    return 0;
+}
+
+int estimatePoseHomographies(cv::InputArray p1, cv::InputArray p2, cv::OutputArray R, cv::OutputArray t, cv::OutputArray E, double th, int &inliers,
+                             cv::InputOutputArray mask, bool checkPlaneStrength, bool varTh, std::vector<std::pair<cv::Mat, cv::Mat>> *inlier_points,
+                             std::vector<unsigned int> *numbersHinliers, std::vector<cv::Mat> *homographies, std::vector<double> *planeStrengths) {
+    const int n = p1.rows();
+    CV_Assert(n == p2.rows() && n > 0 && p1.cols() == 2 && p2.cols() == 2 && p1.type() == CV_64F && p2.type() == CV_64F);
+    std::vector<double> a, b;
+    flatten(p1.getMat(), a), flatten(p2.getMat(), b);
+    std::vector<uint8_t> m_in, m_out((size_t)n);
+    if (!mask.empty()) {  // :153-164: a non-empty mask selects the rows the planes are searched in
+        cv::Mat mm = mask.getMat();
+        CV_Assert(mm.type() == CV_8U && mm.rows * mm.cols == n);
+        m_in.assign(mm.data, mm.data + n);
+    }
+    constexpr int cap = 50;  // MAX_PLANES_PER_PAIR
+    double Rv[9], tv[3], Ev[9], Hv[cap * 9], strength[cap];
+    int32_t num[cap];
+    std::vector<int32_t> labels((size_t)n, -1);
+    int result = 0, ninl = 0, n_planes = 0, rc;
+    {
+        mlpl_facade_arrsac_rng_lock lock;
+        rc = mlpl_pose_homographies(mlpl_facade_default_ctx(), a.data(), b.data(), n, m_in.empty() ? nullptr : m_in.data(), th, checkPlaneStrength ? 1 : 0,
+                                    varTh ? 1 : 0, lock.state, &result, Rv, tv, Ev, &ninl, m_out.data(), cap, &n_planes, Hv, num, strength,
+                                    inlier_points ? labels.data() : nullptr, nullptr);
+    }
+    if (rc != MLPL_OK) throw cv::Exception(std::string("estimatePoseHomographies: ") + mlpl_last_error());
+    if (result != 0) return result;
+    if (!t.needed()) return -4;  // :199-207: checked after the alignment, t before R, as in the reference
+    t.create(3, 1, CV_64F);
+    std::memcpy(t.getMat().data, tv, 24);
+    if (!R.needed()) return -4;
+    R.create(3, 3, CV_64F);
+    std::memcpy(R.getMat().data, Rv, 72);
+    if (E.needed()) {
+        E.create(3, 3, CV_64F);
+        std::memcpy(E.getMat().data, Ev, 72);
+    }
+    inliers = ninl;
+    if (mask.needed()) {
+        if (mask.empty()) mask.create(1, n, CV_8U);
+        std::memcpy(mask.getMat().data, m_out.data(), (size_t)n);
+    }
+    if (planeStrengths) planeStrengths->assign(strength, strength + n_planes);
+    if (inlier_points) {  // the planes' correspondences among the rows the input mask kept
+        std::vector<double> ka, kb;
+        for (int i = 0; i < n; ++i)
+            if (m_in.empty() || m_in[(size_t)i]) ka.push_back(a[2 * i]), ka.push_back(a[2 * i + 1]), kb.push_back(b[2 * i]), kb.push_back(b[2 * i + 1]);
+        const int kept = (int)(ka.size() / 2);
+        inlier_points->clear();
+        std::vector<uint8_t> sel((size_t)std::max(kept, 1));
+        for (int k = 0; k < n_planes; ++k) {
+            for (int i = 0; i < kept; ++i) sel[(size_t)i] = labels[(size_t)i] == k;
+            inlier_points->push_back(std::make_pair(rows_of(ka, sel.data(), kept), rows_of(kb, sel.data(), kept)));
+        }
+    }
+    if (numbersHinliers) numbersHinliers->assign(num, num + n_planes);
+    if (homographies) {
+        homographies->clear();
+        for (int k = 0; k < n_planes; ++k) {
+            cv::Mat h(3, 3, CV_64F);
+            std::memcpy(h.data, Hv + 9 * k, 72);
+            homographies->push_back(h);
+        }
+    }
     return 0;
 }
 

@@ -36,6 +36,9 @@ enum HubKernelId {
     HK_HOM_REFINE,
     HK_HOM_FINAL,
     HK_HOM_PLANES_OUT,
+    HK_HOM_MASK_ROWS,  // ... and the rows an input mask keeps
+    HK_HOM_STRICT,     // ... and estimatePoseHomographies' final mask under the alignment's E
+    HK_HOM_ALIGN,      // homography_align_impl.h: Homographys_Alignment, a whole problem in one workgroup
     HK_NUM
 };
 static_assert(HK_NUM <= kHubMaxKernels, "kernel table too small");

@@ -70,6 +70,7 @@ enum WsSlot {
     WS_BA,              // bundle adjustment (bundle_adjust.hip): per-point state of every problem, then the compacted row lists
     WS_HOMOG,           // homography ARRSAC (homography_impl.h): packed correspondences, the models of every sample solved in a call, the compacted inliers
     WS_HOMOG_PLANES,    // estimateMultHomographys: the two point buffers the rounds alternate between, the round's mask, the planes' masks
+    WS_HOMOG_ALIGN,     // homography alignment (homography_align_impl.h): the result block and the correspondences sorted by plane
     WS_NUM_SLOTS
 };
 

@@ -7,6 +7,7 @@
 // One thread per correspondence; the same double->float rounding points as the reference, no FMA contraction.
 
 #include "mlpl_internal.h"
+#include "reproj_error2.h"
 
 namespace mlpl {
 namespace {
@@ -106,14 +107,7 @@ __global__ void inliers_strict_kernel(const double *__restrict__ p1, const doubl
     bool in = false;
     if (i < n) {
         const double x1 = p1[2 * i], y1 = p1[2 * i + 1], x2 = p2[2 * i], y2 = p2[2 * i + 1];
-        const double Ex1_0 = __dadd_rn(__dadd_rn(__dmul_rn(E[0], x1), __dmul_rn(E[1], y1)), E[2]);
-        const double Ex1_1 = __dadd_rn(__dadd_rn(__dmul_rn(E[3], x1), __dmul_rn(E[4], y1)), E[5]);
-        const double Ex1_2 = __dadd_rn(__dadd_rn(__dmul_rn(E[6], x1), __dmul_rn(E[7], y1)), E[8]);
-        const double x2tEx1 = __dadd_rn(__dadd_rn(__dmul_rn(x2, Ex1_0), __dmul_rn(y2, Ex1_1)), Ex1_2);
-        const double Etx2_0 = __dadd_rn(__dadd_rn(__dmul_rn(E[0], x2), __dmul_rn(E[3], y2)), E[6]);
-        const double Etx2_1 = __dadd_rn(__dadd_rn(__dmul_rn(E[1], x2), __dmul_rn(E[4], y2)), E[7]);
-        const double a = __dmul_rn(Ex1_0, Ex1_0), b = __dmul_rn(Ex1_1, Ex1_1), c = __dmul_rn(Etx2_0, Etx2_0), d = __dmul_rn(Etx2_1, Etx2_1);
-        const double e = __ddiv_rn(__dmul_rn(x2tEx1, x2tEx1), __dadd_rn(__dadd_rn(__dadd_rn(a, b), c), d));
+        const double e = reproj_error2_point(E, x1, y1, x2, y2);
         err[i] = e;
         in = e < th2;  // strict, pose_helper.cpp:3038
         mask[i] = in ? 1 : 0;
@@ -125,6 +119,7 @@ __global__ void inliers_strict_kernel(const double *__restrict__ p1, const doubl
 }
 
 }  // namespace
+
 }  // namespace mlpl
 
 using namespace mlpl;

@@ -59,6 +59,7 @@
 
 #include "mlpl_internal.h"
 #include "usac_degen_math.h"
+#include "reproj_error2.h"
 
 namespace mlpl {
 
@@ -3316,6 +3317,7 @@ void hub_streams_free(void *p) {
 }
 #include "arrsac_impl.h"
 #include "homography_impl.h"
+#include "homography_align_impl.h"
 #include "usac_impl.h"
 #include "pair_batch_impl.h"
 #include "pair_batch_usac.h"
@@ -4286,6 +4288,173 @@ int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *
     int rc;
     if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
     return homography_sample_models(ctx, (const double *)dp1, (const double *)dp2, n, idx, m, count, H, ok, ctx->stream);
+}
+
+// ---- pose from planes (homography_align_impl.h) ----
+// labels against P and num_inl: every label below P, exactly num_inl[k] labels k
+static bool alignment_labels_ok(const char *who, const int32_t *labels, int n, int P, const int32_t *num_inl) {
+    std::vector<int> cnt((size_t)std::max(P, 1), 0);
+    for (int i = 0; i < n; ++i) {
+        if (labels[i] >= P) {
+            set_error("%s: label %d of correspondence %d is not below the %d planes", who, labels[i], i, P);
+            return false;
+        }
+        if (labels[i] >= 0) ++cnt[(size_t)labels[i]];
+    }
+    for (int k = 0; k < P; ++k)
+        if (num_inl[k] != cnt[(size_t)k]) {
+            set_error("%s: num_inl[%d] = %d, but %d labels name plane %d", who, k, num_inl[k], cnt[(size_t)k], k);
+            return false;
+        }
+    return true;
+}
+static bool alignment_args_ok(const char *who, mlpl_ctx *ctx, const void *p1, const void *p2, const void *labels, int n, int P, const int32_t *num_inl,
+                              const double *H0, double tol, const double *R, const double *t, const double *E, const double *norms, const double *Hs_out,
+                              const double *info) {
+    if (!ctx || !p1 || !p2 || !labels || !num_inl || !H0 || !R || !t || !E || !norms || !Hs_out || !info || n < 1 || P < 0 || P > kAlignMaxPlanes ||
+        !(tol > 0) || !std::isfinite(tol)) {
+        set_error("%s: bad arguments (n >= 1, 0 <= planes <= %d, tol positive and finite)", who, kAlignMaxPlanes);
+        return false;
+    }
+    for (int k = 0; k < P; ++k)
+        if (num_inl[k] < 0) {
+            set_error("%s: num_inl[%d] is negative", who, k);
+            return false;
+        }
+    return true;
+}
+static int alignment_checked(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, const int32_t *d_labels, int n, int P, const int32_t *num_inl,
+                             const double *H0, double tol, double *R, double *t, double *E, double *norms, double *Hs_out, double *info, hipStream_t s) {
+    for (int k = 0; k < P && P >= 2; ++k)
+        if (num_inl[k] == 0) {  // a plane without correspondences: defined failure 6, nothing launched
+            for (int i = 0; i < kAlignInfo; ++i) info[i] = 0;
+            info[0] = -3, info[17] = 6;
+            return MLPL_OK;
+        }
+    return homography_alignment_dev(ctx, d_p1, d_p2, d_labels, n, P, num_inl, H0, tol, R, t, E, norms, Hs_out, info, s);
+}
+
+int mlpl_homography_alignment_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, const int32_t *d_labels, int n, int n_planes, const int32_t *num_inl,
+                                  const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms, double *Hs_out, double info[24],
+                                  void *stream) {
+    static const char *who = "mlpl_homography_alignment_dev";
+    if (!alignment_args_ok(who, ctx, d_p1, d_p2, d_labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info)) return MLPL_E_BAD_INPUT;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = pick_stream(ctx, stream);
+    try {
+        std::vector<int32_t> lab((size_t)n);
+        MLPL_HIP_TRY(hipMemcpyAsync(lab.data(), d_labels, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        MLPL_HIP_TRY(hipStreamSynchronize(s));
+        if (!alignment_labels_ok(who, lab.data(), n, n_planes, num_inl)) return MLPL_E_BAD_INPUT;
+        return alignment_checked(ctx, d_p1, d_p2, d_labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info, s);
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+}
+
+int mlpl_homography_alignment(mlpl_ctx *ctx, const double *p1, const double *p2, const int32_t *labels, int n, int n_planes, const int32_t *num_inl,
+                              const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms, double *Hs_out, double info[24]) {
+    static const char *who = "mlpl_homography_alignment";
+    if (!alignment_args_ok(who, ctx, p1, p2, labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info)) return MLPL_E_BAD_INPUT;
+    try {
+        if (!alignment_labels_ok(who, labels, n, n_planes, num_inl)) return MLPL_E_BAD_INPUT;
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    void *dp1, *dp2, *dlab;
+    int rc;
+    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
+    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n * 4, &dlab))) return rc;
+    MLPL_HIP_TRY(hipMemcpyAsync(dlab, labels, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    try {
+        return alignment_checked(ctx, (const double *)dp1, (const double *)dp2, (const int32_t *)dlab, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out,
+                                 info, ctx->stream);
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+}
+
+static bool pose_homographies_args_ok(const char *who, mlpl_ctx *ctx, const void *p1, const void *p2, int n, double th, const uint64_t *rng_state,
+                                      const int *result, const double *R, const double *t, const double *E, const int *n_inliers, const void *mask_out, int cap,
+                                      const int *n_planes, const double *H, const int32_t *num_inl, const double *strength) {
+    const int planes_set = (n_planes != nullptr) + (H != nullptr) + (num_inl != nullptr) + (strength != nullptr);
+    if (!ctx || !p1 || !p2 || !rng_state || !result || !R || !t || !E || !n_inliers || !mask_out || n < 1 || !(th > 0) || !std::isfinite(th) ||
+        (planes_set != 0 && (planes_set != 4 || cap < 1))) {
+        set_error("%s: bad arguments (n >= 1, th positive and finite; n_planes, H, num_inl, strength all null or all set with cap >= 1)", who);
+        return false;
+    }
+    return true;
+}
+
+int mlpl_pose_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const uint8_t *d_mask_in, double th, int check_plane_strength,
+                               int var_th, uint64_t rng_state[2], int *result, double R[9], double t[3], double E[9], int *n_inliers, uint8_t *d_mask_out,
+                               int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *d_labels, double *info, void *stream) {
+    static const char *who = "mlpl_pose_homographies_dev";
+    if (!pose_homographies_args_ok(who, ctx, d_p1, d_p2, n, th, rng_state, result, R, t, E, n_inliers, d_mask_out, cap, n_planes, H, num_inl, strength))
+        return MLPL_E_BAD_INPUT;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    try {
+        return pose_homographies_dev(ctx, d_p1, d_p2, n, d_mask_in, th, check_plane_strength, var_th, rng_state, result, R, t, E, n_inliers, d_mask_out, cap,
+                                     n_planes, H, num_inl, strength, d_labels, info, pick_stream(ctx, stream));
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+}
+
+int mlpl_pose_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
+                                     int check_plane_strength, int var_th, uint64_t *rng_states, int32_t *results, double *R, double *t, double *E,
+                                     int32_t *n_inliers, uint8_t *d_masks, int cap, int32_t *n_planes, double *H, int32_t *num_inl, double *strength,
+                                     int32_t *d_labels, double *info, int32_t *status, void *stream) {
+    static const char *who = "mlpl_pose_homographies_batch_dev";
+    if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || !results || !R || !t || !E || !n_inliers || !d_masks || cap < 1 ||
+        !n_planes || !H || !num_inl || !strength || !status || !(th > 0) || !std::isfinite(th)) {
+        set_error("%s: bad arguments", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    if (!homography_batch_counts_ok(who, n_problems, counts, stride)) return MLPL_E_BAD_INPUT;
+    if (n_problems == 0) return MLPL_OK;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    try {
+        return pose_homographies_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, check_plane_strength, var_th, rng_states, results, R, t, E,
+                                           n_inliers, d_masks, cap, n_planes, H, num_inl, strength, d_labels, info, status, pick_stream(ctx, stream));
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+}
+
+int mlpl_pose_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask_in, double th, int check_plane_strength, int var_th,
+                           uint64_t rng_state[2], int *result, double R[9], double t[3], double E[9], int *n_inliers, uint8_t *mask_out, int cap,
+                           int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *labels, double *info) {
+    static const char *who = "mlpl_pose_homographies";
+    if (!pose_homographies_args_ok(who, ctx, p1, p2, n, th, rng_state, result, R, t, E, n_inliers, mask_out, cap, n_planes, H, num_inl, strength))
+        return MLPL_E_BAD_INPUT;
+    MLPL_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    void *dp1, *dp2, *dmasks, *dlab;
+    int rc;
+    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
+    const size_t mask_b = (((size_t)n + 255) / 256) * 256;
+    if ((rc = ws_get(ctx, WS_AUX6, 2 * mask_b, &dmasks))) return rc;
+    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n * 4, &dlab))) return rc;
+    uint8_t *d_in = (uint8_t *)dmasks, *d_out = d_in + mask_b;
+    if (mask_in) MLPL_HIP_TRY(hipMemcpyAsync(d_in, mask_in, (size_t)n, hipMemcpyHostToDevice, s));
+    try {
+        rc = pose_homographies_dev(ctx, (const double *)dp1, (const double *)dp2, n, mask_in ? d_in : nullptr, th, check_plane_strength, var_th, rng_state,
+                                   result, R, t, E, n_inliers, d_out, cap, n_planes, H, num_inl, strength, (int32_t *)dlab, info, s);
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    }
+    if (rc) return rc;
+    if (*result == 0) MLPL_HIP_TRY(hipMemcpy(mask_out, d_out, (size_t)n, hipMemcpyDeviceToHost));
+    if (labels && n_planes && *n_planes > 0) MLPL_HIP_TRY(hipMemcpy(labels, dlab, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return MLPL_OK;
 }
 
 int mlpl_robust_essential_refine(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask, const double E_init[9],

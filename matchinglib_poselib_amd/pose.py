@@ -648,6 +648,137 @@ def mult_homographies_batch(d_p1, d_p2, counts, th: float, var_th: bool = True, 
     return out
 
 
+POSE_HOM_MAX_PLANES = 50   # MAX_PLANES_PER_PAIR of the reference's pose_homography.cpp
+
+
+def homography_alignment(p1, p2, labels, n_planes: int, num_inl, H0, tol: float, ctx: Optional[Context] = None) -> dict:
+    """Homographys_Alignment and its caller's part (mlpl_homography_alignment): the pose from labelled plane correspondences, no plane
+    search inside.  code = 0 or -3; with 0: R, t, E, norms [n_planes, 3], Hs [n_planes, 3, 3]; info = the 24 doubles of mlpl_c.h."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n, P = p1.shape[0], int(n_planes)
+    labels = np.ascontiguousarray(labels, np.int32)
+    num = np.ascontiguousarray(num_inl, np.int32)
+    assert labels.shape == (n,) and num.shape == (P,)
+    H0 = np.ascontiguousarray(H0, np.float64).reshape(3, 3)
+    R, t, E, info = np.zeros((3, 3)), np.zeros(3), np.zeros((3, 3)), np.zeros(24)
+    norms, Hs = np.zeros((max(P, 1), 3)), np.zeros((max(P, 1), 3, 3))
+    check(ctx.lib.mlpl_homography_alignment(ctx.handle, p1.ctypes.data, p2.ctypes.data, labels.ctypes.data, n, P, num.ctypes.data if P else labels.ctypes.data,
+                                            H0.ctypes.data, float(tol), R.ctypes.data, t.ctypes.data, E.ctypes.data, norms.ctypes.data, Hs.ctypes.data,
+                                            info.ctypes.data), "mlpl_homography_alignment")
+    return dict(code=int(info[0]), R=R, t=t, E=E, norms=norms[:P], Hs=Hs[:P], info=info)
+
+
+def _pose_hom_result(result, R, t, E, ninl, npl, H, num, strength, info):
+    k = max(npl.value, 0)
+    return dict(result=result.value, R=R, t=t, E=E, n_inliers=ninl.value, n_planes=npl.value, H=H[:k].copy(), num_inl=num[:k].copy(),
+                strength=strength[:k].copy(), info=info)
+
+
+def pose_homographies(p1, p2, th: float, mask=None, check_plane_strength: bool = False, var_th: bool = False, rng_state=None,
+                      ctx: Optional[Context] = None) -> dict:
+    """poselib::estimatePoseHomographies (mlpl_pose_homographies): result = 0 / -1 / -2 / -3 as the reference; with 0: R, t, E, the strict
+    mask over all rows and n_inliers.  n_planes, H, num_inl, strength describe the planes found; labels: the plane of every row the input
+    mask kept (in the kept rows' order)."""
+    ctx = ctx or default_context()
+    p1, p2 = _pts(p1), _pts(p2)
+    n = p1.shape[0]
+    st = _rng_pair(rng_state)
+    m_in = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, np.uint8)
+    assert m_in is None or m_in.shape == (n,)
+    cap = POSE_HOM_MAX_PLANES
+    result, ninl, npl = C.c_int(0), C.c_int(0), C.c_int(0)
+    R, t, E, info = np.zeros((3, 3)), np.zeros(3), np.zeros((3, 3)), np.zeros(24)
+    H, num, strength = np.zeros((cap, 3, 3)), np.zeros(cap, np.int32), np.zeros(cap)
+    mask_out, labels = np.zeros(max(n, 1), np.uint8), np.full(max(n, 1), -1, np.int32)
+    check(ctx.lib.mlpl_pose_homographies(ctx.handle, p1.ctypes.data, p2.ctypes.data, n, None if m_in is None else m_in.ctypes.data, float(th),
+                                         1 if check_plane_strength else 0, 1 if var_th else 0, st.ctypes.data, C.addressof(result), R.ctypes.data,
+                                         t.ctypes.data, E.ctypes.data, C.addressof(ninl), mask_out.ctypes.data, cap, C.addressof(npl), H.ctypes.data,
+                                         num.ctypes.data, strength.ctypes.data, labels.ctypes.data, info.ctypes.data), "mlpl_pose_homographies")
+    out = _pose_hom_result(result, R, t, E, ninl, npl, H, num, strength, info)
+    kept = n if m_in is None else int(m_in.sum())
+    out.update(mask=mask_out[:n], labels=labels[:kept])
+    return out
+
+
+def pose_homographies_device(p1, p2, th: float, mask=None, check_plane_strength: bool = False, var_th: bool = False, rng_state=None,
+                             ctx: Optional[Context] = None, stream: Optional[int] = None) -> dict:
+    """pose_homographies on device-resident torch tensors (float64 [n,2]; mask: uint8 [n] or None); the output mask and the labels stay on
+    the device."""
+    import torch
+
+    assert p1.is_cuda and p2.is_cuda and p1.dtype == torch.float64 and p1.is_contiguous() and p2.is_contiguous()
+    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == (p1.shape[0],))
+    ctx = ctx or default_context(p1.device.index or 0)
+    n = p1.shape[0]
+    st = _rng_pair(rng_state)
+    cap = POSE_HOM_MAX_PLANES
+    result, ninl, npl = C.c_int(0), C.c_int(0), C.c_int(0)
+    R, t, E, info = np.zeros((3, 3)), np.zeros(3), np.zeros((3, 3)), np.zeros(24)
+    H, num, strength = np.zeros((cap, 3, 3)), np.zeros(cap, np.int32), np.zeros(cap)
+    mask_out = torch.zeros(max(n, 1), dtype=torch.uint8, device=p1.device)
+    labels = torch.full((max(n, 1),), -1, dtype=torch.int32, device=p1.device)
+    sm = torch.cuda.current_stream(p1.device).cuda_stream if stream is None else stream
+    check(ctx.lib.mlpl_pose_homographies_dev(ctx.handle, p1.data_ptr(), p2.data_ptr(), n, None if mask is None else mask.data_ptr(), float(th),
+                                             1 if check_plane_strength else 0, 1 if var_th else 0, st.ctypes.data, C.addressof(result), R.ctypes.data,
+                                             t.ctypes.data, E.ctypes.data, C.addressof(ninl), mask_out.data_ptr(), cap, C.addressof(npl), H.ctypes.data,
+                                             num.ctypes.data, strength.ctypes.data, labels.data_ptr(), info.ctypes.data, sm), "mlpl_pose_homographies_dev")
+    out = _pose_hom_result(result, R, t, E, ninl, npl, H, num, strength, info)
+    out.update(mask=mask_out[:n], labels=labels[:n])
+    return out
+
+
+def pose_homographies_batch(d_p1, d_p2, counts, th: float, check_plane_strength: bool = False, var_th: bool = False, rng_states=None,
+                            masks_out=None, labels_out=None, ctx: Optional[Context] = None) -> list:
+    """A batch of estimatePoseHomographies problems in ONE library call (mlpl_pose_homographies_batch_dev), inputs as
+    mult_homographies_batch.  Returns one dict per problem with the keys of pose_homographies_device (result, R, t, E, n_inliers,
+    n_planes, H, num_inl, strength, info) plus rng_state; masks through masks_out (uint8 CUDA tensor [B, stride]), labels through
+    labels_out (int32 CUDA tensor [B, stride])."""
+    import torch
+
+    ctx = ctx or default_context()
+    B, stride, cn, st = _plane_batch_inputs(d_p1, d_p2, counts, rng_states)
+    cap = POSE_HOM_MAX_PLANES
+    if masks_out is None:
+        masks_out = torch.zeros((B, stride), dtype=torch.uint8, device=d_p1.device)
+    if labels_out is None:
+        labels_out = torch.full((B, stride), -1, dtype=torch.int32, device=d_p1.device)
+    assert masks_out.is_cuda and masks_out.dtype == torch.uint8 and masks_out.shape == (B, stride) and masks_out.is_contiguous()
+    assert labels_out.is_cuda and labels_out.dtype == torch.int32 and labels_out.shape == (B, stride) and labels_out.is_contiguous()
+    res, ninl, npl, status = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    R, t, E, info = np.zeros((B, 3, 3)), np.zeros((B, 3)), np.zeros((B, 3, 3)), np.zeros((B, 24))
+    H, num, strength = np.zeros((B, cap, 3, 3)), np.zeros((B, cap), np.int32), np.zeros((B, cap))
+    rc = ctx.lib.mlpl_pose_homographies_batch_dev(ctx.handle, B, d_p1.data_ptr(), d_p2.data_ptr(), stride, cn.ctypes.data, float(th),
+                                                  1 if check_plane_strength else 0, 1 if var_th else 0, st.ctypes.data, res.ctypes.data, R.ctypes.data,
+                                                  t.ctypes.data, E.ctypes.data, ninl.ctypes.data, masks_out.data_ptr(), cap, npl.ctypes.data, H.ctypes.data,
+                                                  num.ctypes.data, strength.ctypes.data, labels_out.data_ptr(), info.ctypes.data, status.ctypes.data,
+                                                  torch.cuda.current_stream(d_p1.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_pose_homographies_batch_dev", _lib.last_error())
+    out = []
+    for b in range(B):
+        k = max(int(npl[b]), 0)
+        out.append(dict(result=int(res[b]), R=R[b].copy(), t=t[b].copy(), E=E[b].copy(), n_inliers=int(ninl[b]), n_planes=int(npl[b]), H=H[b, :k].copy(),
+                        num_inl=num[b, :k].copy(), strength=strength[b, :k].copy(), info=info[b].copy(), rng_state=st[b].copy()))
+    return out
+
+
+def estimatePoseHomographies(p1, p2, th: float, mask=None, checkPlaneStrength: bool = False, varTh: bool = False, ctx: Optional[Context] = None):
+    """The reference's signature in Python: (rc, R, t, E, inliers, mask, inlier_points, numbersHinliers, homographies, planeStrengths); the
+    process-wide stream pair, as its statics.  inlier_points: per plane the pair (left, right) of its correspondences among the rows the
+    input mask kept.  With rc != 0 everything but rc is None, as the reference leaves its outputs alone."""
+    q1, q2 = _pts(p1), _pts(p2)
+    r = pose_homographies(q1, q2, th, mask=mask, check_plane_strength=checkPlaneStrength, var_th=varTh, ctx=ctx)
+    if r["result"] != 0:
+        return r["result"], None, None, None, None, None, None, None, None, None
+    if mask is not None:
+        keep = np.asarray(mask).reshape(-1) != 0
+        q1, q2 = q1[keep], q2[keep]
+    pts = [(q1[r["labels"] == k].copy(), q2[r["labels"] == k].copy()) for k in range(r["n_planes"])]
+    return (0, r["R"], r["t"].reshape(3, 1), r["E"], r["n_inliers"], r["mask"].reshape(1, -1), pts, [int(v) for v in r["num_inl"]],
+            [h for h in r["H"]], [float(v) for v in r["strength"]])
+
+
 def homography_sample_models(p1, p2, idx, ctx: Optional[Context] = None):
     """mlpl_debug_homography_models: the device's estimator on index lists idx [count, m] -> (H [count,3,3], ok [count])."""
     ctx = ctx or default_context()

@@ -19,6 +19,7 @@
 #define CV_8U 0
 #define CV_32F 5
 #define CV_64F 6
+#define CV_32FC1 CV_32F
 
 namespace cv {
 
@@ -39,6 +40,11 @@ struct Size {
     int width = 0, height = 0;
     Size() = default;
     Size(int w, int h) : width(w), height(h) {}
+};
+struct Rect {   // cv::Rect_<int>
+    int x = 0, y = 0, width = 0, height = 0;
+    Rect() = default;
+    Rect(int x_, int y_, int w, int h) : x(x_), y(y_), width(w), height(h) {}
 };
 struct KeyPoint {
     Point2f pt;

@@ -412,6 +412,78 @@ int mlpl_subpix_separate_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matc
                              int width2, int height2, size_t step2, size_t batch_stride2, int correspondences_rule, mlpl_dmatch *d_out,
                              int32_t *d_n_out, int32_t *d_status, float *d_kp1_out, float *d_kp2_out, uint8_t *d_inlier, void *stream);
 
+/* ---- stereo rectification: poselib::getRectificationParameters, cv::initUndistortRectifyMap, poselib::GetRectifiedImages ----------
+ * The end of the reference harness' per-pair loop (T/poselib-test/main.cpp:2051-2070).  OpenCV is not in this tree: the arithmetic of
+ * cv::initUndistortRectifyMap and of cv::remap's fixed-point bilinear path is RESTATED from OpenCV 4.x as remembered, and the operation
+ * order of every entry is written down once, in tests/rectify_oracle.py, which the code follows line by line; that file is the definition.
+ * The maps and the images of the device equal it bit for bit / byte for byte.
+ *
+ * mlpl_rectify_parameters: getRectificationParameters with globRectFunct = true, i.e. rectifyFusiello (P/source/pose_helper.cpp:1366-1422,
+ * :1459-1857) with cvUndistortPoints2 (:2290-2412) and icvGetRectanglesV0 (:2429-2503).  Host arithmetic, no device, no context.
+ *   In: R[9], t[3] (divided by its norm when that is further than 1e-4 from 1, :1394-1397), K1[9], K2[9] (row major), dist1 / dist2 with
+ *   n_dist1 / n_dist2 in {0, 4, 5, 8} coefficients (k1, k2, p1, p2[, k3[, k4, k5, k6]]), the image size, alpha, the new image size
+ *   ((0, 0), or any size with a zero side: the image size).  Out: Rect1[9], Rect2[9], Knew[9] (K1new = K2new); optional roi[4] = {x, y,
+ *   width, height}, the intersection at :1819-1823 (the reference never writes its roi2 on this branch); optional P1[12], P2[12]; optional info[8] = {fc_new
+ *   before scaling, s0, s1 (both 0 when alpha < 0), s, and the number of 0.01 reduction steps each of the four undistortion loops took:
+ *   corners of camera 1, of camera 2, the 9 x 9 grid of camera 1, of camera 2}.
+ *   Kept from the reference: the float32 roundings of the Point2f corner and grid points (and the float32 arithmetic that forms the grid),
+ *   of cvUndistortPoints2's outputs, of the Rect_<float> rectangles (inner.x + inner.width is a float32 sum) and of the proofdist test
+ *   against 0.25 (float32 products, sum and root; a NaN passes); the in-place re-undistortion inside the corner loop (a valid corner returns
+ *   to its saved pixel position, an invalid one moves inwards by floor()); the coefficient-free pass once the reduction reaches 0.25; the
+ *   clamp of s to 1 outside [0.5, 2]; the focal length branch on dk1 < 0 and idx = |t.x| > |t.y| ? 0 : 1.
+ *   Deviations:
+ *   - The three 3 x 3 inverses (K1; K2 R; Knew) are adjugate over determinant in a fixed order; matrix products add their three terms
+ *     left to right.  OpenCV's own inverse and gemm may order differently (last bits).
+ *   - cv::projectPoints is handed the 3 x 3 Rect as its rotation; OpenCV passes it through Rodrigues and back, which moves an orthonormal
+ *     matrix at 1e-16.  The matrix is used directly.  cv::mean is the sum in order over 4.
+ *   - icvGetRectanglesV0 copies its grid into a std::vector and then undistorts the UNINITIALISED matrix the copy was made from, so what
+ *     the reference computes there depends on uninitialised memory.  Here the grid itself is undistorted, as in OpenCV's icvGetRectangles,
+ *     of which the function is a copy.
+ *   - n_dist = 0 is eight zeros (the reference asserts on an empty coefficient matrix).  The (int) casts of the roi saturate, NaN -> 0.
+ *   MLPL_E_BAD_INPUT: a NULL input or output matrix, a value that is not finite, t = 0, a size < 1, a negative new size, another n_dist.
+ *   The stereoRectify2 branch (globRectFunct = false) is not built.
+ *
+ * mlpl_rectify_maps / _dev: cv::initUndistortRectifyMap(K, dist, Rect, Knew, size, CV_32FC1, mapx, mapy).  All arithmetic in double, per
+ *   pixel (u = column, v = row), one lane for 4 adjacent pixels: ir = (Knew Rect)^-1 on the host as above; _x = u ir0 + (v ir1 + ir2), _y and
+ *   _w likewise; x = _x / _w, y = _y / _w; r2 = x x + y y; kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2);
+ *   xd = (x kr + p1 ((2 x) y)) + p2 (r2 + 2 x x), yd = (y kr + p1 (r2 + 2 y y)) + p2 ((2 x) y); mapx = (float)(fx xd + cx),
+ *   mapy = (float)(fy yd + cy) with fx, fy, cx, cy of K.  Deviation, unmeasured: OpenCV's scalar path accumulates _x += ir0 along a row;
+ *   the direct product can differ from it in the last float bit.  Host form: mapx, mapy [height][width] dense.  Device form: row stride
+ *   map_stride in floats (>= width), one launch on `stream`, no synchronisation.  Sides in [1, 16384].
+ *
+ * mlpl_remap_bilinear / _dev: cv::remap(img, out, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT (0)) on an 8-bit single-channel image,
+ *   OpenCV's fixed-point path: a = mapx * 32 in float32; sx = round-half-even(a), ix = sx >> 5 saturated to int16, fx = sx & 31, y likewise;
+ *   weights (32-fx)(32-fy) 32, fx (32-fy) 32, (32-fx) fy 32, fx fy 32 (sum 2^15) on the taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1);
+ *   value = (sum + 16384) >> 15; a tap outside the image adds 0.  (OpenCV stores the weight 32768 as 32767: immaterial, (32767 p + 16384)
+ *   >> 15 = p for every byte p.)  Safety: a map value that is NaN or whose product with 32 does not fit an int32 makes the pixel 0; image
+ *   sides above 16384 are MLPL_E_BAD_INPUT, so a saturated index is always outside; no source address is formed before its tap has passed
+ *   the inside test.  The maps are [out_height][out_width]; step / out_step in bytes (>= width).
+ *
+ * mlpl_rectify_images_dev: the fused hot path for `batch` pairs in one launch; the image index is a grid dimension.  d_img1 / d_img2:
+ *   [batch] planes of width x height bytes, `step` bytes from row to row and batch_stride bytes from pair to pair; d_out1 / d_out2 likewise
+ *   with out_width, out_height, out_step, out_batch_stride.  params: a HOST array [batch][2] of blocks {K[9], dist[8], Rect[9], Knew[9]}
+ *   (35 doubles; image 1 then image 2 of a pair), read before the call returns.  Each lane computes the map values of 4 adjacent pixels in
+ *   registers, rounds them to float32 exactly as mlpl_rectify_maps does, samples as mlpl_remap_bilinear does and stores the 4 bytes with one
+ *   store (row tails and unaligned outputs: byte stores); no map reaches memory.  The result is byte for byte mlpl_rectify_maps_dev followed
+ *   by mlpl_remap_bilinear_dev.  One small upload and one launch on `stream`, no synchronisation.  batch in [1, 32767].
+ * mlpl_rectify_images: the same for one pair of HOST images (params [2][35]). */
+int mlpl_rectify_parameters(const double R[9], const double t[3], const double K1[9], const double K2[9], const double *dist1, int n_dist1,
+                            const double *dist2, int n_dist2, int width, int height, double alpha, int new_width, int new_height,
+                            double Rect1[9], double Rect2[9], double Knew[9], int roi[4], double P1[12], double P2[12], double info[8]);
+int mlpl_rectify_maps(mlpl_ctx *ctx, const double K[9], const double *dist, int n_dist, const double Rect[9], const double Knew[9], int width,
+                      int height, float *mapx, float *mapy);
+int mlpl_rectify_maps_dev(mlpl_ctx *ctx, const double K[9], const double *dist, int n_dist, const double Rect[9], const double Knew[9],
+                          int width, int height, float *d_mapx, float *d_mapy, size_t map_stride, void *stream);
+int mlpl_remap_bilinear(mlpl_ctx *ctx, const uint8_t *img, int width, int height, size_t step, const float *mapx, const float *mapy, int out_width,
+                        int out_height, uint8_t *out, size_t out_step);
+int mlpl_remap_bilinear_dev(mlpl_ctx *ctx, const uint8_t *d_img, int width, int height, size_t step, const float *d_mapx, const float *d_mapy,
+                            size_t map_stride, int out_width, int out_height, uint8_t *d_out, size_t out_step, void *stream);
+int mlpl_rectify_images(mlpl_ctx *ctx, const uint8_t *img1, const uint8_t *img2, int width, int height, size_t step, const double *params,
+                        int out_width, int out_height, uint8_t *out1, uint8_t *out2, size_t out_step);
+int mlpl_rectify_images_dev(mlpl_ctx *ctx, int batch, const uint8_t *d_img1, const uint8_t *d_img2, int width, int height, size_t step,
+                            size_t batch_stride, const double *params, int out_width, int out_height, uint8_t *d_out1, uint8_t *d_out2,
+                            size_t out_step, size_t out_batch_stride, void *stream);
+
 /* ---- correspondence gather (pre-step of the pose path) -------------------------------------------------------
  * Replaces the gather + ImgToCamCoordTrans of StereoRefine::addNewCorrespondences (P/source/stereo_pose_refinement.cpp:
  * 428-455, P/source/pose_helper.cpp:1100-1109): p1[i] = ((double)kp1[m.queryIdx] - c0) / f0 rounded to float and widened

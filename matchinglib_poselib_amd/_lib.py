@@ -215,6 +215,16 @@ _SIGNATURES = {
     "mlpl_subpix_separate_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                          c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_int, c_size_t, c_size_t, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_rectify_parameters": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mlpl_rectify_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "mlpl_rectify_maps_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mlpl_remap_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),
+    "mlpl_remap_bilinear_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t,
+                                        c_void_p]),
+    "mlpl_rectify_images": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t]),
+    "mlpl_rectify_images_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                        c_size_t, c_size_t, c_void_p]),
     "mlpl_recover_pose_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
     "mlpl_recover_pose_translation": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,

@@ -71,6 +71,7 @@ enum WsSlot {
     WS_HOMOG,           // homography ARRSAC (homography_impl.h): packed correspondences, the models of every sample solved in a call, the compacted inliers
     WS_HOMOG_PLANES,    // estimateMultHomographys: the two point buffers the rounds alternate between, the round's mask, the planes' masks
     WS_HOMOG_ALIGN,     // homography alignment (homography_align_impl.h): the result block and the correspondences sorted by plane
+    WS_RECTIFY,         // stereo rectification (rectify.hip): the per-image map parameters of the fused, batched entry
     WS_NUM_SLOTS
 };
 

@@ -1105,6 +1105,141 @@ def estimateRelativePose(p1, p2, threshold: float = PIX_MIN_GOOD_TH, refine: boo
     return True, E, R, t, Q, mask2
 
 
+# ---- stereo rectification (include/mlpl_c.h, "stereo rectification") --------------------------------------------------------------------------
+def _dist(d):
+    d = np.zeros(0) if d is None else np.ascontiguousarray(np.asarray(d, np.float64).reshape(-1))
+    if d.size not in (0, 4, 5, 8):
+        raise MlplError(_lib.MLPL_E_BAD_INPUT, "rectification", "0, 4, 5 or 8 distortion coefficients")
+    return d
+
+
+def _m33(m):
+    return np.ascontiguousarray(np.asarray(m, np.float64).reshape(9))
+
+
+def _u8_image(img, what):
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.size == 0:
+        raise MlplError(_lib.MLPL_E_BAD_INPUT, what, "images are 8-bit, single channel and not empty")
+    return a if a.strides[1] == 1 and a.strides[0] >= a.shape[1] else np.ascontiguousarray(a)
+
+
+def rectification_parameters(R, t, K1, K2, dist1, dist2, image_size, alpha: float = -1.0, new_image_size=(0, 0)) -> dict:
+    """mlpl_rectify_parameters: poselib::getRectificationParameters with globRectFunct = true (Fusiello) -> dict(Rect1, Rect2, Knew [3, 3],
+    roi [x, y, width, height], P1, P2 [3, 4], info [8] = {fc_new before scaling, s0, s1, s, reduction steps of the four undistortion loops}).
+    image_size / new_image_size = (width, height); a new size with a zero side means the image size.  Host arithmetic: no device needed."""
+    lib = _lib.load_library()
+    Rm, tv, k1, k2, d1, d2 = _m33(R), np.ascontiguousarray(np.asarray(t, np.float64).reshape(3)), _m33(K1), _m33(K2), _dist(dist1), _dist(dist2)
+    r1, r2, kn, roi, p1, p2, info = np.zeros(9), np.zeros(9), np.zeros(9), np.zeros(4, np.int32), np.zeros(12), np.zeros(12), np.zeros(8)
+    rc = lib.mlpl_rectify_parameters(Rm.ctypes.data, tv.ctypes.data, k1.ctypes.data, k2.ctypes.data, d1.ctypes.data if d1.size else None, d1.size,
+                                     d2.ctypes.data if d2.size else None, d2.size, int(image_size[0]), int(image_size[1]), float(alpha),
+                                     int(new_image_size[0]), int(new_image_size[1]), r1.ctypes.data, r2.ctypes.data, kn.ctypes.data,
+                                     roi.ctypes.data, p1.ctypes.data, p2.ctypes.data, info.ctypes.data)
+    check(rc, "mlpl_rectify_parameters")
+    return dict(Rect1=r1.reshape(3, 3), Rect2=r2.reshape(3, 3), Knew=kn.reshape(3, 3), roi=[int(v) for v in roi], P1=p1.reshape(3, 4),
+                P2=p2.reshape(3, 4), info=info)
+
+
+def rectify_maps(K, dist, Rect, Knew, size, ctx: Optional[Context] = None, device_out=None, stream: Optional[int] = None):
+    """cv::initUndistortRectifyMap(K, dist, Rect, Knew, size, CV_32FC1) -> (mapx, mapy) float32 [height, width]; size = (width, height).
+    device_out = (mapx, mapy) float32 CUDA tensors [height, >= width] with unit column stride: mlpl_rectify_maps_dev fills and returns them
+    (enqueued on `stream`, None = torch's current stream, no synchronisation); otherwise numpy arrays through mlpl_rectify_maps."""
+    ctx = ctx or default_context()
+    k, d, r, kn = _m33(K), _dist(dist), _m33(Rect), _m33(Knew)
+    w, h = int(size[0]), int(size[1])
+    dp = d.ctypes.data if d.size else None
+    if device_out is not None:
+        import torch
+
+        mx, my = device_out
+        for m in (mx, my):
+            assert m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.shape == (h, w) and m.stride(1) == 1 and m.stride(0) == mx.stride(0)
+        st = torch.cuda.current_stream(mx.device).cuda_stream if stream is None else stream
+        check(ctx.lib.mlpl_rectify_maps_dev(ctx.handle, k.ctypes.data, dp, d.size, r.ctypes.data, kn.ctypes.data, w, h, mx.data_ptr(), my.data_ptr(),
+                                            mx.stride(0), st), "mlpl_rectify_maps_dev")
+        return mx, my
+    mx, my = np.zeros((max(h, 1), max(w, 1)), np.float32), np.zeros((max(h, 1), max(w, 1)), np.float32)
+    check(ctx.lib.mlpl_rectify_maps(ctx.handle, k.ctypes.data, dp, d.size, r.ctypes.data, kn.ctypes.data, w, h, mx.ctypes.data, my.ctypes.data),
+          "mlpl_rectify_maps")
+    return mx, my
+
+
+def remap_bilinear(img, mapx, mapy, ctx: Optional[Context] = None, device_out=None, stream: Optional[int] = None):
+    """cv::remap(img, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT) on an 8-bit single-channel image, OpenCV's fixed-point arithmetic -> uint8
+    [map height, map width].  numpy arguments: mlpl_remap_bilinear.  CUDA tensors (img uint8 [h, >= w], maps float32 of one row stride, all
+    with unit column stride): mlpl_remap_bilinear_dev into device_out (uint8, allocated when None), enqueued without synchronising."""
+    ctx = ctx or default_context()
+    if hasattr(img, "is_cuda"):
+        import torch
+
+        assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 2 and img.stride(1) == 1
+        for m in (mapx, mapy):
+            assert m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.shape == mapx.shape and m.stride(1) == 1 and m.stride(0) == mapx.stride(0)
+        oh, ow = mapx.shape
+        out = torch.empty((oh, ow), dtype=torch.uint8, device=img.device) if device_out is None else device_out
+        assert out.is_cuda and out.dtype == torch.uint8 and out.shape == (oh, ow) and out.stride(1) == 1
+        st = torch.cuda.current_stream(img.device).cuda_stream if stream is None else stream
+        check(ctx.lib.mlpl_remap_bilinear_dev(ctx.handle, img.data_ptr(), img.shape[1], img.shape[0], img.stride(0), mapx.data_ptr(), mapy.data_ptr(),
+                                              mapx.stride(0), ow, oh, out.data_ptr(), out.stride(0), st), "mlpl_remap_bilinear_dev")
+        return out
+    im = _u8_image(img, "remap_bilinear")
+    mx, my = np.ascontiguousarray(mapx, np.float32), np.ascontiguousarray(mapy, np.float32)
+    if mx.ndim != 2 or mx.shape != my.shape:
+        raise MlplError(_lib.MLPL_E_BAD_INPUT, "remap_bilinear", "two maps of one shape")
+    out = np.zeros(mx.shape, np.uint8)
+    check(ctx.lib.mlpl_remap_bilinear(ctx.handle, im.ctypes.data, im.shape[1], im.shape[0], im.strides[0], mx.ctypes.data, my.ctypes.data,
+                                      mx.shape[1], mx.shape[0], out.ctypes.data, out.strides[0] if out.size else 0), "mlpl_remap_bilinear")
+    return out
+
+
+def rectify_param_block(K, dist, Rect, Knew) -> np.ndarray:
+    """{K[9], dist[8], Rect[9], Knew[9]}: the per-image parameter block of rectify_images / rectify_images_batch (35 doubles)"""
+    d = _dist(dist)
+    return np.concatenate([_m33(K), d, np.zeros(8 - d.size), _m33(Rect), _m33(Knew)])
+
+
+def rectify_images(img1, img2, params, new_size=None, ctx: Optional[Context] = None):
+    """mlpl_rectify_images: the fused map + remap on one pair of 8-bit numpy images of one size -> (out1, out2) uint8 [new height, new
+    width].  params: [2, 35], one rectify_param_block per image; new_size = (width, height), None = the image size."""
+    ctx = ctx or default_context()
+    a, b = _u8_image(img1, "rectify_images"), _u8_image(img2, "rectify_images")
+    if a.shape != b.shape:
+        raise MlplError(_lib.MLPL_E_BAD_INPUT, "rectify_images", "the two images must have one size")
+    if a.strides[0] != b.strides[0]:
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(2, 35))
+    ow, oh = (a.shape[1], a.shape[0]) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    o1, o2 = np.zeros((max(oh, 1), max(ow, 1)), np.uint8), np.zeros((max(oh, 1), max(ow, 1)), np.uint8)
+    check(ctx.lib.mlpl_rectify_images(ctx.handle, a.ctypes.data, b.ctypes.data, a.shape[1], a.shape[0], a.strides[0], p.ctypes.data, ow, oh,
+                                      o1.ctypes.data, o2.ctypes.data, o1.strides[0]), "mlpl_rectify_images")
+    return o1, o2
+
+
+def rectify_images_batch(img1, img2, params, new_size=None, out=None, ctx: Optional[Context] = None, stream: Optional[int] = None):
+    """mlpl_rectify_images_dev: `B` pairs in one launch.  img1, img2: uint8 CUDA tensors [B, height, >= width] of one shape and strides, unit
+    column stride; params: host array [B, 2, 35] (rectify_param_block per image), read before the call returns; out = (out1, out2) uint8 CUDA
+    tensors [B, new height, new width] of one layout (allocated when None).  Enqueues on `stream` (None = torch's current stream) without
+    synchronising; returns (out1, out2)."""
+    import torch
+
+    assert img1.is_cuda and img2.is_cuda and img1.dtype == torch.uint8 and img2.dtype == torch.uint8 and img1.dim() == 3
+    assert img1.shape == img2.shape and img1.stride() == img2.stride() and img1.stride(2) == 1
+    B, h, w = img1.shape
+    ctx = ctx or default_context(img1.device.index or 0)
+    p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(B, 2, 35))
+    ow, oh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    if out is None:
+        out = (torch.empty((B, oh, ow), dtype=torch.uint8, device=img1.device), torch.empty((B, oh, ow), dtype=torch.uint8, device=img1.device))
+    o1, o2 = out
+    assert o1.is_cuda and o2.is_cuda and o1.dtype == torch.uint8 and o2.dtype == torch.uint8 and o1.shape == o2.shape == (B, oh, ow)
+    assert o1.stride() == o2.stride() and o1.stride(2) == 1
+    st = torch.cuda.current_stream(img1.device).cuda_stream if stream is None else stream
+    check(ctx.lib.mlpl_rectify_images_dev(ctx.handle, B, img1.data_ptr(), img2.data_ptr(), w, h, img1.stride(1), img1.stride(0) if B > 1 else 0,
+                                          p.ctypes.data, ow, oh, o1.data_ptr(), o2.data_ptr(), o1.stride(1), o1.stride(0) if B > 1 else 0, st),
+          "mlpl_rectify_images_dev")
+    return o1, o2
+
+
 def smoke_check(ctx, oracle) -> None:
     """Used by __graft_entry__.smoke(): one small RANSAC + pose recovery on the GPU, checked against the CPU oracle."""
     from . import synth

@@ -42,22 +42,17 @@ __device__ __forceinline__ void jacobi_right_vectors(double (&G)[N][N], double (
                     beta += G[i][q] * G[i][q];
                     gamma += G[i][p] * G[i][q];
                 }
-                if (gamma * gamma <= (eps * eps) * (alpha * beta) || gamma == 0.0) continue;  // |gamma| <= eps sqrt(alpha beta)
+                if (fabs(gamma) <= eps * sqrt(alpha * beta) || gamma == 0.0) continue;
                 rotated = true;
-                // A plane rotation stays orthogonal to rounding for ANY tangent t as long as c = (1 + t^2)^-1/2 is accurate and s = c t;
-                // an inexact t only leaves the pair at ~1e-8 of its former inner product, which the next sweep removes, and the
-                // iteration still ends on the test above.  So the tangent comes from v_rcp_f64 / v_sqrt_f64 (~2^-26) and only c is
-                // Newton-refined: three IEEE divisions and three IEEE square roots (~150 instructions per pair) become ~25.
-                const double zeta = (beta - alpha) * __builtin_amdgcn_rcp(2.0 * gamma);
-                const double az = fabs(zeta);
-                double t = __builtin_amdgcn_rcp(az + __builtin_amdgcn_sqrt(az * az + 1.0));
-                t = zeta >= 0 ? t : -t;
-                if (!(az < 1e150)) t = 0.5 / zeta;  // zeta^2 overflows: t = 1 / (2 zeta) to rounding
-                const double x1 = t * t + 1.0;
-                double c = __builtin_amdgcn_rsq(x1);
-                c = c * (1.5 - 0.5 * x1 * c * c);
-                c = c * (1.5 - 0.5 * x1 * c * c);
-                const double s = c * t;
+                // IEEE divisions and square roots, operation for operation the arithmetic of the CPU checker (oracle/pose_oracle.c,
+                // jacobi_svd_impl).  This iteration decomposes E, once per problem in one lane, and an essential matrix has two EQUAL
+                // singular values: which of the two comes out larger, and with it the orientation of (u1, u2), the sign of t = u1 x u2
+                // and the ORDER of the four candidates, is decided by the last bit.  With the approximate tangent that
+                // plane_rotation() below uses for the triangulation systems the order came out differently from the checker's on exact
+                // essential matrices, and where the candidates' counts tie (no correspondence, an all-zero mask) so did the pose.
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
 #pragma unroll
                 for (int i = 0; i < N; ++i) {
                     const double gp = G[i][p], gq = G[i][q];
@@ -77,6 +72,10 @@ __device__ __forceinline__ void jacobi_right_vectors(double (&G)[N][N], double (
 // rotation (c = 1, s = 0 leave its columns bit for bit).  The two rotations of a round touch different columns, so their dependent
 // chains (three inner products, reciprocal, root, inverse root, two Newton steps) interleave in one lane; the cyclic order above left the
 // kernel waiting 60 % of its wave cycles (SQ_WAIT_ANY / SQ_WAVE_CYCLES, profiles/r03_pmc_summary.json) with one chain per lane.
+// A plane rotation stays orthogonal to rounding for ANY tangent t as long as c = (1 + t^2)^-1/2 is accurate and s = c t; an inexact t only
+// leaves the pair at ~1e-8 of its former inner product, which the next sweep removes, and the iteration still ends on the orthogonality
+// test.  So here the tangent comes from v_rcp_f64 / v_sqrt_f64 (~2^-26) and only c is Newton-refined: three IEEE divisions and three IEEE
+// square roots (~150 instructions per pair) become ~25.  (The singular values of these systems are distinct; see jacobi_right_vectors.)
 struct PlaneRot {
     double c, s;
     bool on;
@@ -89,7 +88,7 @@ __device__ __forceinline__ PlaneRot plane_rotation(double alpha, double beta, do
     const double az = fabs(zeta);
     double t = __builtin_amdgcn_rcp(az + __builtin_amdgcn_sqrt(__builtin_fma(az, az, 1.0)));
     t = zeta >= 0 ? t : -t;
-    if (!(az < 1e150)) t = 0.5 * __builtin_amdgcn_rcp(zeta);  // zeta^2 overflows: t = 1 / (2 zeta); any t of that size does (see above)
+    if (!(az < 1e150)) t = 0.5 * __builtin_amdgcn_rcp(zeta);  // zeta^2 overflows: t = 1 / (2 zeta); any t of that size does
     const double x1 = __builtin_fma(t, t, 1.0);
     double c = __builtin_amdgcn_rsq(x1);
     c = c * __builtin_fma(-0.5 * x1, c * c, 1.5);
@@ -536,7 +535,8 @@ extern "C" int mlpl_recover_pose_translation(mlpl_ctx *ctx, const double t_only[
 
 static int recover_pose_impl(mlpl_ctx *ctx, const double *E, const double *t_only, const double *p1, const double *p2, int n,
                              double dist, double *R, double *t, double *Q, uint8_t *mask_inout, bool dev, hipStream_t stream) {
-    if (!ctx || !p1 || !p2 || !R || !t || (!Q && !dev) || n < 0) {
+    // (an empty set has no coordinates to point at: the device entry is handed null pointers for an empty tensor)
+    if (!ctx || (n > 0 && (!p1 || !p2)) || !R || !t || (!Q && !dev) || n < 0) {
         set_error("mlpl_recover_pose: R, t and Q are mandatory outputs");  // pose_estim.cpp:925-926 returns -1
         return MLPL_E_BAD_INPUT;
     }

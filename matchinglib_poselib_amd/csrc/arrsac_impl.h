@@ -25,6 +25,10 @@
 // thousand scalar operations.  A wrong guess costs a discarded batch, never a wrong result: the cache is keyed by content and the random
 // streams the host advances are the real ones.  Final mask: inlier_mask_count_kernel; refinement: arrsac_refine_kernel (one workgroup,
 // iteratively re-weighted 9x9 eigenproblem, no host hop inside).
+//
+// Included after batch_hub.h (Launcher, HubSlot, hub_batch_drive) and before homography_impl.h.  The host program is written once, as
+// ArrsacTemplate<Run> below: ArrsacRun (here) and HomogRun (homography_impl.h) are its two estimators and keep only their buffers, their
+// device batch, their row staging and bit().
 
 namespace {
 
@@ -785,25 +789,369 @@ struct ArrKeyHash {
         return (size_t)h;
     }
 };
-struct ArrIds {  // ids of a sample's VALID models in the order of the convention
+template <int kMax>
+struct ArrIdsOf {  // ids of a sample's VALID models (at most kMax) in the order of the convention
     int n;
-    int id[10];
+    int id[kMax];
     size_t size() const { return (size_t)n; }
     bool empty() const { return n == 0; }
     int operator[](size_t i) const { return id[i]; }
     const int *begin() const { return id; }
     const int *end() const { return id + n; }
 };
+using ArrIds = ArrIdsOf<10>;
 
-struct ArrBufs {  // a run's buffers when the caller provides them (batched runs: one slice per run)
-    char *dev = nullptr, *pin = nullptr, *pin_dev = nullptr;
+// ---- the ARRSAC template (arrsac.h), once for every estimator ----------------------------------------------------------------------------
+// The sequential host program of Arrsac<...>: the two samplers, PROSAC's growth table, the SPRT with its adaptation,
+// GenerateInitialHypothesisSet with the speculative play-forward of both samplers, and Estimate with its preemptive stage.  Every decision,
+// every draw from the two cv::RNG streams and every speculation depth is the reference's, turn by turn.  Run is the estimator's side
+// (struct Run : ArrsacTemplate<Run>); all calls into it are resolved at compile time.  It provides
+//   kMinSample, kNonMin, kNonMinMin   Arrsac's min_sample_size, max non-minimal sample size and the size below which a non-minimal sample
+//                                     is solved as a minimal one
+//   kPoolSamples, kBatchCap           samples the device keeps per call / solves per batch: the speculation depths read them
+//   n, flag_points                    correspondences; how many of them every model's up-front bit row covers
+//   pool_samples                      samples solved so far
+//   cache                             sample (ArrKey) -> ids of its valid models (ArrIdsOf), filled by
+//   int run_batch(keys)               one device batch: every key gets its cache entry; counts stats[8], stats[9]
+//   int ensure_bits(ids, count)       makes bits [0, count) of these models readable by bit()
+//   bool bit(id, i)                   model id's inlier bit of correspondence i
+//   void trace_turn(...)              a turn of the first stage, for diagnostics
+template <class Run>
+struct ArrsacTemplate {
+    // Arrsac's members (arrsac.h:102-118); max_candidate_hyps and block_size are 500 and 100 in both of the reference's instances
+    static constexpr int kMaxHyps = 500, kBlock = 100, kMaxInner = 20;
+    static constexpr double kConf = 0.95, kTimeRatio = 250.0;
+    double sigma = 0.05, epsilon = 0.1;
+    int verified_accum = 0, num_rejected = 0;
+    double rejected_accum = 0.0;
+    CvRng prosac_rng, random_rng;
+    // [0] turns of the first stage that gave models, [1] hypotheses it accepted, [2] PROSAC / [3] inner samples, [4] inner stages begun,
+    // [5] samples of the generation branch, [6] correspondences walked, [7] survivors, [8] batches, [9] samples sent, [10] samples used
+    long long stats[12] = {0};
+
+    Run &run() { return static_cast<Run &>(*this); }
+    const Run &run() const { return static_cast<const Run &>(*this); }
+    static int sample_kind(int size) { return (size == Run::kMinSample || size < Run::kNonMinMin) ? 0 : 1; }
+
+    // ProsacSampler::Sample for sample number k over the first `count` correspondences (prosac_sampler.h:85-157).  The growth function
+    // (subset size n and T'_n after k turns, Eq. 3-5 of the PROSAC paper as the reference evaluates them) does not depend on the stream:
+    // one pass tabulates it for every k the call can reach.
+    std::vector<int> prosac_nn;
+    std::vector<double> prosac_tnp;
+    void prosac_table(int count) {
+        constexpr int kMinSample = Run::kMinSample;
+        prosac_nn.assign(kMaxHyps + 2, kMinSample);
+        prosac_tnp.assign(kMaxHyps + 2, 1.0);
+        double t_n = 200000;
+        int nn = kMinSample;
+        for (int i = 0; i < kMinSample; i++) t_n *= static_cast<double>(nn - i) / (double)((size_t)count - i);
+        double t_n_prime = 1.0;
+        for (int t = 1; t <= kMaxHyps + 1; t++) {
+            if (t > t_n_prime && nn < count) {
+                const double t_n_plus1 = (t_n * ((double)nn + 1.0)) / ((double)nn + 1.0 - (double)kMinSample);
+                t_n_prime += std::ceil(t_n_plus1 - t_n);
+                t_n = t_n_plus1;
+                nn++;
+            }
+            prosac_nn[t] = nn, prosac_tnp[t] = t_n_prime;
+        }
+    }
+    void prosac_sample(CvRng &rng, int k, ArrKey &key) const {
+        constexpr int kMinSample = Run::kMinSample;
+        const int nn = prosac_nn[k];
+        const double t_n_prime = prosac_tnp[k];
+        key.reset(0);
+        const bool all_random = t_n_prime < k;
+        const int picks = all_random ? kMinSample : kMinSample - 1, range = all_random ? nn : nn - 1;
+        for (int i = 0; i < picks; i++) {
+            int r;
+            do r = rng.uniform(0, range);
+            while (key.has(r));
+            key.push(r);
+        }
+        if (!all_random) key.push(nn - 1);
+    }
+    // RandomSampler::Sample (random_sampler.h:57-78): `size` distinct positions of the universe
+    static void random_sample(CvRng &rng, const std::vector<int> &universe, int size, int kind, ArrKey &key) {
+        key.reset(kind);
+        int used[kArrMaxSample];
+        for (int i = 0; i < size; i++) {
+            int r;
+            do r = rng.uniform(0, (int)universe.size());
+            while (std::find(used, used + i, r) != used + i);
+            used[i] = r;
+            key.push(universe[r]);
+        }
+    }
+    static int to_int_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }  // cvttsd2si
+    static int hyps_needed(double eps, double power) {
+        return std::min(kMaxHyps, to_int_x86(std::ceil(std::log(1.0 - kConf) / std::log(1.0 - std::pow(eps, power)))));
+    }
+    static double sprt_threshold(double sg, double ep, int nmv) {  // sequential_probability_ratio.cc:38-62
+        const double c = (1.0 - sg) * std::log((1.0 - sg) / (1.0 - ep)) + sg * std::log(sg / ep);
+        const double a_0 = kTimeRatio * c / static_cast<double>(nmv) + 1.0;
+        double th = a_0;
+        for (int i = 0; i < 1000; i++) {
+            const double nt = a_0 + std::log(th);
+            const double step = std::fabs(nt - th);
+            th = nt;
+            if (step < 1e-4) break;
+        }
+        return th;
+    }
+    // SequentialProbabilityRatioTest over the first `count` correspondences, on the model's bit row
+    bool sprt(int id, int count, double dt, double *ratio, int *num_inl) const {
+        *num_inl = 0;
+        double lr = 1.0;
+        const double up = sigma / epsilon, down = (1.0 - sigma) / (1.0 - epsilon);
+        for (int i = 0; i < count; ++i) {
+            if (run().bit(id, i)) {
+                lr *= up;
+                *num_inl += 1;
+            } else {
+                lr *= down;
+            }
+            if (lr > dt) {
+                *ratio = static_cast<double>(*num_inl) / static_cast<double>(i + 1);
+                return false;
+            }
+        }
+        *ratio = static_cast<double>(*num_inl) / static_cast<double>(count);
+        return true;
+    }
+    void rejected(double ratio) {
+        rejected_accum += ratio;
+        num_rejected++;
+        const double st = rejected_accum / static_cast<double>(num_rejected);
+        if (st > 0) sigma = st;
+    }
+
+    struct Scored {
+        int id;
+        double score;
+    };
+
+    // Arrsac::GenerateInitialHypothesisSet (arrsac.h:236-372)
+    int initial_set(int count, std::vector<Scored> &accepted, int *rc_out) {
+        constexpr int kMinSample = Run::kMinSample, kNonMin = Run::kNonMin;
+        Run &R = run();
+        int k = 1, k2 = 0, m_prime = kMaxHyps, inner_its = 0, max_num_inliers = 0, random_size = kNonMin;
+        bool inner = false;
+        std::vector<int> data;
+        ArrKey key;
+        prosac_table(count);
+        while (k <= m_prime) {
+            // the sample of this turn, from the real streams
+            if (!inner) {
+                prosac_sample(prosac_rng, k, key);
+                stats[2]++;
+            } else {
+                random_sample(random_rng, data, random_size, sample_kind(random_size), key);
+                stats[3]++;
+            }
+            auto it = R.cache.find(key);
+            if (it == R.cache.end()) {
+                // play the samplers forward under "no event" and solve what is coming in one batch
+                std::vector<ArrKey> batch(1, key);
+                std::unordered_set<ArrKey, ArrKeyHash> in_batch;
+                in_batch.insert(key);
+                CvRng pr = prosac_rng, rr = random_rng;
+                int kk = k + 1, its = inner_its;
+                bool in = inner;
+                if (in && ++its == kMaxInner) its = 0, in = false;
+                // speculation depth: 128 samples while the device pool is at most half full, 16 afterwards.  An event (at most one per value of
+                // the best support, < 100) costs one batch, so the pool of 8192 samples cannot overflow in this stage: 4096 / 128 = 32 deep
+                // batches, then 256 shallow ones.
+                const int want = R.pool_samples <= Run::kPoolSamples / 2 ? 128 : 16;
+                ArrKey nk;
+                while (kk <= m_prime && (int)batch.size() < want) {
+                    if (!in) {
+                        prosac_sample(pr, kk, nk);
+                    } else {
+                        random_sample(rr, data, random_size, sample_kind(random_size), nk);
+                        if (++its == kMaxInner) its = 0, in = false;
+                    }
+                    kk++;
+                    if (R.cache.find(nk) == R.cache.end() && in_batch.insert(nk).second) batch.push_back(nk);
+                }
+                if ((*rc_out = R.run_batch(batch))) return 0;
+                it = R.cache.find(key);
+            }
+            stats[10]++;
+            const auto &hyps = it->second;
+            const int inner_turn = inner ? 1 : 0;
+            if (inner) {
+                inner_its++;
+                if (inner_its == kMaxInner) inner_its = 0, inner = false;
+            }
+            if (hyps.empty()) {
+                R.trace_turn(k, inner_turn, key, 0, nullptr);
+                k2++, k++;
+                continue;
+            }
+            verified_accum += (int)hyps.size();
+            const double dt = sprt_threshold(sigma, epsilon, verified_accum / (k - k2));
+            int res[10];
+            for (size_t j = 0; j < hyps.size(); j++) {
+                int num_inl;
+                double ratio;
+                const bool ok = sprt(hyps[j], count, dt, &ratio, &num_inl);
+                if (j < 10) res[j] = (ok ? 1000 : 0) + num_inl;
+                if (!ok) {
+                    rejected(ratio);
+                } else if (num_inl > max_num_inliers) {
+                    max_num_inliers = num_inl;
+                    accepted.push_back(Scored{hyps[j], (double)num_inl});
+                    if (num_inl > kMinSample) {
+                        inner = true;
+                        inner_its = 0;
+                        random_size = std::max(std::min(kNonMin, (int)std::floor((float)max_num_inliers / 2.0f)), kMinSample);
+                        data.clear();
+                        for (int i = 0; i < count; i++)
+                            if (R.bit(hyps[j], i)) data.push_back(i);
+                        epsilon = ratio == 1.0 ? 0.9999 : ratio;
+                        m_prime = hyps_needed(epsilon, (double)kMinSample);
+                        stats[4]++;
+                    }
+                } else {
+                    accepted.push_back(Scored{hyps[j], (double)num_inl});
+                }
+            }
+            R.trace_turn(k, inner_turn, key, (int)std::min<size_t>(hyps.size(), 10), res);
+            k++;
+        }
+        if (accepted.empty()) return 0;
+        return k - k2 - 1;
+    }
+
+    // Arrsac::Estimate (arrsac.h:375-547); returns the pool id of the best model or -1
+    int estimate(int *rc_out) {
+        constexpr int kMinSample = Run::kMinSample;
+        Run &R = run();
+        const int n = R.n;
+        const int sub_block = (int)std::floor((float)kBlock / 5.0);
+        const int kill_thresh = (int)std::floor(7.0 * (float)sub_block / 12.0);
+        std::vector<Scored> hyps;
+        int k = initial_set(std::min(n, kBlock), hyps, rc_out);
+        stats[0] = k, stats[1] = (long long)hyps.size();
+        if (*rc_out || k == 0) return -1;
+        if (n <= kBlock) {
+            double hi = 0.0;
+            int at = 0;
+            for (size_t i = 0; i < hyps.size(); i++)
+                if (hyps[i].score > hi) hi = hyps[i].score, at = (int)i;
+            return hyps[at].id;
+        }
+        auto cmp = [](Scored a, Scored b) { return a.score > b.score; };  // CompareScoredData (arrsac.h:82-84); std::sort as the reference
+        std::vector<int> all(n);
+        for (int i = 0; i < n; ++i) all[i] = i;
+        int nh = (int)hyps.size();
+        std::vector<int> ids;
+        // the preemptive stage walks the accepted hypotheses' bits beyond the first block
+        for (const Scored &h : hyps) ids.push_back(h.id);
+        if ((*rc_out = R.ensure_bits(ids, kBlock + 1))) return -1;
+        bool past_rows = false;
+        int i = kBlock;
+        for (; i < n; i++) {
+            if (i >= R.flag_points && !past_rows) {
+                // Past the correspondences every model was tested on.  Reached when the hypothesis set GROWS (generation branch, inlier
+                // ratios above ~0.9: k climbs towards 500 and nothing halves): the survivors' bits over all n are computed on demand.
+                // Hypotheses that join later bring theirs along (the generation branch below, on i + 1 > flag_points correspondences).
+                ids.clear();
+                for (const Scored &h : hyps) ids.push_back(h.id);
+                if ((*rc_out = R.ensure_bits(ids, n))) return -1;
+                past_rows = true;
+            }
+            if ((i + 1) % kBlock == 0) {
+                std::sort(hyps.begin(), hyps.end(), cmp);
+                double max_inliers = hyps[0].score;
+                epsilon = max_inliers / static_cast<double>(i + 1);
+                if (epsilon == 1.0) epsilon = 0.9999;
+                int temp_max = hyps_needed(epsilon, (double)(i + 1));
+                if (temp_max > k) {
+                    int k2 = 0;
+                    ArrKey key;
+                    for (int j = 0; j < (long long)temp_max - k; j++) {
+                        random_sample(random_rng, all, kMinSample, 0, key);
+                        stats[5]++;
+                        auto it = R.cache.find(key);
+                        if (it == R.cache.end()) {  // the uniform sampler's future does not depend on any outcome
+                            std::vector<ArrKey> batch(1, key);
+                            std::unordered_set<ArrKey, ArrKeyHash> in_batch;
+                            in_batch.insert(key);
+                            CvRng rr = random_rng;
+                            ArrKey nk;
+                            for (int jj = j + 1, kk = k + 1; jj < (long long)temp_max - kk && (int)batch.size() < Run::kBatchCap; ++jj, ++kk) {
+                                random_sample(rr, all, kMinSample, 0, nk);
+                                if (R.cache.find(nk) == R.cache.end() && in_batch.insert(nk).second) batch.push_back(nk);
+                            }
+                            if ((*rc_out = R.run_batch(batch))) return -1;
+                            // these are tested on i + 1 correspondences
+                            ids.clear();
+                            for (const ArrKey &bk : batch)
+                                for (int id : R.cache.find(bk)->second) ids.push_back(id);
+                            if ((*rc_out = R.ensure_bits(ids, i + 1))) return -1;
+                            it = R.cache.find(key);
+                        }
+                        stats[10]++;
+                        const auto &est = it->second;
+                        if (est.empty()) {
+                            k2++;
+                            continue;
+                        }
+                        // a sample met before (first stage, earlier block) may hold only its leading bits: complete the rows (no-ops otherwise)
+                        ids.assign(est.begin(), est.end());
+                        if ((*rc_out = R.ensure_bits(ids, i + 1))) return -1;
+                        verified_accum += (int)est.size();
+                        const double dt = sprt_threshold(sigma, epsilon, verified_accum / (k + j + 1 - k2));
+                        for (size_t m = 0; m < est.size(); m++) {
+                            int num_inl;
+                            double ratio;
+                            const bool ok = sprt(est[m], i + 1, dt, &ratio, &num_inl);
+                            if (!ok) {
+                                rejected(ratio);
+                            } else if (num_inl > (int)max_inliers) {
+                                hyps.push_back(Scored{est[m], (double)num_inl});
+                                max_inliers = static_cast<double>(num_inl);
+                                epsilon = ratio == 1.0 ? 0.9999 : ratio;
+                                temp_max = hyps_needed(epsilon, (double)(i + 1));
+                                if (temp_max <= (k + j + 1)) break;
+                            } else {
+                                hyps.push_back(Scored{est[m], (double)num_inl});
+                            }
+                        }
+                        k++;
+                    }
+                    nh = (int)hyps.size();
+                } else {
+                    const int n1 = std::max(1, (int)std::floor((float)k * std::pow(2.0, -1.0 * std::floor((float)(i + 1) / (float)kBlock))));
+                    if (n1 < static_cast<int>(hyps.size())) {
+                        hyps.resize(n1);
+                        nh = n1;
+                    }
+                }
+            } else if ((i + 1) % sub_block == 0) {
+                std::sort(hyps.begin(), hyps.end(), cmp);
+                int j = nh - 1;
+                for (; j > 0; j--)
+                    if (hyps[j - 1].score - hyps[j].score > kill_thresh) break;
+                nh = nh - j;
+                hyps.resize(nh);
+            }
+            if (nh == 1) break;
+            for (size_t j = 0; j < hyps.size(); j++)
+                if (R.bit(hyps[j].id, i)) hyps[j].score += 1.0;
+        }
+        stats[6] = i, stats[7] = nh;
+        return hyps[0].id;
+    }
 };
 
-struct ArrsacRun {
+struct ArrsacRun : ArrsacTemplate<ArrsacRun> {
     mlpl_ctx *ctx;
     hipStream_t s;
     Launcher L;                    // launches now (a run alone) or records for the hub (a run of a batch, batch_hub.h)
-    const ArrBufs *bufs = nullptr;
+    const HubSlot *bufs = nullptr; // a run's blocks when the caller provides them (batched runs: one slot per run)
     int32_t *trace_buf = nullptr;  // turn records of the first stage (this run's buffer)
     int trace_cap = 0, trace_len = 0;
     const double *d_p1, *d_p2;
@@ -827,15 +1175,9 @@ struct ArrsacRun {
     unsigned long long *d_Fpool = nullptr;
     int pool_samples = 0;  // samples whose rows are in use
     std::unordered_map<ArrKey, ArrIds, ArrKeyHash> cache;  // sample -> its valid models
-    long long stats[12] = {0};                 // [8] batches, [9] samples sent, [10] samples used
 
-    // Arrsac(5, thr^2, 500, 100, 14, 8) (modelest.cpp:270) and its members (arrsac.h:102-118)
-    static constexpr int kMinSample = 5, kMaxHyps = 500, kBlock = 100, kNonMin = 14, kNonMinMin = 8, kMaxInner = 20;
-    double sigma = 0.05, epsilon = 0.1;
-    static constexpr double kConf = 0.95, kTimeRatio = 250.0;
-    int verified_accum = 0, num_rejected = 0;
-    double rejected_accum = 0.0;
-    CvRng prosac_rng, random_rng;
+    // Arrsac(5, thr^2, 500, 100, 14, 8) (modelest.cpp:270)
+    static constexpr int kMinSample = 5, kNonMin = 14, kNonMinMin = 8, kPoolSamples = kArrPoolSamples, kBatchCap = kArrBatchCap;
 
     static size_t out_bytes(int B) {
         const size_t batch = (size_t)B * 4 + (size_t)B * 40 + (size_t)B * 80 + (size_t)B * 10 * kArrHeadWords * 8 + 64;
@@ -1025,6 +1367,14 @@ struct ArrsacRun {
         return MLPL_OK;
     }
 
+    // The template's hook.  A model arrives with its first 128 bits; whoever asks here walks further (the preemptive stage): the whole row
+    // up to flag_points, whatever the count, and the bits of all n beyond it.
+    int ensure_bits(const std::vector<int> &ids, int count) {
+        int rc;
+        if ((rc = ensure_full(ids))) return rc;
+        return count > flag_points ? ensure_ext(ids) : MLPL_OK;
+    }
+
     bool bit(int id, int i) const {
         const ArrModelHost &m = pool[id];
         if (i < kArrHeadWords * 64) return (m.head[i >> 6] >> (i & 63)) & 1;
@@ -1032,101 +1382,6 @@ struct ArrsacRun {
         return (full_rows[m.full].bits[i >> 6] >> (i & 63)) & 1;                    // callers fetch the row first (ensure_full)
     }
 
-    // ProsacSampler::Sample for sample number k over the first `count` correspondences (prosac_sampler.h:85-157).  The growth function
-    // (subset size n and T'_n after k turns, Eq. 3-5 of the PROSAC paper as the reference evaluates them) does not depend on the stream:
-    // one pass tabulates it for every k the call can reach.
-    std::vector<int> prosac_nn;
-    std::vector<double> prosac_tnp;
-    void prosac_table(int count) {
-        prosac_nn.assign(kMaxHyps + 2, kMinSample);
-        prosac_tnp.assign(kMaxHyps + 2, 1.0);
-        double t_n = 200000;
-        int nn = kMinSample;
-        for (int i = 0; i < kMinSample; i++) t_n *= static_cast<double>(nn - i) / (double)((size_t)count - i);
-        double t_n_prime = 1.0;
-        for (int t = 1; t <= kMaxHyps + 1; t++) {
-            if (t > t_n_prime && nn < count) {
-                const double t_n_plus1 = (t_n * ((double)nn + 1.0)) / ((double)nn + 1.0 - (double)kMinSample);
-                t_n_prime += std::ceil(t_n_plus1 - t_n);
-                t_n = t_n_plus1;
-                nn++;
-            }
-            prosac_nn[t] = nn, prosac_tnp[t] = t_n_prime;
-        }
-    }
-    void prosac_sample(CvRng &rng, int k, ArrKey &key) const {
-        const int nn = prosac_nn[k];
-        const double t_n_prime = prosac_tnp[k];
-        key.reset(0);
-        const bool all_random = t_n_prime < k;
-        const int picks = all_random ? kMinSample : kMinSample - 1, range = all_random ? nn : nn - 1;
-        for (int i = 0; i < picks; i++) {
-            int r;
-            do r = rng.uniform(0, range);
-            while (key.has(r));
-            key.push(r);
-        }
-        if (!all_random) key.push(nn - 1);
-    }
-    // RandomSampler::Sample (random_sampler.h:57-78): `size` distinct positions of the universe
-    static void random_sample(CvRng &rng, const std::vector<int> &universe, int size, int kind, ArrKey &key) {
-        key.reset(kind);
-        int used[kArrMaxSample];
-        for (int i = 0; i < size; i++) {
-            int r;
-            do r = rng.uniform(0, (int)universe.size());
-            while (std::find(used, used + i, r) != used + i);
-            used[i] = r;
-            key.push(universe[r]);
-        }
-    }
-    static int to_int_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }  // cvttsd2si
-    static int hyps_needed(double eps, double power) {
-        return std::min(kMaxHyps, to_int_x86(std::ceil(std::log(1.0 - kConf) / std::log(1.0 - std::pow(eps, power)))));
-    }
-    static double sprt_threshold(double sg, double ep, int nmv) {  // sequential_probability_ratio.cc:38-62
-        const double c = (1.0 - sg) * std::log((1.0 - sg) / (1.0 - ep)) + sg * std::log(sg / ep);
-        const double a_0 = kTimeRatio * c / static_cast<double>(nmv) + 1.0;
-        double th = a_0;
-        for (int i = 0; i < 1000; i++) {
-            const double nt = a_0 + std::log(th);
-            const double step = std::fabs(nt - th);
-            th = nt;
-            if (step < 1e-4) break;
-        }
-        return th;
-    }
-    // SequentialProbabilityRatioTest over the first `count` correspondences, on the model's bit row
-    bool sprt(int id, int count, double dt, double *ratio, int *num_inl) const {
-        *num_inl = 0;
-        double lr = 1.0;
-        const double up = sigma / epsilon, down = (1.0 - sigma) / (1.0 - epsilon);
-        for (int i = 0; i < count; ++i) {
-            if (bit(id, i)) {
-                lr *= up;
-                *num_inl += 1;
-            } else {
-                lr *= down;
-            }
-            if (lr > dt) {
-                *ratio = static_cast<double>(*num_inl) / static_cast<double>(i + 1);
-                return false;
-            }
-        }
-        *ratio = static_cast<double>(*num_inl) / static_cast<double>(count);
-        return true;
-    }
-    void rejected(double ratio) {
-        rejected_accum += ratio;
-        num_rejected++;
-        const double st = rejected_accum / static_cast<double>(num_rejected);
-        if (st > 0) sigma = st;
-    }
-
-    struct Scored {
-        int id;
-        double score;
-    };
     // diagnostics (mlpl_debug_arrsac_trace): 20 ints per turn of the first stage
     void trace_turn(int k, int inner_turn, const ArrKey &key, int nvalid, const int *res) {
         if (!trace_buf || trace_len + 20 > trace_cap) return;
@@ -1137,220 +1392,6 @@ struct ArrsacRun {
         for (int i = 0; i < 10; ++i) r[9 + i] = i < nvalid ? res[i] : -1;
         r[19] = (key.size() > 5 ? key.v[6] : 0) + 100 * (key.size() > 6 ? key.v[7] : 0);  // indices of the first stage are < 100
         trace_len += 20;
-    }
-
-    // Arrsac::GenerateInitialHypothesisSet (arrsac.h:236-372)
-    int initial_set(int count, std::vector<Scored> &accepted, int *rc_out) {
-        int k = 1, k2 = 0, m_prime = kMaxHyps, inner_its = 0, max_num_inliers = 0, random_size = kNonMin;
-        bool inner = false;
-        std::vector<int> data;
-        ArrKey key;
-        prosac_table(count);
-        while (k <= m_prime) {
-            // the sample of this turn, from the real streams
-            if (!inner) {
-                prosac_sample(prosac_rng, k, key);
-                stats[2]++;
-            } else {
-                const int kind = (random_size == kMinSample || random_size < kNonMinMin) ? 0 : 1;
-                random_sample(random_rng, data, random_size, kind, key);
-                stats[3]++;
-            }
-            auto it = cache.find(key);
-            if (it == cache.end()) {
-                // play the samplers forward under "no event" and solve what is coming in one batch
-                std::vector<ArrKey> batch(1, key);
-                std::unordered_set<ArrKey, ArrKeyHash> in_batch;
-                in_batch.insert(key);
-                CvRng pr = prosac_rng, rr = random_rng;
-                int kk = k + 1, its = inner_its;
-                bool in = inner;
-                if (in && ++its == kMaxInner) its = 0, in = false;
-                // speculation depth: 128 samples while the device pool is at most half full, 16 afterwards.  An event (at most one per value of
-                // the best support, < 100) costs one batch, so the pool of 8192 samples cannot overflow in this stage: 4096 / 128 = 32 deep
-                // batches, then 256 shallow ones.
-                const int want = pool_samples <= kArrPoolSamples / 2 ? 128 : 16;
-                ArrKey nk;
-                while (kk <= m_prime && (int)batch.size() < want) {
-                    if (!in) {
-                        prosac_sample(pr, kk, nk);
-                    } else {
-                        const int kind = (random_size == kMinSample || random_size < kNonMinMin) ? 0 : 1;
-                        random_sample(rr, data, random_size, kind, nk);
-                        if (++its == kMaxInner) its = 0, in = false;
-                    }
-                    kk++;
-                    if (cache.find(nk) == cache.end() && in_batch.insert(nk).second) batch.push_back(nk);
-                }
-                if ((*rc_out = run_batch(batch))) return 0;
-                it = cache.find(key);
-            }
-            stats[10]++;
-            const ArrIds &hyps = it->second;
-            const int inner_turn = inner ? 1 : 0;
-            if (inner) {
-                inner_its++;
-                if (inner_its == kMaxInner) inner_its = 0, inner = false;
-            }
-            if (hyps.empty()) {
-                trace_turn(k, inner_turn, key, 0, nullptr);
-                k2++, k++;
-                continue;
-            }
-            verified_accum += (int)hyps.size();
-            const double dt = sprt_threshold(sigma, epsilon, verified_accum / (k - k2));
-            int res[10];
-            for (size_t j = 0; j < hyps.size(); j++) {
-                int num_inl;
-                double ratio;
-                const bool ok = sprt(hyps[j], count, dt, &ratio, &num_inl);
-                if (j < 10) res[j] = (ok ? 1000 : 0) + num_inl;
-                if (!ok) {
-                    rejected(ratio);
-                } else if (num_inl > max_num_inliers) {
-                    max_num_inliers = num_inl;
-                    accepted.push_back(Scored{hyps[j], (double)num_inl});
-                    if (num_inl > kMinSample) {
-                        inner = true;
-                        inner_its = 0;
-                        random_size = std::max(std::min(kNonMin, (int)std::floor((float)max_num_inliers / 2.0f)), kMinSample);
-                        data.clear();
-                        for (int i = 0; i < count; i++)
-                            if (bit(hyps[j], i)) data.push_back(i);
-                        epsilon = ratio == 1.0 ? 0.9999 : ratio;
-                        m_prime = hyps_needed(epsilon, (double)kMinSample);
-                        stats[4]++;
-                    }
-                } else {
-                    accepted.push_back(Scored{hyps[j], (double)num_inl});
-                }
-            }
-            trace_turn(k, inner_turn, key, (int)std::min<size_t>(hyps.size(), 10), res);
-            k++;
-        }
-        if (accepted.empty()) return 0;
-        return k - k2 - 1;
-    }
-
-    // Arrsac::Estimate (arrsac.h:375-547); returns the pool id of the best model or -1
-    int estimate(int *rc_out) {
-        const int sub_block = (int)std::floor((float)kBlock / 5.0);
-        const int kill_thresh = (int)std::floor(7.0 * (float)sub_block / 12.0);
-        std::vector<Scored> hyps;
-        int k = initial_set(std::min(n, kBlock), hyps, rc_out);
-        stats[0] = k, stats[1] = (long long)hyps.size();
-        if (*rc_out || k == 0) return -1;
-        if (n <= kBlock) {
-            double hi = 0.0;
-            int at = 0;
-            for (size_t i = 0; i < hyps.size(); i++)
-                if (hyps[i].score > hi) hi = hyps[i].score, at = (int)i;
-            return hyps[at].id;
-        }
-        auto cmp = [](Scored a, Scored b) { return a.score > b.score; };  // CompareScoredData (arrsac.h:82-84); std::sort as the reference
-        std::vector<int> all(n);
-        for (int i = 0; i < n; ++i) all[i] = i;
-        int nh = (int)hyps.size();
-        {  // the preemptive stage walks the accepted hypotheses' bits beyond the first block: fetch their rows (one host hop)
-            std::vector<int> ids;
-            for (const Scored &h : hyps) ids.push_back(h.id);
-            if ((*rc_out = ensure_full(ids))) return -1;
-        }
-        int i = kBlock;
-        for (; i < n; i++) {
-            if (i >= flag_points) {
-                // Past the correspondences every model was tested on.  Reached when the hypothesis set GROWS (generation branch, inlier
-                // ratios above ~0.9: k climbs towards 500 and nothing halves): the survivors' bits over all n are computed on demand.
-                std::vector<int> ids;
-                for (const Scored &h : hyps)
-                    if (pool[h.id].ext < 0) ids.push_back(h.id);
-                if (!ids.empty() && (*rc_out = ensure_ext(ids))) return -1;
-            }
-            if ((i + 1) % kBlock == 0) {
-                std::sort(hyps.begin(), hyps.end(), cmp);
-                double max_inliers = hyps[0].score;
-                epsilon = max_inliers / static_cast<double>(i + 1);
-                if (epsilon == 1.0) epsilon = 0.9999;
-                int temp_max = hyps_needed(epsilon, (double)(i + 1));
-                if (temp_max > k) {
-                    int k2 = 0;
-                    ArrKey key;
-                    for (int j = 0; j < (long long)temp_max - k; j++) {
-                        random_sample(random_rng, all, kMinSample, 0, key);
-                        stats[5]++;
-                        auto it = cache.find(key);
-                        if (it == cache.end()) {  // the uniform sampler's future does not depend on any outcome
-                            std::vector<ArrKey> batch(1, key);
-                            std::unordered_set<ArrKey, ArrKeyHash> in_batch;
-                            in_batch.insert(key);
-                            CvRng rr = random_rng;
-                            ArrKey nk;
-                            for (int jj = j + 1, kk = k + 1; jj < (long long)temp_max - kk && (int)batch.size() < kArrBatchCap; ++jj, ++kk) {
-                                random_sample(rr, all, kMinSample, 0, nk);
-                                if (cache.find(nk) == cache.end() && in_batch.insert(nk).second) batch.push_back(nk);
-                            }
-                            if ((*rc_out = run_batch(batch))) return -1;
-                            // these are tested on i + 1 > 128 correspondences: their whole rows are needed
-                            std::vector<int> ids;
-                            for (const ArrKey &bk : batch)
-                                for (int id : cache.find(bk)->second) ids.push_back(id);
-                            if ((*rc_out = ensure_full(ids))) return -1;
-                            if (i + 1 > flag_points && (*rc_out = ensure_ext(ids))) return -1;
-                            it = cache.find(key);
-                        }
-                        stats[10]++;
-                        const ArrIds &est = it->second;
-                        if (est.empty()) {
-                            k2++;
-                            continue;
-                        }
-                        {  // a sample met before (first stage, earlier block) may hold only its leading bits: complete the rows (no-ops otherwise)
-                            std::vector<int> ids(est.begin(), est.end());
-                            if ((*rc_out = ensure_full(ids))) return -1;
-                            if (i + 1 > flag_points && (*rc_out = ensure_ext(ids))) return -1;
-                        }
-                        verified_accum += (int)est.size();
-                        const double dt = sprt_threshold(sigma, epsilon, verified_accum / (k + j + 1 - k2));
-                        for (size_t m = 0; m < est.size(); m++) {
-                            int num_inl;
-                            double ratio;
-                            const bool ok = sprt(est[m], i + 1, dt, &ratio, &num_inl);
-                            if (!ok) {
-                                rejected(ratio);
-                            } else if (num_inl > (int)max_inliers) {
-                                hyps.push_back(Scored{est[m], (double)num_inl});
-                                max_inliers = static_cast<double>(num_inl);
-                                epsilon = ratio == 1.0 ? 0.9999 : ratio;
-                                temp_max = hyps_needed(epsilon, (double)(i + 1));
-                                if (temp_max <= (k + j + 1)) break;
-                            } else {
-                                hyps.push_back(Scored{est[m], (double)num_inl});
-                            }
-                        }
-                        k++;
-                    }
-                    nh = (int)hyps.size();
-                } else {
-                    const int n1 = std::max(1, (int)std::floor((float)k * std::pow(2.0, -1.0 * std::floor((float)(i + 1) / (float)kBlock))));
-                    if (n1 < static_cast<int>(hyps.size())) {
-                        hyps.resize(n1);
-                        nh = n1;
-                    }
-                }
-            } else if ((i + 1) % sub_block == 0) {
-                std::sort(hyps.begin(), hyps.end(), cmp);
-                int j = nh - 1;
-                for (; j > 0; j--)
-                    if (hyps[j - 1].score - hyps[j].score > kill_thresh) break;
-                nh = nh - j;
-                hyps.resize(nh);
-            }
-            if (nh == 1) break;
-            for (size_t j = 0; j < hyps.size(); j++)
-                if (bit(hyps[j].id, i)) hyps[j].score += 1.0;
-        }
-        stats[6] = i, stats[7] = nh;
-        return hyps[0].id;
     }
 };
 
@@ -1449,119 +1490,32 @@ constexpr int kArrBatchRuns = 128;
 int arrsac_essential_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double thresh,
                                int refine, uint64_t *rng_states, double *E, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, hipStream_t s,
                                const CohortFeed *feed = nullptr) {
-    if (B <= 0) return MLPL_OK;
-    int rc;
-    size_t max_dev = 0, max_pin = 0;
+    const char *name = "mlpl_arrsac_essential_batch_dev";
+    HubBatch P{name, kArrBatchRuns, 0, 0, !feed, nullptr};
     for (int b = 0; b < (feed ? 1 : B); ++b) {  // (a feed delivers the counts later: blocks for `stride` correspondences)
         const ArrsacRun::Layout Y = ArrsacRun::layout(std::max(feed ? stride : counts[b], 6));
-        max_dev = std::max(max_dev, Y.dev_total), max_pin = std::max(max_pin, Y.pin_total);
+        P.slot_dev = std::max(P.slot_dev, Y.dev_total), P.slot_pin = std::max(P.slot_pin, Y.pin_total);
     }
-    // cohorts of <= kArrBatchRuns runs, two in flight (batch_hub.h kHubLanes): one cohort's host turns run beside the other's launches
-    int n_cohorts = 0, lanes = 0;
-    const int cohort = hub_cohort_size(ctx, B, kArrBatchRuns, &n_cohorts, &lanes);
-    if (feed && (feed->cohort != cohort || feed->n_cohorts != n_cohorts)) {
-        set_error("mlpl_arrsac_essential_batch_dev: the feed's cohorts are not the estimator's");
-        return MLPL_E_INTERNAL;
-    }
-    void *pblk, *dblk;
-    if ((rc = pinned_batch_get(ctx, (size_t)lanes * cohort * max_pin, &pblk))) return rc;
-    if ((rc = ws_get(ctx, WS_BATCH_RUNS, (size_t)lanes * cohort * max_dev, &dblk))) return rc;
-    char *pin = (char *)pblk, *pin_dev = nullptr;
-    {
-        void *alias = nullptr;
-        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pin, 0));
-        pin_dev = (char *)alias;
-    }
-    hipStream_t lane_stream[kHubLanes];
-    for (int l = 0; l < lanes; ++l)
-        if ((rc = hub_lane_stream(ctx, l, s, &lane_stream[l]))) return rc;
-    if (lanes > 1 && !feed) MLPL_HIP_TRY(hipStreamSynchronize(s));  // the correspondences were produced on the caller's stream; a lane's own stream has no other ordering
-    struct LaneOut {
-        long long rounds = 0, merged = 0;
-        int first_err = 0;
-        std::string first_msg;
-    };
-    LaneOut lane_out[kHubLanes];
-    auto serve_lane = [&](int l) {
-        LaneOut &LO = lane_out[l];
-        const hipStream_t ls = lane_stream[l];
-        if (l > 0 && hipSetDevice(ctx->device) != hipSuccess) {  // a lane's own thread starts on device 0
-            LO.first_err = MLPL_E_INTERNAL, LO.first_msg = "batched estimator: hipSetDevice failed on a lane thread";
-            return;
-        }
-        for (int c = l; c < n_cohorts; c += lanes) {
-            const int b0 = c * cohort, nb = std::min(cohort, B - b0);
-            if (feed) {  // the producer's event (everything this cohort reads on the device is behind it), then its host-side hand-over
-                int frc = hipEventSynchronize(feed->ready[c]) == hipSuccess ? MLPL_OK : MLPL_E_HIP;
-                if (!frc) frc = feed->on_ready(c, hub_resources(ctx)->lane[l].threads);
-                if (frc) {
-                    LO.first_err = frc, LO.first_msg = "mlpl_arrsac_essential_batch_dev: the hand-over of a cohort failed";
-                    break;
-                }
+    if (feed)  // the producer's event (everything this cohort reads on the device is behind it), then its host-side hand-over
+        P.before_cohort = [=](const HubCohort &c) {
+            if (feed->cohort != c.cohort || feed->n_cohorts != c.n_cohorts) {
+                set_error("%s: the feed's cohorts are not the estimator's", name);
+                return (int)MLPL_E_INTERNAL;
             }
-            BatchHub hub(ctx, ls, nb, l);
-            std::vector<ArrBufs> bufs((size_t)nb);
-            std::vector<std::string> msgs((size_t)nb);
-            for (int k = 0; k < nb; ++k) {
-                const size_t slot = (size_t)l * cohort + k;
-                bufs[k].dev = (char *)dblk + slot * max_dev;
-                bufs[k].pin = pin + slot * max_pin, bufs[k].pin_dev = pin_dev + slot * max_pin;
-            }
-            HubThreads &pool = hub_resources(ctx)->lane[l].threads;
-            pool.start(nb, [&](int k) {
-                const int b = b0 + k;
-                HubRun &hr = hub.run(k);
-                int r = MLPL_OK;
-                if (counts[b] < 6) {  // (a pair without enough matches in a batch of image pairs: nothing to estimate)
-                    status[b] = MLPL_E_FAILED;
-                    if (n_inliers) n_inliers[b] = 0;
-                    hub.finish(hr);
-                    return;
-                }
-                try {
-                    ArrsacRun R;
-                    R.ctx = ctx, R.s = ls, R.L.s = ls, R.L.hub = &hub, R.L.run = &hr, R.bufs = &bufs[k];
-                    R.d_p1 = d_p1 + (size_t)b * stride * 2, R.d_p2 = d_p2 + (size_t)b * stride * 2, R.n = counts[b];
-                    int ninl = 0;
-                    r = arrsac_run_problem(R, thresh, refine, rng_states + 2 * (size_t)b, E + (size_t)b * 9, d_masks + (size_t)b * stride, &ninl, nullptr);
-                    if (n_inliers) n_inliers[b] = ninl;
-                } catch (const std::bad_alloc &) {
-                    r = MLPL_E_NOMEM;
-                    set_error("mlpl_arrsac_essential_batch_dev: out of host memory");
-                } catch (...) {  // (anything else -- a length_error of a vector, say -- must not unwind off the fiber's makecontext frame)
-                    r = MLPL_E_INTERNAL;
-                    set_error("mlpl_arrsac_essential_batch_dev: a run ended with an unexpected C++ exception");
-                }
-                if (r && r != MLPL_E_FAILED) msgs[k] = mlpl_last_error();
-                status[b] = r;
-                hub.finish(hr);
-            }, ctx->opt_hub_workers);
-            const int hrc = hub.serve();
-            pool.wait();
-            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches();
-            for (int k = 0; k < nb && !LO.first_err; ++k)
-                if (status[b0 + k] && status[b0 + k] != MLPL_E_FAILED) LO.first_err = status[b0 + k], LO.first_msg = msgs[k];
-            if (hrc && !LO.first_err) LO.first_err = hrc;
-            if (LO.first_err) break;
+            int frc = hipEventSynchronize(feed->ready[c.index]) == hipSuccess ? MLPL_OK : MLPL_E_HIP;
+            if (!frc) frc = feed->on_ready(c.index, hub_resources(ctx)->lane[c.lane].threads);
+            if (frc) set_error("%s: the hand-over of a cohort failed", name);
+            return frc;
+        };
+    return hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) {
+        int ninl = 0, r = MLPL_E_FAILED;  // (a pair without enough matches in a batch of image pairs: nothing to estimate)
+        if (counts[b] >= 6) {
+            ArrsacRun R;
+            R.ctx = ctx, R.s = L.s, R.L = L, R.bufs = &slot;
+            R.d_p1 = d_p1 + (size_t)b * stride * 2, R.d_p2 = d_p2 + (size_t)b * stride * 2, R.n = counts[b];
+            r = arrsac_run_problem(R, thresh, refine, rng_states + 2 * (size_t)b, E + (size_t)b * 9, d_masks + (size_t)b * stride, &ninl, nullptr);
         }
-    };
-    {
-        std::vector<std::thread> others;
-        for (int l = 1; l < lanes; ++l) others.emplace_back(serve_lane, l);
-        serve_lane(0);
-        for (auto &t : others) t.join();
-    }
-    int first_err = 0;
-    std::string first_msg;
-    long long rounds = 0, merged = 0;
-    for (int l = 0; l < lanes; ++l) {
-        rounds += lane_out[l].rounds, merged += lane_out[l].merged;
-        if (lane_out[l].first_err && !first_err) first_err = lane_out[l].first_err, first_msg = lane_out[l].first_msg;
-    }
-    ctx->last_arrsac_stats[8] = rounds, ctx->last_arrsac_stats[9] = merged;
-    if (first_err) {
-        if (!first_msg.empty()) set_error("%s", first_msg.c_str());
-        return first_err;
-    }
-    return MLPL_OK;
+        if (n_inliers) n_inliers[b] = ninl;
+        return r;
+    });
 }

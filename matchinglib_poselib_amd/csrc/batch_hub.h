@@ -1,5 +1,7 @@
 // batch_hub.h -- many sequential estimators (USAC, ARRSAC) sharing every kernel launch.
-// Included by ransac_5pt.hip inside namespace mlpl, before arrsac_impl.h / usac_impl.h.
+// Included by ransac_5pt.hip inside namespace mlpl, before arrsac_impl.h / homography_impl.h / usac_impl.h.  At its end: the cohort / lane
+// driver of the batched ARRSAC estimators (hub_batch_drive: essential matrix, homography, multi-plane, pose from planes) and hub_on_lanes,
+// which every entry that serves lanes on threads of their own starts them with.
 //
 // USAC and ARRSAC are sequential programs whose control flow runs on the host (usac_impl.h, arrsac_impl.h): a run alternates between
 // host decisions and small dependent launch chains (a speculative batch of samples: solver -> roots -> check; a local optimisation; a
@@ -489,5 +491,142 @@ struct Launcher {
         return hub->wait(*run);
     }
 };
+
+// Joins every joinable thread on the way out, whatever happens in between: a joinable std::thread must not be destroyed.
+struct JoinThreads {
+    std::vector<std::thread> t;
+    ~JoinThreads() {
+        for (auto &x : t)
+            if (x.joinable()) x.join();
+    }
+};
+// fn(1) ... fn(lanes - 1) on threads of their own, fn(0) on the caller's; returns when all have.  A thread that cannot be started fails the
+// call (MLPL_E_INTERNAL, fn(0) not run) after the lanes that did start have finished.
+template <class Fn>
+inline int hub_on_lanes(int lanes, const char *name, const Fn &fn) {
+    JoinThreads others;
+    try {
+        others.t.reserve((size_t)lanes);
+        for (int l = 1; l < lanes; ++l) others.t.emplace_back(fn, l);
+    } catch (const std::exception &e) {
+        set_error("%s: %s", name, e.what());
+        return MLPL_E_INTERNAL;
+    }
+    fn(0);
+    return MLPL_OK;
+}
+
+// ---- the cohort / lane driver of a batched sequential estimator ------------------------------------------------------------------------
+// B problems in cohorts of at most cohort_default runs (hub_cohort_size), up to kHubLanes cohorts in flight on the lanes' streams: every
+// run a fiber on one of the lane's worker threads, every launch merged over the cohort's runs by its BatchHub.  A run's blocks are one slot
+// of WS_BATCH_RUNS (slot_dev bytes) and one of the batch's pinned block (slot_pin bytes); the slots of lane l are [l * cohort, (l + 1) * cohort).
+// job(b, slot, launcher) is problem b's sequential program -- the one the single entry runs -- and returns its status; status[b] receives
+// it.  before_cohort (may be empty) runs on the lane's thread before a cohort's hub is built: what the cohort needs on the device or from
+// a producer first; it reports a failure with set_error.  Every problem's outputs are those of the single entry on it alone.
+struct HubSlot {  // a run's blocks
+    char *dev = nullptr, *pin = nullptr, *pin_dev = nullptr;
+};
+struct HubCohort {
+    int lane, index, size;  // the lane that serves it, its number, its runs
+    int cohort, n_cohorts;  // the batch's geometry
+    hipStream_t stream;
+    char *dev;              // the lane's first device slot
+};
+struct HubBatch {
+    const char *name;             // the entry, for messages
+    int cohort_default;           // the estimator's cohort size without the option
+    size_t slot_dev, slot_pin;
+    bool inputs_on_caller_stream; // the problems' inputs were produced on the caller's stream (no producer orders them for the lanes)
+    std::function<int(const HubCohort &)> before_cohort;
+};
+static int hub_batch_drive(mlpl_ctx *ctx, int B, const HubBatch &P, int32_t *status, hipStream_t s,
+                           const std::function<int(int, const HubSlot &, const Launcher &)> &job) {
+    if (B <= 0) return MLPL_OK;
+    int rc, n_cohorts = 0, lanes = 0;
+    const int cohort = hub_cohort_size(ctx, B, P.cohort_default, &n_cohorts, &lanes);
+    void *pblk, *dblk;
+    if ((rc = pinned_batch_get(ctx, (size_t)lanes * cohort * P.slot_pin, &pblk))) return rc;
+    if ((rc = ws_get(ctx, WS_BATCH_RUNS, (size_t)lanes * cohort * P.slot_dev, &dblk))) return rc;
+    char *pin = (char *)pblk, *pin_dev = nullptr;
+    {
+        void *alias = nullptr;
+        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pin, 0));
+        pin_dev = (char *)alias;
+    }
+    hipStream_t lane_stream[kHubLanes];
+    for (int l = 0; l < lanes; ++l)
+        if ((rc = hub_lane_stream(ctx, l, s, &lane_stream[l]))) return rc;
+    if (lanes > 1 && P.inputs_on_caller_stream) MLPL_HIP_TRY(hipStreamSynchronize(s));  // a lane's own stream has no other ordering behind the caller's
+    struct LaneOut {
+        long long rounds = 0, merged = 0;
+        int first_err = 0;
+        std::string first_msg;
+    };
+    LaneOut lane_out[kHubLanes];
+    auto serve_lane = [&](int l) {
+        LaneOut &LO = lane_out[l];
+        const hipStream_t ls = lane_stream[l];
+        if (l > 0 && hipSetDevice(ctx->device) != hipSuccess) {  // a lane's own thread starts on device 0
+            LO.first_err = MLPL_E_INTERNAL, LO.first_msg = "batched estimator: hipSetDevice failed on a lane thread";
+            return;
+        }
+        const size_t slot0 = (size_t)l * cohort;
+        for (int c = l; c < n_cohorts; c += lanes) {
+            const int b0 = c * cohort, nb = std::min(cohort, B - b0);
+            if (P.before_cohort) {
+                const HubCohort hc{l, c, nb, cohort, n_cohorts, ls, (char *)dblk + slot0 * P.slot_dev};
+                if ((LO.first_err = P.before_cohort(hc))) {
+                    LO.first_msg = mlpl_last_error();
+                    break;
+                }
+            }
+            BatchHub hub(ctx, ls, nb, l);
+            std::vector<std::string> msgs((size_t)nb);
+            HubThreads &pool = hub_resources(ctx)->lane[l].threads;
+            pool.start(nb, [&](int k) {
+                const int b = b0 + k;
+                HubRun &hr = hub.run(k);
+                int r = MLPL_OK;
+                try {
+                    const size_t slot = slot0 + k;
+                    const HubSlot bufs{(char *)dblk + slot * P.slot_dev, pin + slot * P.slot_pin, pin_dev + slot * P.slot_pin};
+                    Launcher L;
+                    L.s = ls, L.hub = &hub, L.run = &hr;
+                    r = job(b, bufs, L);
+                } catch (const std::bad_alloc &) {
+                    r = MLPL_E_NOMEM;
+                    set_error("out of host memory");
+                } catch (...) {  // (anything else -- a length_error of a vector, say -- must not unwind off the fiber's makecontext frame)
+                    r = MLPL_E_INTERNAL;
+                    set_error("a run ended with an unexpected C++ exception");
+                }
+                if (r && r != MLPL_E_FAILED) msgs[k] = std::string(P.name) + ": problem " + std::to_string(b) + ": " + mlpl_last_error();
+                status[b] = r;
+                hub.finish(hr);
+            }, ctx->opt_hub_workers);
+            const int hrc = hub.serve();
+            pool.wait();
+            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches();
+            for (int k = 0; k < nb && !LO.first_err; ++k)
+                if (status[b0 + k] && status[b0 + k] != MLPL_E_FAILED) LO.first_err = status[b0 + k], LO.first_msg = msgs[k];
+            if (hrc && !LO.first_err) LO.first_err = hrc;
+            if (LO.first_err) break;
+        }
+    };
+    if ((rc = hub_on_lanes(lanes, P.name, serve_lane))) return rc;
+    int first_err = 0;
+    std::string first_msg;
+    long long rounds = 0, merged = 0;
+    for (int l = 0; l < lanes; ++l) {
+        rounds += lane_out[l].rounds, merged += lane_out[l].merged;
+        if (lane_out[l].first_err && !first_err) first_err = lane_out[l].first_err, first_msg = lane_out[l].first_msg;
+    }
+    ctx->last_arrsac_stats[8] = rounds, ctx->last_arrsac_stats[9] = merged;  // the hub's counters
+    if (first_err) {
+        if (!first_msg.empty()) set_error("%s", first_msg.c_str());
+        return first_err;
+    }
+    return MLPL_OK;
+}
 
 }  // namespace

@@ -1,6 +1,7 @@
 // homography_align_impl.h -- the pose-from-planes half of poselib::estimatePoseHomographies on the MI355X: Homographys_Alignment
 // (poselib/source/HomographyAlignment.cpp:197-360) and its caller's part (ComputeHomographyMotion :82-171, pose_homography.cpp:195-213).
-// Included by ransac_5pt.hip inside namespace mlpl after homography_impl.h.
+// Included by ransac_5pt.hip inside namespace mlpl after homography_impl.h (its batch entry runs on that file's homography_batch_drive, a
+// caller of batch_hub.h's hub_batch_drive).
 //
 // The algorithm is a long chain of small dependent solves, each fed by sums over all correspondences: two candidate motions from the
 // Longuet-Higgins decomposition of plane 0's homography, and for each of them up to 4 outer turns of up to 40 rounds of {a 3 x 3 system

@@ -1,6 +1,7 @@
 // homography_impl.h -- poselib::computeHomographyArrsac / estimateMultHomographys (poselib/source/pose_homography.cpp:291-885) on the MI355X.
-// Included by ransac_5pt.hip inside namespace mlpl after arrsac_impl.h: it reuses that file's control-plane helpers (CvRng, ArrKey and its
-// hash, the uniform sampler, sprt_threshold, hyps_needed, to_int_x86) and ransac_5pt.hip's jacobi9_wave.
+// Included by ransac_5pt.hip inside namespace mlpl after batch_hub.h and arrsac_impl.h: HomogRun is the homography side of that file's
+// ArrsacTemplate (the sequential ARRSAC program, written once for both estimators), the batch entries are callers of the hub's cohort / lane
+// driver (hub_batch_drive), and the sample kernel uses ransac_5pt.hip's jacobi9_wave.
 //
 // The estimator is the same theia::Arrsac template the essential-matrix path runs, constructed as Arrsac(4, th^2, 500, 100, 12)
 // (pose_homography.cpp:505): minimal sample 4, at most 500 hypotheses, blocks of 100, inner RANSAC on min(12, max_inl / 2) points with the
@@ -708,7 +709,7 @@ struct HomBufs {
     }
 };
 
-struct HomogRun {
+struct HomogRun : ArrsacTemplate<HomogRun> {  // the ARRSAC program itself: arrsac_impl.h
     mlpl_ctx *ctx;
     Launcher L;  // launches now (a run alone) or records for the hub (a run of a batch, batch_hub.h)
     const HomBufs *B;
@@ -717,16 +718,11 @@ struct HomogRun {
     double thresh2;
     std::vector<HomModelHost> pool;
     std::vector<std::vector<uint64_t>> ext_rows;
-    std::unordered_map<ArrKey, int, ArrKeyHash> cache;  // sample -> its model (pool index) or -1
+    std::unordered_map<ArrKey, ArrIdsOf<1>, ArrKeyHash> cache;  // sample -> its model (pool index), if it gave one
     int pool_samples = 0;
-    long long stats[12] = {0};  // [0..7] as the E entry, [8] batches, [9] samples sent, [10] samples used
 
-    // Arrsac(4, th^2, 500, 100, 12) (pose_homography.cpp:505) and its members (arrsac.h:102-118)
-    static constexpr int kMinSample = kHomMinSample, kMaxHyps = 500, kBlock = 100, kNonMin = kHomMaxSample, kNonMinMin = 0, kMaxInner = 20;
-    double sigma = 0.05, epsilon = 0.1;
-    int verified_accum = 0, num_rejected = 0;
-    double rejected_accum = 0.0;
-    CvRng prosac_rng, random_rng;
+    // Arrsac(4, th^2, 500, 100, 12) (pose_homography.cpp:505)
+    static constexpr int kMinSample = kHomMinSample, kNonMin = kHomMaxSample, kNonMinMin = 0, kPoolSamples = kHomPoolSamples, kBatchCap = kHomBatchCap;
 
     int sync() { return L.sync(); }
     void pack_points() {
@@ -775,15 +771,15 @@ struct HomogRun {
         const int32_t *h_ok = (const int32_t *)(B->pin + B->p_ok);
         const uint64_t *h_rows = (const uint64_t *)(B->pin + B->p_rows);
         for (int b = 0; b < nb; ++b) {
-            int id = -1;
+            ArrIdsOf<1> ids{0, {-1}};
             if (h_ok[b]) {
                 HomModelHost mh;
                 mh.row = pool_samples + b;
                 std::memcpy(mh.bits, h_rows + (size_t)b * kArrFlagWords, sizeof(mh.bits));
-                id = (int)pool.size();
+                ids.id[ids.n++] = (int)pool.size();
                 pool.push_back(mh);
             }
-            cache.emplace(keys[b], id);
+            cache.emplace(keys[b], ids);
         }
         pool_samples += nb;
         stats[8]++;
@@ -818,267 +814,14 @@ struct HomogRun {
         }
         return MLPL_OK;
     }
+    // The template's hook: a model arrives with its first flag_points bits; beyond them the bits of all n are computed.
+    int ensure_bits(const std::vector<int> &ids, int count) { return count > flag_points ? ensure_ext(ids) : MLPL_OK; }
     bool bit(int id, int i) const {
         const HomModelHost &m = pool[id];
-        if (i >= flag_points) return (ext_rows[m.ext][i >> 6] >> (i & 63)) & 1;  // callers compute the row first (ensure_ext)
+        if (i >= flag_points) return (ext_rows[m.ext][i >> 6] >> (i & 63)) & 1;  // callers compute the row first (ensure_bits)
         return (m.bits[i >> 6] >> (i & 63)) & 1;
     }
-
-    // ProsacSampler::Sample (prosac_sampler.h:85-157) for minimal samples of 4: the growth function, tabulated for every turn a call can reach
-    std::vector<int> prosac_nn;
-    std::vector<double> prosac_tnp;
-    void prosac_table(int count) {
-        prosac_nn.assign(kMaxHyps + 2, kMinSample);
-        prosac_tnp.assign(kMaxHyps + 2, 1.0);
-        double t_n = 200000;
-        int nn = kMinSample;
-        for (int i = 0; i < kMinSample; i++) t_n *= static_cast<double>(nn - i) / (double)((size_t)count - i);
-        double t_n_prime = 1.0;
-        for (int t = 1; t <= kMaxHyps + 1; t++) {
-            if (t > t_n_prime && nn < count) {
-                const double t_n_plus1 = (t_n * ((double)nn + 1.0)) / ((double)nn + 1.0 - (double)kMinSample);
-                t_n_prime += std::ceil(t_n_plus1 - t_n);
-                t_n = t_n_plus1;
-                nn++;
-            }
-            prosac_nn[t] = nn, prosac_tnp[t] = t_n_prime;
-        }
-    }
-    void prosac_sample(CvRng &rng, int k, ArrKey &key) const {
-        const int nn = prosac_nn[k];
-        const double t_n_prime = prosac_tnp[k];
-        key.reset(0);
-        const bool all_random = t_n_prime < k;
-        const int picks = all_random ? kMinSample : kMinSample - 1, range = all_random ? nn : nn - 1;
-        for (int i = 0; i < picks; i++) {
-            int r;
-            do r = rng.uniform(0, range);
-            while (key.has(r));
-            key.push(r);
-        }
-        if (!all_random) key.push(nn - 1);
-    }
-    static int sample_kind(int size) { return (size == kMinSample || size < kNonMinMin) ? 0 : 1; }
-    bool sprt(int id, int count, double dt, double *ratio, int *num_inl) const {
-        *num_inl = 0;
-        double lr = 1.0;
-        const double up = sigma / epsilon, down = (1.0 - sigma) / (1.0 - epsilon);
-        for (int i = 0; i < count; ++i) {
-            if (bit(id, i)) {
-                lr *= up;
-                *num_inl += 1;
-            } else {
-                lr *= down;
-            }
-            if (lr > dt) {
-                *ratio = static_cast<double>(*num_inl) / static_cast<double>(i + 1);
-                return false;
-            }
-        }
-        *ratio = static_cast<double>(*num_inl) / static_cast<double>(count);
-        return true;
-    }
-    void rejected(double ratio) {
-        rejected_accum += ratio;
-        num_rejected++;
-        const double st = rejected_accum / static_cast<double>(num_rejected);
-        if (st > 0) sigma = st;
-    }
-    struct Scored {
-        int id;
-        double score;
-    };
-
-    // Arrsac::GenerateInitialHypothesisSet (arrsac.h:206-347)
-    int initial_set(int count, std::vector<Scored> &accepted, int *rc_out) {
-        int k = 1, k2 = 0, m_prime = kMaxHyps, inner_its = 0, max_num_inliers = 0, random_size = kNonMin;
-        bool inner = false;
-        std::vector<int> data;
-        ArrKey key;
-        prosac_table(count);
-        while (k <= m_prime) {
-            if (!inner) {
-                prosac_sample(prosac_rng, k, key);
-                stats[2]++;
-            } else {
-                ArrsacRun::random_sample(random_rng, data, random_size, sample_kind(random_size), key);
-                stats[3]++;
-            }
-            auto it = cache.find(key);
-            if (it == cache.end()) {
-                // play the samplers forward under "no event" and solve what is coming in one batch (arrsac_impl.h)
-                std::vector<ArrKey> batch(1, key);
-                std::unordered_set<ArrKey, ArrKeyHash> in_batch;
-                in_batch.insert(key);
-                CvRng pr = prosac_rng, rr = random_rng;
-                int kk = k + 1, its = inner_its;
-                bool in = inner;
-                if (in && ++its == kMaxInner) its = 0, in = false;
-                const int want = pool_samples <= kHomPoolSamples / 2 ? 128 : 16;
-                ArrKey nk;
-                while (kk <= m_prime && (int)batch.size() < want) {
-                    if (!in) {
-                        prosac_sample(pr, kk, nk);
-                    } else {
-                        ArrsacRun::random_sample(rr, data, random_size, sample_kind(random_size), nk);
-                        if (++its == kMaxInner) its = 0, in = false;
-                    }
-                    kk++;
-                    if (cache.find(nk) == cache.end() && in_batch.insert(nk).second) batch.push_back(nk);
-                }
-                if ((*rc_out = run_batch(batch))) return 0;
-                it = cache.find(key);
-            }
-            stats[10]++;
-            const int id = it->second;
-            if (inner) {
-                inner_its++;
-                if (inner_its == kMaxInner) inner_its = 0, inner = false;
-            }
-            if (id < 0) {
-                k2++, k++;
-                continue;
-            }
-            verified_accum += 1;  // one model per sample
-            const double dt = ArrsacRun::sprt_threshold(sigma, epsilon, verified_accum / (k - k2));
-            int num_inl;
-            double ratio;
-            if (!sprt(id, count, dt, &ratio, &num_inl)) {
-                rejected(ratio);
-            } else if (num_inl > max_num_inliers) {
-                max_num_inliers = num_inl;
-                accepted.push_back(Scored{id, (double)num_inl});
-                if (num_inl > kMinSample) {
-                    inner = true;
-                    inner_its = 0;
-                    random_size = std::max(std::min(kNonMin, (int)std::floor((float)max_num_inliers / 2.0f)), kMinSample);
-                    data.clear();
-                    for (int i = 0; i < count; i++)
-                        if (bit(id, i)) data.push_back(i);
-                    epsilon = ratio == 1.0 ? 0.9999 : ratio;
-                    m_prime = ArrsacRun::hyps_needed(epsilon, (double)kMinSample);
-                    stats[4]++;
-                }
-            } else {
-                accepted.push_back(Scored{id, (double)num_inl});
-            }
-            k++;
-        }
-        if (accepted.empty()) return 0;
-        return k - k2 - 1;
-    }
-
-    // Arrsac::Estimate (arrsac.h:350-547); returns the pool id of the best model or -1
-    int estimate(int *rc_out) {
-        const int sub_block = (int)std::floor((float)kBlock / 5.0);
-        const int kill_thresh = (int)std::floor(7.0 * (float)sub_block / 12.0);
-        std::vector<Scored> hyps;
-        int k = initial_set(std::min(n, kBlock), hyps, rc_out);
-        stats[0] = k, stats[1] = (long long)hyps.size();
-        if (*rc_out || k == 0) return -1;
-        if (n <= kBlock) {
-            double hi = 0.0;
-            int at = 0;
-            for (size_t i = 0; i < hyps.size(); i++)
-                if (hyps[i].score > hi) hi = hyps[i].score, at = (int)i;
-            return hyps[at].id;
-        }
-        auto cmp = [](Scored a, Scored b) { return a.score > b.score; };  // CompareScoredData (arrsac.h:82-84); std::sort as the reference
-        std::vector<int> all(n);
-        for (int i = 0; i < n; ++i) all[i] = i;
-        int nh = (int)hyps.size();
-        int i = kBlock;
-        for (; i < n; i++) {
-            if (i >= flag_points) {
-                // Past the correspondences every model was tested on.  Reached when the hypothesis set GROWS (generation branch at inlier
-                // ratios above ~0.9: k closes half of its gap to 500 per block and nothing halves before correspondence 1100): the
-                // survivors' bits over all n are computed on demand, as arrsac_impl.h does for E.
-                std::vector<int> ids;
-                for (const Scored &h : hyps)
-                    if (pool[h.id].ext < 0) ids.push_back(h.id);
-                if (!ids.empty() && (*rc_out = ensure_ext(ids))) return -1;
-            }
-            if ((i + 1) % kBlock == 0) {
-                std::sort(hyps.begin(), hyps.end(), cmp);
-                double max_inliers = hyps[0].score;
-                epsilon = max_inliers / static_cast<double>(i + 1);
-                if (epsilon == 1.0) epsilon = 0.9999;
-                int temp_max = ArrsacRun::hyps_needed(epsilon, (double)(i + 1));
-                if (temp_max > k) {
-                    int k2 = 0;
-                    ArrKey key;
-                    for (int j = 0; j < (long long)temp_max - k; j++) {
-                        ArrsacRun::random_sample(random_rng, all, kMinSample, 0, key);
-                        stats[5]++;
-                        auto it = cache.find(key);
-                        if (it == cache.end()) {  // the uniform sampler's future does not depend on any outcome
-                            std::vector<ArrKey> batch(1, key);
-                            std::unordered_set<ArrKey, ArrKeyHash> in_batch;
-                            in_batch.insert(key);
-                            CvRng rr = random_rng;
-                            ArrKey nk;
-                            for (int jj = j + 1, kk = k + 1; jj < (long long)temp_max - kk && (int)batch.size() < kHomBatchCap; ++jj, ++kk) {
-                                ArrsacRun::random_sample(rr, all, kMinSample, 0, nk);
-                                if (cache.find(nk) == cache.end() && in_batch.insert(nk).second) batch.push_back(nk);
-                            }
-                            if ((*rc_out = run_batch(batch))) return -1;
-                            if (i + 1 > flag_points) {  // these are tested on i + 1 correspondences: beyond their rows
-                                std::vector<int> ids;
-                                for (const ArrKey &bk : batch) {
-                                    const int bid = cache.find(bk)->second;
-                                    if (bid >= 0) ids.push_back(bid);
-                                }
-                                if ((*rc_out = ensure_ext(ids))) return -1;
-                            }
-                            it = cache.find(key);
-                        }
-                        stats[10]++;
-                        const int id = it->second;
-                        if (id < 0) {
-                            k2++;
-                            continue;
-                        }
-                        // (a sample met before may hold only its first row: a no-op otherwise)
-                        if (i + 1 > flag_points && (*rc_out = ensure_ext(std::vector<int>(1, id)))) return -1;
-                        verified_accum += 1;
-                        const double dt = ArrsacRun::sprt_threshold(sigma, epsilon, verified_accum / (k + j + 1 - k2));
-                        int num_inl;
-                        double ratio;
-                        if (!sprt(id, i + 1, dt, &ratio, &num_inl)) {
-                            rejected(ratio);
-                        } else if (num_inl > (int)max_inliers) {
-                            hyps.push_back(Scored{id, (double)num_inl});
-                            max_inliers = static_cast<double>(num_inl);
-                            epsilon = ratio == 1.0 ? 0.9999 : ratio;
-                            temp_max = ArrsacRun::hyps_needed(epsilon, (double)(i + 1));
-                        } else {
-                            hyps.push_back(Scored{id, (double)num_inl});
-                        }
-                        k++;
-                    }
-                    nh = (int)hyps.size();
-                } else {
-                    const int n1 = std::max(1, (int)std::floor((float)k * std::pow(2.0, -1.0 * std::floor((float)(i + 1) / (float)kBlock))));
-                    if (n1 < static_cast<int>(hyps.size())) {
-                        hyps.resize(n1);
-                        nh = n1;
-                    }
-                }
-            } else if ((i + 1) % sub_block == 0) {
-                std::sort(hyps.begin(), hyps.end(), cmp);
-                int j = nh - 1;
-                for (; j > 0; j--)
-                    if (hyps[j - 1].score - hyps[j].score > kill_thresh) break;
-                nh = nh - j;
-                hyps.resize(nh);
-            }
-            if (nh == 1) break;
-            for (size_t j = 0; j < hyps.size(); j++)
-                if (bit(hyps[j].id, i)) hyps[j].score += 1.0;
-        }
-        stats[6] = i, stats[7] = nh;
-        return hyps[0].id;
-    }
+    void trace_turn(int, int, const ArrKey &, int, const int *) {}  // (no turn records)
 };
 
 // Where the multi-plane loop wants a plane's by-products (all device pointers, all optional).
@@ -1348,112 +1091,31 @@ int mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2,
                                  d_labels, found_at, L);
 }
 
-// ---- batches of plane problems: every run a fiber on a worker thread, every launch merged over the runs (batch_hub.h) --------------------------------
-// The shape of arrsac_essential_batch_dev: cohorts of at most 128 runs, up to four of them in flight on the lanes' streams; a run's blocks are
-// one slot of WS_BATCH_RUNS / the batch's pinned block, laid out for the largest problem.  job(b, bufs, launcher) is problem b's sequential
-// program -- the one the single entries run -- and returns its status.  Every problem's outputs are those of the single entry on it alone.
+// ---- batches of plane problems on the hub's cohort / lane driver (batch_hub.h hub_batch_drive) -----------------------------------------------------
+// A run's slot is a HomBufs laid out for the batch's largest problem.  job(b, bufs, launcher) is problem b's sequential program -- the one
+// the single entries run -- and returns its status.  Every problem's outputs are those of the single entry on it alone.
 namespace {
 constexpr int kHomBatchRuns = 128;
 
 static int homography_batch_drive(mlpl_ctx *ctx, int B, const int32_t *counts, bool want_planes, bool clear_labels, int32_t *status, hipStream_t s,
                                   const char *name, const std::function<int(int, const HomBufs &, const Launcher &)> &job) {
-    if (B <= 0) return MLPL_OK;
-    int rc, n_max = 1;
+    int n_max = 1;
     for (int b = 0; b < B; ++b) n_max = std::max(n_max, counts[b]);
     HomBufs Y;
     Y.layout(n_max);
-    const size_t slot_dev = Y.dev_total + (want_planes ? HomBufs::up(Y.planes_total) : 0), slot_pin = Y.pin_total;
-    int n_cohorts = 0, lanes = 0;
-    const int cohort = hub_cohort_size(ctx, B, kHomBatchRuns, &n_cohorts, &lanes);
-    void *pblk, *dblk;
-    if ((rc = pinned_batch_get(ctx, (size_t)lanes * cohort * slot_pin, &pblk))) return rc;
-    if ((rc = ws_get(ctx, WS_BATCH_RUNS, (size_t)lanes * cohort * slot_dev, &dblk))) return rc;
-    char *pin = (char *)pblk, *pin_dev = nullptr;
-    {
-        void *alias = nullptr;
-        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pin, 0));
-        pin_dev = (char *)alias;
-    }
-    hipStream_t lane_stream[kHubLanes];
-    for (int l = 0; l < lanes; ++l)
-        if ((rc = hub_lane_stream(ctx, l, s, &lane_stream[l]))) return rc;
-    if (lanes > 1) MLPL_HIP_TRY(hipStreamSynchronize(s));  // the correspondences were produced on the caller's stream; a lane's own stream has no other ordering
-    struct LaneOut {
-        long long rounds = 0, merged = 0;
-        int first_err = 0;
-        std::string first_msg;
-    };
-    LaneOut lane_out[kHubLanes];
-    auto serve_lane = [&](int l) {
-        LaneOut &LO = lane_out[l];
-        const hipStream_t ls = lane_stream[l];
-        if (l > 0 && hipSetDevice(ctx->device) != hipSuccess) {  // a lane's own thread starts on device 0
-            LO.first_err = MLPL_E_INTERNAL, LO.first_msg = "batched estimator: hipSetDevice failed on a lane thread";
-            return;
-        }
-        for (int c = l; c < n_cohorts; c += lanes) {
-            const int b0 = c * cohort, nb = std::min(cohort, B - b0);
-            char *dev0 = (char *)dblk + (size_t)l * cohort * slot_dev;
-            if (clear_labels &&  // the label rows of all this cohort's slots: -1 = taken by no round
-                hipMemset2DAsync(dev0 + Y.dev_total + Y.pl_labels, slot_dev, 0xFF, (size_t)n_max * 4, (size_t)nb, ls) != hipSuccess) {
-                LO.first_err = MLPL_E_HIP, LO.first_msg = std::string(name) + ": clearing the label rows failed";
-                break;
-            }
-            BatchHub hub(ctx, ls, nb, l);
-            std::vector<HomBufs> bufs((size_t)nb);
-            std::vector<std::string> msgs((size_t)nb);
-            for (int k = 0; k < nb; ++k) {
-                const size_t slot = (size_t)l * cohort + k;
-                bufs[k].carve(n_max, (char *)dblk + slot * slot_dev, pin + slot * slot_pin, pin_dev + slot * slot_pin, want_planes);
-            }
-            HubThreads &pool = hub_resources(ctx)->lane[l].threads;
-            pool.start(nb, [&](int k) {
-                const int b = b0 + k;
-                HubRun &hr = hub.run(k);
-                int r = MLPL_OK;
-                try {
-                    Launcher L;
-                    L.s = ls, L.hub = &hub, L.run = &hr;
-                    r = job(b, bufs[k], L);
-                } catch (const std::bad_alloc &) {
-                    r = MLPL_E_NOMEM;
-                    set_error("out of host memory");
-                } catch (...) {  // (anything else -- a length_error of a vector, say -- must not unwind off the fiber's makecontext frame)
-                    r = MLPL_E_INTERNAL;
-                    set_error("a run ended with an unexpected C++ exception");
-                }
-                if (r && r != MLPL_E_FAILED) msgs[k] = std::string(name) + ": problem " + std::to_string(b) + ": " + mlpl_last_error();
-                status[b] = r;
-                hub.finish(hr);
-            }, ctx->opt_hub_workers);
-            const int hrc = hub.serve();
-            pool.wait();
-            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches();
-            for (int k = 0; k < nb && !LO.first_err; ++k)
-                if (status[b0 + k] && status[b0 + k] != MLPL_E_FAILED) LO.first_err = status[b0 + k], LO.first_msg = msgs[k];
-            if (hrc && !LO.first_err) LO.first_err = hrc;
-            if (LO.first_err) break;
-        }
-    };
-    {
-        std::vector<std::thread> others;
-        for (int l = 1; l < lanes; ++l) others.emplace_back(serve_lane, l);
-        serve_lane(0);
-        for (auto &t : others) t.join();
-    }
-    int first_err = 0;
-    std::string first_msg;
-    long long rounds = 0, merged = 0;
-    for (int l = 0; l < lanes; ++l) {
-        rounds += lane_out[l].rounds, merged += lane_out[l].merged;
-        if (lane_out[l].first_err && !first_err) first_err = lane_out[l].first_err, first_msg = lane_out[l].first_msg;
-    }
-    ctx->last_arrsac_stats[8] = rounds, ctx->last_arrsac_stats[9] = merged;  // the hub's counters, where the E batch leaves its own
-    if (first_err) {
-        if (!first_msg.empty()) set_error("%s", first_msg.c_str());
-        return first_err;
-    }
-    return MLPL_OK;
+    const size_t slot_dev = Y.dev_total + (want_planes ? HomBufs::up(Y.planes_total) : 0);
+    HubBatch P{name, kHomBatchRuns, slot_dev, Y.pin_total, true, nullptr};
+    if (clear_labels)  // the label rows of all the cohort's slots: -1 = taken by no round
+        P.before_cohort = [=](const HubCohort &c) {
+            if (hipMemset2DAsync(c.dev + Y.dev_total + Y.pl_labels, slot_dev, 0xFF, (size_t)n_max * 4, (size_t)c.size, c.stream) == hipSuccess) return (int)MLPL_OK;
+            set_error("%s: clearing the label rows failed", name);
+            return (int)MLPL_E_HIP;
+        };
+    return hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) {
+        HomBufs bufs;
+        bufs.carve(n_max, slot.dev, slot.pin, slot.pin_dev, want_planes);
+        return job(b, bufs, L);
+    });
 }
 }  // namespace
 

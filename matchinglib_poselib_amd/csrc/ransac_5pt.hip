@@ -4732,24 +4732,8 @@ int mlpl_pair_pose_batch_lanes_dev(mlpl_ctx *const *ctxs, void *const *streams, 
             lane_span_ms[2 * l + 1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
     };
-    {
-        std::vector<std::thread> others;
-        struct Join {  // whatever happens below, no joinable thread is destroyed
-            std::vector<std::thread> &t;
-            ~Join() {
-                for (auto &x : t)
-                    if (x.joinable()) x.join();
-            }
-        } join{others};
-        try {
-            others.reserve((size_t)L);
-            for (int l = 1; l < L; ++l) others.emplace_back(run_lane, l);
-        } catch (const std::exception &e) {  // a thread could not be started: the lanes that did start finish their shares, the call fails
-            set_error("mlpl_pair_pose_batch_lanes_dev: %s", e.what());
-            return MLPL_E_INTERNAL;
-        }
-        run_lane(0);
-    }
+    // (a thread that cannot be started: the lanes that did start finish their shares, the call fails)
+    if (const int lrc = hub_on_lanes(L, "mlpl_pair_pose_batch_lanes_dev", run_lane)) return lrc;
     for (int l = 0; l < L; ++l)
         if (rcs[l]) {
             set_error("%s", msgs[l].c_str());

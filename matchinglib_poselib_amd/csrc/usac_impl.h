@@ -3001,12 +3001,7 @@ int usac_essential_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const dou
             if (LO.first_err) break;
         }
     };
-    {
-        std::vector<std::thread> others;
-        for (int l = 1; l < lanes; ++l) others.emplace_back(serve_lane, l);
-        serve_lane(0);
-        for (auto &t : others) t.join();
-    }
+    if ((rc = hub_on_lanes(lanes, "mlpl_usac_essential_batch_dev", serve_lane))) return rc;
     long long rounds = 0, merged = 0, host_us = 0, device_us = 0, spawn_us = 0;
     int first_err = 0;
     std::string first_msg;

@@ -51,6 +51,55 @@ def test_batch_equals_the_single_problem_entry(ctx, refine):
     assert oks >= B - 6
 
 
+def test_cohort_and_lane_edges(ctx, oracle):
+    """The batch on the hub's cohort / lane driver (csrc/batch_hub.h): 19 problems as one cohort, as cohorts of 8, 8 and 3 on one lane and on
+    two, with one and three worker threads -- the same bytes every time, and those of the single entry.  Scenes and stream pairs are chosen
+    so that the CPU restatement returns a model for every problem (checked for all 19 when they were chosen, asserted here for two)."""
+    import torch
+    import option_guard
+    from matchinglib_poselib_amd import pose
+
+    B, stride = 19, 300
+    sizes = [(80, 150, 300)[b % 3] for b in range(B)]
+    scenes = [make_golden.usac_scene(sizes[b], 0.6 + 0.2 * b / 18, 1300 + b) for b in range(B)]
+    th = scenes[0][2]
+    p1, p2 = np.zeros((B, stride, 2)), np.zeros((B, stride, 2))
+    for b, (a, c, t, truth, order) in enumerate(scenes):
+        assert t == th
+        p1[b, :sizes[b]], p2[b, :sizes[b]] = a, c
+    states = np.array([[0xFFFFFFFF + 977 * (b + 1), 0xFFFFFFFF + 31 * (b + 1) * (b + 1)] for b in range(B)], np.uint64)
+    assert len({tuple(s) for s in states.tolist()}) == B
+    for b in (0, B - 1):                     # the choice of the seeds, checked where it was made
+        assert oracle.arrsac_essential(p1[b, :sizes[b]], p2[b, :sizes[b]], th, rng_state=states[b].copy())["ok"]
+    dev = torch.device("cuda:0")
+    d1, d2 = torch.from_numpy(p1).to(dev), torch.from_numpy(p2).to(dev)
+
+    def run():
+        masks = torch.full((B, stride), 7, dtype=torch.uint8, device=dev)
+        st = states.copy()
+        got = pose.arrsac_essential_batch(d1, d2, sizes, th, rng_states=st, masks_out=masks, ctx=ctx)
+        return dict(E=np.stack([g["E"] for g in got]), n_inliers=np.array([g["n_inliers"] for g in got], np.int32),
+                    status=np.array([g["ok"] for g in got]), states=st, masks=masks.cpu().numpy())
+
+    ref = run()                              # the default setting: one cohort of 19
+    assert np.all(ref["status"])
+    for b in range(B):
+        n, st = sizes[b], states[b].copy()
+        one = pose.arrsac_essential(p1[b, :n], p2[b, :n], th, rng_state=st, ctx=ctx)
+        assert one["ok"], b
+        assert np.array_equal(ref["E"][b].view(np.uint64), one["E"].ravel().view(np.uint64)), b
+        assert ref["n_inliers"][b] == one["n_inliers"] and np.array_equal(ref["states"][b], st), b
+        assert np.array_equal(ref["masks"][b, :n], one["mask"]) and np.all(ref["masks"][b, n:] == 7), b
+    for lanes in (1, 2, 4):
+        for workers in (1, 3):
+            # cohorts of 8, 8 and 3 on one lane and on two (lane 1 serves one cohort, lane 0 two); asked for four lanes, hub_cohort_size
+            # keeps fewer than 8 problems per lane together: one cohort of 19
+            with option_guard.options(ctx, hub_cohort=8, hub_lanes=lanes, hub_workers=workers):
+                bt = run()
+            for key in ("E", "n_inliers", "status", "states", "masks"):
+                assert bt[key].tobytes() == ref[key].tobytes(), (f"hub_lanes={lanes} hub_workers={workers}", key)
+
+
 def test_batched_image_pairs_with_arrsac_equal_the_single_problem_entries(ctx):
     """mlpl_pair_pose_batch_arrsac_dev against match -> gather -> mlpl_arrsac_essential -> getPoseTriangPts per pair."""
     import ctypes as C

@@ -1486,28 +1486,22 @@ int arrsac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, 
 // (0, MLPL_E_FAILED, < 0 errors), E, n_inliers, its mask at d_masks + b * stride.  Every problem's outputs are those of
 // mlpl_arrsac_essential_dev on it alone.
 constexpr int kArrBatchRuns = 128;
+// the hub's counters of an ARRSAC or homography batch whose lanes ran, where mlpl_arrsac_last_stats reports them
+static void hub_arrsac_stats(mlpl_ctx *ctx, const HubBatchStats &st) {
+    if (st.lanes) ctx->last_arrsac_stats[8] = st.rounds, ctx->last_arrsac_stats[9] = st.merged;
+}
 
 int arrsac_essential_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double thresh,
                                int refine, uint64_t *rng_states, double *E, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, hipStream_t s,
                                const CohortFeed *feed = nullptr) {
-    const char *name = "mlpl_arrsac_essential_batch_dev";
-    HubBatch P{name, kArrBatchRuns, 0, 0, !feed, nullptr};
+    HubBatch P{"mlpl_arrsac_essential_batch_dev", kArrBatchRuns, 0, 0, !feed, nullptr};
+    P.feed = feed;
     for (int b = 0; b < (feed ? 1 : B); ++b) {  // (a feed delivers the counts later: blocks for `stride` correspondences)
         const ArrsacRun::Layout Y = ArrsacRun::layout(std::max(feed ? stride : counts[b], 6));
         P.slot_dev = std::max(P.slot_dev, Y.dev_total), P.slot_pin = std::max(P.slot_pin, Y.pin_total);
     }
-    if (feed)  // the producer's event (everything this cohort reads on the device is behind it), then its host-side hand-over
-        P.before_cohort = [=](const HubCohort &c) {
-            if (feed->cohort != c.cohort || feed->n_cohorts != c.n_cohorts) {
-                set_error("%s: the feed's cohorts are not the estimator's", name);
-                return (int)MLPL_E_INTERNAL;
-            }
-            int frc = hipEventSynchronize(feed->ready[c.index]) == hipSuccess ? MLPL_OK : MLPL_E_HIP;
-            if (!frc) frc = feed->on_ready(c.index, hub_resources(ctx)->lane[c.lane].threads);
-            if (frc) set_error("%s: the hand-over of a cohort failed", name);
-            return frc;
-        };
-    return hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) {
+    HubBatchStats st;
+    const int rc = hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) {
         int ninl = 0, r = MLPL_E_FAILED;  // (a pair without enough matches in a batch of image pairs: nothing to estimate)
         if (counts[b] >= 6) {
             ArrsacRun R;
@@ -1517,5 +1511,7 @@ int arrsac_essential_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const d
         }
         if (n_inliers) n_inliers[b] = ninl;
         return r;
-    });
+    }, st);
+    hub_arrsac_stats(ctx, st);
+    return rc;
 }

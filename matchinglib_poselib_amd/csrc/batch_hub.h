@@ -1,6 +1,6 @@
 // batch_hub.h -- many sequential estimators (USAC, ARRSAC) sharing every kernel launch.
 // Included by ransac_5pt.hip inside namespace mlpl, before arrsac_impl.h / homography_impl.h / usac_impl.h.  At its end: the cohort / lane
-// driver of the batched ARRSAC estimators (hub_batch_drive: essential matrix, homography, multi-plane, pose from planes) and hub_on_lanes,
+// driver of the batched estimators (hub_batch_drive: USAC, ARRSAC's essential matrix, homography, multi-plane, pose from planes) and hub_on_lanes,
 // which every entry that serves lanes on threads of their own starts them with.
 //
 // USAC and ARRSAC are sequential programs whose control flow runs on the host (usac_impl.h, arrsac_impl.h): a run alternates between
@@ -298,6 +298,17 @@ struct CohortFeed {
     const hipEvent_t *ready = nullptr;
     std::function<int(int c, HubThreads &pool)> on_ready;
 };
+// The events of a batch (one per cohort), destroyed on every way out of the entry that created them.
+struct HubEvents {
+    std::vector<hipEvent_t> ev;
+    explicit HubEvents(size_t n = 0) : ev(n, nullptr) {}
+    HubEvents(const HubEvents &) = delete;
+    HubEvents &operator=(const HubEvents &) = delete;
+    ~HubEvents() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 
 class BatchHub;
 struct HubRun {  // one run's side of the hub
@@ -521,10 +532,16 @@ inline int hub_on_lanes(int lanes, const char *name, const Fn &fn) {
 // run a fiber on one of the lane's worker threads, every launch merged over the cohort's runs by its BatchHub.  A run's blocks are one slot
 // of WS_BATCH_RUNS (slot_dev bytes) and one of the batch's pinned block (slot_pin bytes); the slots of lane l are [l * cohort, (l + 1) * cohort).
 // job(b, slot, launcher) is problem b's sequential program -- the one the single entry runs -- and returns its status; status[b] receives
-// it.  before_cohort (may be empty) runs on the lane's thread before a cohort's hub is built: what the cohort needs on the device or from
-// a producer first; it reports a failure with set_error.  Every problem's outputs are those of the single entry on it alone.
+// it.  Per cohort, on the lane's thread and before the cohort's hub is built: the feed's hand-over (if there is a feed), then before_cohort
+// (may be empty) -- what the cohort needs on the device or on the host first; it reports a failure with set_error.  before_lanes (may be
+// empty) runs once on the caller's thread when the geometry and the pinned block are known and no lane has started: it receives the
+// shared_pin bytes in front of the run slots (USAC: the host copies of the correspondences).  Every problem's outputs are those of the
+// single entry on it alone.
 struct HubSlot {  // a run's blocks
     char *dev = nullptr, *pin = nullptr, *pin_dev = nullptr;
+};
+struct HubGeometry {
+    int cohort, n_cohorts, lanes;
 };
 struct HubCohort {
     int lane, index, size;  // the lane that serves it, its number, its runs
@@ -536,29 +553,50 @@ struct HubBatch {
     const char *name;             // the entry, for messages
     int cohort_default;           // the estimator's cohort size without the option
     size_t slot_dev, slot_pin;
-    bool inputs_on_caller_stream; // the problems' inputs were produced on the caller's stream (no producer orders them for the lanes)
+    bool inputs_on_caller_stream; // the driver has to wait for the caller's stream before lanes with streams of their own read the inputs
     std::function<int(const HubCohort &)> before_cohort;
+    int lanes_default = kHubLanesDefault;  // the estimator's lanes without the option
+    size_t shared_pin = 0;                 // bytes of the pinned block in front of the run slots (a multiple of 256)
+    const CohortFeed *feed = nullptr;      // a producer that delivers the problems cohort by cohort
+    std::function<int(const HubGeometry &, char *shared_pin)> before_lanes;
+};
+struct HubBatchStats {  // what a call did (the callers keep what their entry reports)
+    long long rounds = 0, merged = 0;       // the hubs' rounds and merged launches
+    long long host_us = 0, device_us = 0;   // BatchHub::host_us / device_us, summed over the cohorts
+    long long spawn_us = 0, total_us = 0;   // starting the cohorts' runs; the lanes from first to last
+    int lanes = 0, n_cohorts = 0;           // the geometry the call ran with (0: no lane was started)
+    std::vector<double> cohort_ms;          // [n_cohorts][3]: handed over, runs started, all finished (ms since the lanes' start)
 };
 static int hub_batch_drive(mlpl_ctx *ctx, int B, const HubBatch &P, int32_t *status, hipStream_t s,
-                           const std::function<int(int, const HubSlot &, const Launcher &)> &job) {
+                           const std::function<int(int, const HubSlot &, const Launcher &)> &job, HubBatchStats &st) {
     if (B <= 0) return MLPL_OK;
-    int rc, n_cohorts = 0, lanes = 0;
-    const int cohort = hub_cohort_size(ctx, B, P.cohort_default, &n_cohorts, &lanes);
+    int rc;
+    HubGeometry G;
+    G.cohort = hub_cohort_size(ctx, B, P.cohort_default, &G.n_cohorts, &G.lanes, P.lanes_default);
+    const int cohort = G.cohort, n_cohorts = G.n_cohorts, lanes = G.lanes;
+    if (P.feed && (P.feed->cohort != cohort || P.feed->n_cohorts != n_cohorts)) {
+        set_error("%s: the feed's cohorts are not the estimator's", P.name);
+        return MLPL_E_INTERNAL;
+    }
     void *pblk, *dblk;
-    if ((rc = pinned_batch_get(ctx, (size_t)lanes * cohort * P.slot_pin, &pblk))) return rc;
+    if ((rc = pinned_batch_get(ctx, P.shared_pin + (size_t)lanes * cohort * P.slot_pin, &pblk))) return rc;
     if ((rc = ws_get(ctx, WS_BATCH_RUNS, (size_t)lanes * cohort * P.slot_dev, &dblk))) return rc;
-    char *pin = (char *)pblk, *pin_dev = nullptr;
+    char *pin = (char *)pblk + P.shared_pin, *pin_dev = nullptr;
     {
         void *alias = nullptr;
-        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pin, 0));
-        pin_dev = (char *)alias;
+        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pblk, 0));
+        pin_dev = (char *)alias + P.shared_pin;
     }
     hipStream_t lane_stream[kHubLanes];
     for (int l = 0; l < lanes; ++l)
         if ((rc = hub_lane_stream(ctx, l, s, &lane_stream[l]))) return rc;
     if (lanes > 1 && P.inputs_on_caller_stream) MLPL_HIP_TRY(hipStreamSynchronize(s));  // a lane's own stream has no other ordering behind the caller's
+    if (P.before_lanes && (rc = P.before_lanes(G, (char *)pblk))) return rc;
+    const auto t_all = std::chrono::steady_clock::now();
+    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all).count(); };
+    st.cohort_ms.assign((size_t)n_cohorts * 3, 0.0);
     struct LaneOut {
-        long long rounds = 0, merged = 0;
+        long long rounds = 0, merged = 0, host_us = 0, device_us = 0, spawn_us = 0;
         int first_err = 0;
         std::string first_msg;
     };
@@ -571,8 +609,17 @@ static int hub_batch_drive(mlpl_ctx *ctx, int B, const HubBatch &P, int32_t *sta
             return;
         }
         const size_t slot0 = (size_t)l * cohort;
+        HubThreads &pool = hub_resources(ctx)->lane[l].threads;
         for (int c = l; c < n_cohorts; c += lanes) {
             const int b0 = c * cohort, nb = std::min(cohort, B - b0);
+            if (P.feed) {  // the producer's event (everything this cohort reads on the device is behind it), then its host-side hand-over
+                int frc = hipEventSynchronize(P.feed->ready[c]) == hipSuccess ? MLPL_OK : MLPL_E_HIP;
+                if (!frc) frc = P.feed->on_ready(c, pool);
+                if (frc) {
+                    LO.first_err = frc, LO.first_msg = std::string(P.name) + ": the hand-over of a cohort failed";
+                    break;
+                }
+            }
             if (P.before_cohort) {
                 const HubCohort hc{l, c, nb, cohort, n_cohorts, ls, (char *)dblk + slot0 * P.slot_dev};
                 if ((LO.first_err = P.before_cohort(hc))) {
@@ -580,9 +627,10 @@ static int hub_batch_drive(mlpl_ctx *ctx, int B, const HubBatch &P, int32_t *sta
                     break;
                 }
             }
+            st.cohort_ms[(size_t)c * 3] = since();
             BatchHub hub(ctx, ls, nb, l);
+            const auto t_spawn = std::chrono::steady_clock::now();
             std::vector<std::string> msgs((size_t)nb);
-            HubThreads &pool = hub_resources(ctx)->lane[l].threads;
             pool.start(nb, [&](int k) {
                 const int b = b0 + k;
                 HubRun &hr = hub.run(k);
@@ -604,9 +652,12 @@ static int hub_batch_drive(mlpl_ctx *ctx, int B, const HubBatch &P, int32_t *sta
                 status[b] = r;
                 hub.finish(hr);
             }, ctx->opt_hub_workers);
+            LO.spawn_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_spawn).count();
+            st.cohort_ms[(size_t)c * 3 + 1] = since();
             const int hrc = hub.serve();
             pool.wait();
-            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches();
+            st.cohort_ms[(size_t)c * 3 + 2] = since();
+            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches(), LO.host_us += hub.host_us(), LO.device_us += hub.device_us();
             for (int k = 0; k < nb && !LO.first_err; ++k)
                 if (status[b0 + k] && status[b0 + k] != MLPL_E_FAILED) LO.first_err = status[b0 + k], LO.first_msg = msgs[k];
             if (hrc && !LO.first_err) LO.first_err = hrc;
@@ -616,12 +667,13 @@ static int hub_batch_drive(mlpl_ctx *ctx, int B, const HubBatch &P, int32_t *sta
     if ((rc = hub_on_lanes(lanes, P.name, serve_lane))) return rc;
     int first_err = 0;
     std::string first_msg;
-    long long rounds = 0, merged = 0;
     for (int l = 0; l < lanes; ++l) {
-        rounds += lane_out[l].rounds, merged += lane_out[l].merged;
-        if (lane_out[l].first_err && !first_err) first_err = lane_out[l].first_err, first_msg = lane_out[l].first_msg;
+        const LaneOut &LO = lane_out[l];
+        st.rounds += LO.rounds, st.merged += LO.merged, st.host_us += LO.host_us, st.device_us += LO.device_us, st.spawn_us += LO.spawn_us;
+        if (LO.first_err && !first_err) first_err = LO.first_err, first_msg = LO.first_msg;
     }
-    ctx->last_arrsac_stats[8] = rounds, ctx->last_arrsac_stats[9] = merged;  // the hub's counters
+    st.lanes = lanes, st.n_cohorts = n_cohorts;
+    st.total_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_all).count();
     if (first_err) {
         if (!first_msg.empty()) set_error("%s", first_msg.c_str());
         return first_err;

@@ -1111,11 +1111,14 @@ static int homography_batch_drive(mlpl_ctx *ctx, int B, const int32_t *counts, b
             set_error("%s: clearing the label rows failed", name);
             return (int)MLPL_E_HIP;
         };
-    return hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) {
+    HubBatchStats st;
+    const int rc = hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) {
         HomBufs bufs;
         bufs.carve(n_max, slot.dev, slot.pin, slot.pin_dev, want_planes);
         return job(b, bufs, L);
-    });
+    }, st);
+    hub_arrsac_stats(ctx, st);
+    return rc;
 }
 }  // namespace
 

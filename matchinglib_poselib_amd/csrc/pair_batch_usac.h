@@ -86,14 +86,8 @@ int pair_pose_batch_usac_dev(mlpl_ctx *ctx, int B, const DescView &dv, int nq, i
     int cohort = hub_cohort_size(ctx, B, tmpl ? kUsacBatchRuns : kArrBatchRuns, &n_cohorts, &lanes_used, tmpl ? hub_usac_lanes_default(tmpl->refine) : kHubLanesDefault);
     const bool use_feed = ctx->opt_pair_batch_feed != 0 && n_cohorts > 1;
     if (!use_feed) cohort = B, n_cohorts = 1;  // (option pair_batch_feed = 0, A/B: everything is matched first, then the estimators start -- round 4's order)
-    std::vector<hipEvent_t> ready((size_t)n_cohorts, nullptr);
-    struct EventsGuard {
-        std::vector<hipEvent_t> &ev;
-        ~EventsGuard() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } ready_guard{ready};
+    HubEvents ready_events((size_t)n_cohorts);
+    std::vector<hipEvent_t> &ready = ready_events.ev;
     // on a stream of its own, ordered behind the caller's: lane 0 of the estimators serves on the caller's stream, which must not queue
     // behind the matching of the later cohorts
     HubStreams *hres = hub_resources(ctx);

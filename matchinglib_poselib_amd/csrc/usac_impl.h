@@ -1291,17 +1291,11 @@ inline std::mutex &usac_prosac_tab_mutex() {
     return m;
 }
 
-struct UsacBufs {  // a run's device / pinned buffers when the caller provides them (batched runs: one slice per run, usac_batch.h)
-    char *dev = nullptr;      // device block of dev_bytes(n, refine)
-    char *pin = nullptr;      // pinned, device-mapped block of pin_bytes(...)
-    char *pin_dev = nullptr;  // its device alias
-};
-
 struct UsacRun {
     mlpl_ctx *ctx;
     hipStream_t s;
     Launcher L;                  // launches now (a run alone) or records for the hub (a run of a batch)
-    const UsacBufs *bufs = nullptr;
+    const HubSlot *bufs = nullptr;  // a run of a batch: its slot of the driver's device and pinned, device-mapped blocks (usac_layout's sizes)
     double *trace_buf = nullptr;  // decision trace of this run (batched runs: one buffer per run; else the context's)
     int trace_cap = 0, trace_len = 0;
     const double *d_p1, *d_p2;
@@ -2760,6 +2754,12 @@ static void usac_results(const UsacRun &R, bool ok, double *results) {
                             R.sprt_epsilon};
     std::memcpy(results, fin, sizeof(fin));
 }
+// what estimateEssentialMatUsac reports of the degeneracy tests (usac_estimations.cpp:564-636, 689-726)
+static void usac_degen_report(const UsacRun &R, double d[16]) {
+    std::memset(d, 0, 128);
+    d[0] = R.dg_on ? 1.0 : 0.0, d[1] = R.dg_cnt_rot, d[2] = R.dg_cnt_nomot, d[3] = R.dg_type;
+    std::memcpy(d + 4, R.dg_R, 72);
+}
 // the inlier mask of the run's model to device memory (through the run's pinned block; the run waits for the copy)
 static int usac_mask_to_device(UsacRun &R, uint8_t *d_mask) {
     std::memcpy(R.h_lo5_flags, R.flags.data(), (size_t)R.n);
@@ -2790,11 +2790,8 @@ int usac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, in
     }
     ctx->usac_trace_len = R.trace_len;
     std::memcpy(ctx->last_usac_stats, R.stats, sizeof(R.stats));
-    {  // what estimateEssentialMatUsac reports of the degeneracy tests (usac_estimations.cpp:564-636, 689-726)
-        double *d = ctx->last_usac_degen;
-        std::memset(d, 0, sizeof(ctx->last_usac_degen));
-        d[0] = R.dg_on ? 1.0 : 0.0, d[1] = R.dg_cnt_rot, d[2] = R.dg_cnt_nomot, d[3] = R.dg_type;
-        std::memcpy(d + 4, R.dg_R, 72);
+    {  // the degeneracy tests' report and the two inlier masks behind it
+        usac_degen_report(R, ctx->last_usac_degen);
         std::free(ctx->last_usac_flags);
         ctx->last_usac_flags = nullptr, ctx->last_usac_flags_n = 0;
         if (R.dg_on && n > 0 && R.dg_in_rot.size() == (size_t)n) {
@@ -2833,191 +2830,103 @@ struct UsacBatchTrace {
     int32_t *lens;     // [B]
 };
 
+// A cohort's correspondences to the host copies of the batch, on stream s: only the rows in use (counts[b] <= max_n of the stride rows of a problem)
+static int usac_stage_cohort(const double *d_p1, const double *d_p2, double *h_p1, double *h_p2, int stride, const int32_t *counts, int b0, int nb, hipStream_t s) {
+    int max_n = 1;
+    for (int b = b0; b < b0 + nb; ++b) max_n = std::max(max_n, counts[b]);
+    const size_t at = (size_t)b0 * stride * 2, pitch = (size_t)stride * 16;
+    MLPL_HIP_TRY(hipMemcpy2DAsync(h_p1 + at, pitch, d_p1 + at, pitch, (size_t)max_n * 16, (size_t)nb, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipMemcpy2DAsync(h_p2 + at, pitch, d_p2 + at, pitch, (size_t)max_n * 16, (size_t)nb, hipMemcpyDeviceToHost, s));
+    return MLPL_OK;
+}
+
 int usac_essential_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                              const mlpl_usac_params *params, double *E, uint8_t *d_masks, double *results, int32_t *status, double *degen,
                              const UsacBatchTrace *trace, hipStream_t s, const CohortFeed *feed = nullptr) {
     if (B <= 0) return MLPL_OK;
-    int rc;
-    // the sequential parts read the correspondences on the host: one copy of the whole block through the batch's pinned memory
-    size_t max_dev = 0, max_pin = 0;
+    const char *name = "mlpl_usac_essential_batch_dev";
+    // Cohorts of <= kUsacBatchRuns runs, several of them in flight (batch_hub.h hub_batch_drive): while one cohort's merged launches
+    // execute, the other cohorts' runs walk their bit rows on the host.  The caller's stream is waited for below, not by the driver.
+    HubBatch P{name, kUsacBatchRuns, 0, 0, false, nullptr};
     for (int b = 0; b < B; ++b) {  // (a feed delivers the counts later: blocks for `stride` correspondences)
         const UsacRun::UsacLayout Y = UsacRun::usac_layout((unsigned)std::max(feed ? stride : counts[b], 1), params[b].refine, params[b].check_degeneracy != 0);
-        max_dev = std::max(max_dev, Y.dev_total), max_pin = std::max(max_pin, Y.pin_total);
+        P.slot_dev = std::max(P.slot_dev, Y.dev_total), P.slot_pin = std::max(P.slot_pin, Y.pin_total);
     }
-    // Cohorts of <= kUsacBatchRuns runs, two of them in flight (batch_hub.h kHubLanes): while one cohort's merged launches execute, the
-    // other cohort's runs walk their bit rows on the host.  A batch that fits one cohort is split in two halves for the same reason.
-    int n_cohorts = 0, lanes = 0;
-    const int cohort = hub_cohort_size(ctx, B, kUsacBatchRuns, &n_cohorts, &lanes, hub_usac_lanes_default(params[0].refine));
-    if (feed && (feed->cohort != cohort || feed->n_cohorts != n_cohorts)) {
-        set_error("mlpl_usac_essential_batch_dev: the feed's cohorts are not the estimator's");
-        return MLPL_E_INTERNAL;
-    }
-    const size_t pts_bytes = ((size_t)B * stride * 16 + 255) & ~(size_t)255;
-    void *pblk, *dblk;
-    if ((rc = pinned_batch_get(ctx, 2 * pts_bytes + (size_t)lanes * cohort * max_pin, &pblk))) return rc;
-    if ((rc = ws_get(ctx, WS_BATCH_RUNS, (size_t)lanes * cohort * max_dev, &dblk))) return rc;
-    char *pin = (char *)pblk, *pin_dev = nullptr;
-    {
-        void *alias = nullptr;
-        MLPL_HIP_TRY(hipHostGetDevicePointer(&alias, pin, 0));
-        pin_dev = (char *)alias;
-    }
-    double *h_p1 = (double *)pin, *h_p2 = (double *)(pin + pts_bytes);
     // The sequential parts read the correspondences on the host (normalisation, sample validation, the choices of the 5-point refinements,
-    // the degeneracy tests): they cross PCIe once, cohort by cohort on a stream of their own, so that the first cohort starts after its
-    // own slice has arrived (512 problems of 5000: 3.4 ms for all, 0.85 ms for the first quarter) and the rest travels beside its work.
-    if (!feed) MLPL_HIP_TRY(hipStreamSynchronize(s));  // everything the caller queued before is done: the lanes' own streams need no other ordering
-    HubStreams *hres = hub_resources(ctx);
-    if (!hres->copy) MLPL_HIP_TRY(hipStreamCreateWithFlags(&hres->copy, hipStreamNonBlocking));
-    std::vector<hipEvent_t> arrived((size_t)n_cohorts, nullptr);
-    struct EventsGuard {
-        std::vector<hipEvent_t> &ev;
-        ~EventsGuard() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
+    // the degeneracy tests): they cross PCIe once into the front of the batch's pinned block, cohort by cohort on a stream of their own, so
+    // that the first cohort starts after its own slice has arrived (512 problems of 5000: 3.4 ms for all, 0.85 ms for the first quarter)
+    // and the rest travels beside its work.  With a feed a lane fetches its cohort's slice on its own stream after the hand-over.
+    const size_t pts_bytes = ((size_t)B * stride * 16 + 255) & ~(size_t)255;
+    P.lanes_default = hub_usac_lanes_default(params[0].refine), P.shared_pin = 2 * pts_bytes, P.feed = feed;
+    double *h_p1 = nullptr, *h_p2 = nullptr;
+    HubEvents arrived;
+    uint64_t tsc_all0 = 0;
+    P.before_lanes = [&](const HubGeometry &G, char *shared) -> int {
+        h_p1 = (double *)shared, h_p2 = (double *)(shared + pts_bytes);
+        if (!feed) {
+            MLPL_HIP_TRY(hipStreamSynchronize(s));  // everything the caller queued before is done: the copy stream and the lanes' own streams need no other ordering
+            HubStreams *hres = hub_resources(ctx);
+            if (!hres->copy) MLPL_HIP_TRY(hipStreamCreateWithFlags(&hres->copy, hipStreamNonBlocking));
+            arrived.ev.assign((size_t)G.n_cohorts, nullptr);
+            for (int c = 0; c < G.n_cohorts; ++c) {
+                const int b0 = c * G.cohort;
+                if (const int src = usac_stage_cohort(d_p1, d_p2, h_p1, h_p2, stride, counts, b0, std::min(G.cohort, B - b0), hres->copy)) return src;
+                MLPL_HIP_TRY(hipEventCreateWithFlags(&arrived.ev[(size_t)c], hipEventDisableTiming));
+                MLPL_HIP_TRY(hipEventRecord(arrived.ev[(size_t)c], hres->copy));
+            }
         }
-    } events_guard{arrived};
-    for (int c = 0; c < n_cohorts && !feed; ++c) {
-        const int b0 = c * cohort, nb = std::min(cohort, B - b0);
-        int max_n = 1;  // only the rows in use: counts[b] <= max_n of the stride rows of a problem
-        for (int b = b0; b < b0 + nb; ++b) max_n = std::max(max_n, counts[b]);
-        const size_t at = (size_t)b0 * stride * 2;
-        MLPL_HIP_TRY(hipMemcpy2DAsync(h_p1 + at, (size_t)stride * 16, d_p1 + at, (size_t)stride * 16, (size_t)max_n * 16, (size_t)nb, hipMemcpyDeviceToHost, hres->copy));
-        MLPL_HIP_TRY(hipMemcpy2DAsync(h_p2 + at, (size_t)stride * 16, d_p2 + at, (size_t)stride * 16, (size_t)max_n * 16, (size_t)nb, hipMemcpyDeviceToHost, hres->copy));
-        MLPL_HIP_TRY(hipEventCreateWithFlags(&arrived[(size_t)c], hipEventDisableTiming));
-        MLPL_HIP_TRY(hipEventRecord(arrived[(size_t)c], hres->copy));
-    }
-    char *run_pin = pin + 2 * pts_bytes, *run_pin_dev = pin_dev + 2 * pts_bytes;
-    const auto t_all = std::chrono::steady_clock::now();
-    const uint64_t tsc_all0 = UsacRun::tsc();
-    struct LaneOut {
-        long long rounds = 0, merged = 0, host_us = 0, device_us = 0, spawn_us = 0;
-        int first_err = 0;
-        std::string first_msg;
+        tsc_all0 = UsacRun::tsc();
+        return MLPL_OK;
     };
-    LaneOut lane_out[kHubLanes];
-    hipStream_t lane_stream[kHubLanes];
-    for (int l = 0; l < lanes; ++l)
-        if ((rc = hub_lane_stream(ctx, l, s, &lane_stream[l]))) return rc;
+    P.before_cohort = [&](const HubCohort &c) -> int {
+        if (!feed) {
+            if (hipEventSynchronize(arrived.ev[(size_t)c.index]) == hipSuccess) return MLPL_OK;
+            set_error("%s: the copy of the correspondences failed", name);
+            return MLPL_E_INTERNAL;
+        }
+        if (usac_stage_cohort(d_p1, d_p2, h_p1, h_p2, stride, counts, c.index * c.cohort, c.size, c.stream) == MLPL_OK && hipStreamSynchronize(c.stream) == hipSuccess)
+            return MLPL_OK;
+        set_error("%s: the hand-over of a cohort failed", name);
+        return MLPL_E_HIP;
+    };
     std::atomic<uint64_t> prof_sum[UsacRun::PF_NUM], run_stats[5];
     for (auto &v : prof_sum) v.store(0);
     for (auto &v : run_stats) v.store(0);
-    std::vector<double> cohort_ms((size_t)n_cohorts * 3, 0.0);  // debug (MLPL_USAC_PROF): when a cohort was handed over, when its runs started, when they had all finished
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all).count(); };
-    auto serve_lane = [&](int l) {
-        LaneOut &LO = lane_out[l];
-        const hipStream_t ls = lane_stream[l];
-        if (l > 0 && hipSetDevice(ctx->device) != hipSuccess) {  // a lane's own thread starts on device 0
-            LO.first_err = MLPL_E_INTERNAL, LO.first_msg = "batched estimator: hipSetDevice failed on a lane thread";
-            return;
+    HubBatchStats st;
+    const int rc = hub_batch_drive(ctx, B, P, status, s, [&](int b, const HubSlot &slot, const Launcher &L) -> int {
+        const int n = counts[b];
+        const size_t at = (size_t)b * stride * 2;
+        UsacRun R;
+        usac_configure(R, ctx, d_p1 + at, d_p2 + at, n, &params[b], L.s);
+        R.L = L, R.bufs = &slot;
+        if (trace && trace->buf) R.trace_buf = trace->buf + (size_t)b * trace->cap * 16, R.trace_cap = trace->cap;
+        R.hp1.assign(h_p1 + at, h_p1 + at + (size_t)2 * std::max(n, 0));
+        R.hp2.assign(h_p2 + at, h_p2 + at + (size_t)2 * std::max(n, 0));
+        int r = MLPL_OK;
+        bool ok = false;
+        if (n >= 5) {
+            r = R.setup();
+            if (!r) r = R.solve(&ok);
         }
-        for (int c = l; c < n_cohorts; c += lanes) {
-            const int b0 = c * cohort, nb = std::min(cohort, B - b0);
-            if (feed) {  // the producer's event, its host-side hand-over (counts, orders), then this cohort's correspondences to the host
-                int frc = hipEventSynchronize(feed->ready[c]) == hipSuccess ? MLPL_OK : MLPL_E_HIP;
-                if (!frc) frc = feed->on_ready(c, hub_resources(ctx)->lane[l].threads);
-                if (!frc) {
-                    int max_n = 1;
-                    for (int b = b0; b < b0 + nb; ++b) max_n = std::max(max_n, counts[b]);
-                    const size_t at = (size_t)b0 * stride * 2;
-                    if (hipMemcpy2DAsync(h_p1 + at, (size_t)stride * 16, d_p1 + at, (size_t)stride * 16, (size_t)max_n * 16, (size_t)nb, hipMemcpyDeviceToHost, ls) != hipSuccess ||
-                        hipMemcpy2DAsync(h_p2 + at, (size_t)stride * 16, d_p2 + at, (size_t)stride * 16, (size_t)max_n * 16, (size_t)nb, hipMemcpyDeviceToHost, ls) != hipSuccess ||
-                        hipStreamSynchronize(ls) != hipSuccess)
-                        frc = MLPL_E_HIP;
-                }
-                if (frc) {
-                    LO.first_err = frc, LO.first_msg = "mlpl_usac_essential_batch_dev: the hand-over of a cohort failed";
-                    break;
-                }
-            } else if (hipEventSynchronize(arrived[(size_t)c]) != hipSuccess) {
-                LO.first_err = MLPL_E_INTERNAL, LO.first_msg = "mlpl_usac_essential_batch_dev: the copy of the correspondences failed";
-                break;
-            }
-            cohort_ms[(size_t)c * 3] = since();
-            BatchHub hub(ctx, ls, nb, l);
-            const auto t_spawn = std::chrono::steady_clock::now();
-            std::vector<UsacBufs> bufs((size_t)nb);
-            std::vector<std::string> msgs((size_t)nb);
-            for (int k = 0; k < nb; ++k) {
-                const size_t slot = (size_t)l * cohort + k;
-                bufs[k].dev = (char *)dblk + slot * max_dev;
-                bufs[k].pin = run_pin + slot * max_pin, bufs[k].pin_dev = run_pin_dev + slot * max_pin;
-            }
-            HubThreads &pool = hub_resources(ctx)->lane[l].threads;
-            pool.start(nb, [&](int k) {
-                const int b = b0 + k;
-                const int n = counts[b];
-                HubRun &hr = hub.run(k);
-                int r = MLPL_OK;
-                bool ok = false;
-                try {
-                    UsacRun R;
-                    usac_configure(R, ctx, d_p1 + (size_t)b * stride * 2, d_p2 + (size_t)b * stride * 2, n, &params[b], ls);
-                    R.L.hub = &hub, R.L.run = &hr, R.bufs = &bufs[k];
-                    if (trace && trace->buf) R.trace_buf = trace->buf + (size_t)b * trace->cap * 16, R.trace_cap = trace->cap;
-                    R.hp1.assign(h_p1 + (size_t)b * stride * 2, h_p1 + (size_t)b * stride * 2 + (size_t)2 * std::max(n, 0));
-                    R.hp2.assign(h_p2 + (size_t)b * stride * 2, h_p2 + (size_t)b * stride * 2 + (size_t)2 * std::max(n, 0));
-                    if (n >= 5) {
-                        r = R.setup();
-                        if (!r) r = R.solve(&ok);
-                    }
-                    for (int q = 0; q < UsacRun::PF_NUM; ++q) prof_sum[q].fetch_add(R.prof[q], std::memory_order_relaxed);
-                    for (int q = 0; q < 5; ++q) run_stats[q].fetch_add((uint64_t)R.stats[q], std::memory_order_relaxed);
-                    if (!r) {
-                        usac_results(R, ok, results + (size_t)b * 12);
-                        if (trace && trace->lens) trace->lens[b] = R.trace_len;
-                        if (degen) {
-                            double *d = degen + (size_t)b * 16;
-                            std::memset(d, 0, 128);
-                            d[0] = R.dg_on ? 1.0 : 0.0, d[1] = R.dg_cnt_rot, d[2] = R.dg_cnt_nomot, d[3] = R.dg_type;
-                            std::memcpy(d + 4, R.dg_R, 72);
-                        }
-                        if (ok) {
-                            std::memcpy(E + (size_t)b * 9, R.final_model, 72);
-                            if (d_masks) r = usac_mask_to_device(R, d_masks + (size_t)b * stride);
-                        } else
-                            r = MLPL_E_FAILED;
-                    }
-                } catch (const std::bad_alloc &) {
-                    r = MLPL_E_NOMEM;
-                    set_error("mlpl_usac_essential_batch_dev: out of host memory");
-                } catch (...) {  // (anything else -- a length_error of a vector, say -- must not unwind off the fiber's makecontext frame)
-                    r = MLPL_E_INTERNAL;
-                    set_error("mlpl_usac_essential_batch_dev: a run ended with an unexpected C++ exception");
-                }
-                if (r && r != MLPL_E_FAILED) msgs[k] = mlpl_last_error();
-                status[b] = r;
-                hub.finish(hr);
-            }, ctx->opt_hub_workers);
-            LO.spawn_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_spawn).count();
-            cohort_ms[(size_t)c * 3 + 1] = since();
-            const int hrc = hub.serve();
-            pool.wait();
-            cohort_ms[(size_t)c * 3 + 2] = since();
-            LO.rounds += hub.rounds(), LO.merged += hub.merged_launches(), LO.host_us += hub.host_us(), LO.device_us += hub.device_us();
-            for (int k = 0; k < nb && !LO.first_err; ++k)
-                if (status[b0 + k] && status[b0 + k] != MLPL_E_FAILED) LO.first_err = status[b0 + k], LO.first_msg = msgs[k];
-            if (hrc && !LO.first_err) LO.first_err = hrc;
-            if (LO.first_err) break;
-        }
-    };
-    if ((rc = hub_on_lanes(lanes, "mlpl_usac_essential_batch_dev", serve_lane))) return rc;
-    long long rounds = 0, merged = 0, host_us = 0, device_us = 0, spawn_us = 0;
-    int first_err = 0;
-    std::string first_msg;
-    for (int l = 0; l < lanes; ++l) {
-        const LaneOut &LO = lane_out[l];
-        rounds += LO.rounds, merged += LO.merged, host_us += LO.host_us, device_us += LO.device_us, spawn_us += LO.spawn_us;
-        if (LO.first_err && !first_err) first_err = LO.first_err, first_msg = LO.first_msg;
-    }
-    ctx->last_usac_stats[0] = rounds, ctx->last_usac_stats[1] = merged, ctx->last_usac_stats[2] = host_us, ctx->last_usac_stats[3] = device_us;
-    ctx->last_usac_stats[4] = spawn_us;
-    ctx->last_usac_stats[6] = lanes, ctx->last_usac_stats[7] = n_cohorts;   // the configuration the call actually ran with (bench.py records it)
-    ctx->last_usac_stats[5] = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_all).count();
+        for (int q = 0; q < UsacRun::PF_NUM; ++q) prof_sum[q].fetch_add(R.prof[q], std::memory_order_relaxed);
+        for (int q = 0; q < 5; ++q) run_stats[q].fetch_add((uint64_t)R.stats[q], std::memory_order_relaxed);
+        if (r) return r;
+        usac_results(R, ok, results + (size_t)b * 12);
+        if (trace && trace->lens) trace->lens[b] = R.trace_len;
+        if (degen) usac_degen_report(R, degen + (size_t)b * 16);
+        if (!ok) return MLPL_E_FAILED;
+        std::memcpy(E + (size_t)b * 9, R.final_model, 72);
+        return d_masks ? usac_mask_to_device(R, d_masks + (size_t)b * stride) : MLPL_OK;
+    }, st);
+    if (!st.lanes) return rc;  // no lane was started
+    const uint64_t tsc_all1 = UsacRun::tsc();
+    long long *us = ctx->last_usac_stats;
+    us[0] = st.rounds, us[1] = st.merged, us[2] = st.host_us, us[3] = st.device_us, us[4] = st.spawn_us, us[5] = st.total_us;
+    us[6] = st.lanes, us[7] = st.n_cohorts;  // the configuration the call actually ran with (bench.py records it)
     if (const char *pe = getenv("MLPL_USAC_PROF"); pe && *pe == '1') {  // debug: where the runs' host time goes (TSC ticks summed over the runs; waits excluded)
         static const char *names[UsacRun::PF_NUM] = {"setup", "sampler play-forward", "batch hand-over (host)", "waiting for the device", "local optimisation (host)", "solve() total"};
-        const double ticks_per_us = (double)(UsacRun::tsc() - tsc_all0) / std::max<long long>(1, ctx->last_usac_stats[5]);
-        std::fprintf(stderr, "[mlpl usac prof] %d runs, %d lanes, call %.2f ms:", B, lanes, ctx->last_usac_stats[5] / 1e3);
+        const double ticks_per_us = (double)(tsc_all1 - tsc_all0) / std::max<long long>(1, st.total_us);
+        std::fprintf(stderr, "[mlpl usac prof] %d runs, %d lanes, call %.2f ms:", B, st.lanes, st.total_us / 1e3);
         for (int q = 0; q < UsacRun::PF_NUM; ++q) std::fprintf(stderr, " %s %.1f us per run;", names[q], (double)prof_sum[q].load() / ticks_per_us / B);
 #ifdef MLPL_USAC_LO_STAMPS
         {
@@ -3035,12 +2944,8 @@ int usac_essential_batch_dev(mlpl_ctx *ctx, int B, const double *d_p1, const dou
                      (double)run_stats[0].load() / B, (double)run_stats[1].load() / B, (double)run_stats[2].load() / B, (double)run_stats[3].load() / B,
                      (double)run_stats[4].load() / B);
         std::fprintf(stderr, " cohorts (handed over / runs started / all finished, ms):");
-        for (int c = 0; c < n_cohorts; ++c) std::fprintf(stderr, " [%.2f %.2f %.2f]", cohort_ms[(size_t)c * 3], cohort_ms[(size_t)c * 3 + 1], cohort_ms[(size_t)c * 3 + 2]);
+        for (int c = 0; c < st.n_cohorts; ++c) std::fprintf(stderr, " [%.2f %.2f %.2f]", st.cohort_ms[(size_t)c * 3], st.cohort_ms[(size_t)c * 3 + 1], st.cohort_ms[(size_t)c * 3 + 2]);
         std::fprintf(stderr, "\n");
     }
-    if (first_err) {
-        if (!first_msg.empty()) set_error("%s", first_msg.c_str());
-        return first_err;
-    }
-    return MLPL_OK;
+    return rc;
 }

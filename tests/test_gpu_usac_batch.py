@@ -132,6 +132,79 @@ def test_batched_image_pairs_with_usac_equal_the_single_problem_entries(ctx, pro
         assert np.array_equal(raw["t"][i].view(np.uint64), t.ravel().view(np.uint64)), i
 
 
+def test_cohort_and_lane_edges(ctx, oracle):
+    """The batch on the hub's cohort / lane driver (csrc/batch_hub.h): 19 problems (ConfigUSAC's defaults with the degeneracy tests, a
+    decision trace each) as one cohort, as cohorts of 8, 8 and 3 on one lane and on two, with one and three worker threads -- the same
+    bytes every time, and those of the single entry.  Problems 4 (no correspondence) and 11 (four) are refused beside good neighbours.
+    Scenes and seeds are chosen so that the CPU restatement accepts every other problem (checked for all 17 when they were chosen,
+    asserted here for two).  A USAC batch reports its configuration in mlpl_usac_last_stats and leaves ARRSAC's statistics alone."""
+    import torch
+    import option_guard
+    from matchinglib_poselib_amd import pose
+
+    B, stride, cap = 19, 300, 20000
+    sizes = [(80, 150, 300)[b % 3] for b in range(B)]
+    scenes = [make_golden.usac_scene(sizes[b], 0.6 + 0.2 * b / 18, 1500 + b) for b in range(B)]
+    th = scenes[0][2]
+    p1, p2 = np.zeros((B, stride, 2)), np.zeros((B, stride, 2))
+    for b, (a, c, t, truth, order) in enumerate(scenes):
+        assert t == th
+        p1[b, :sizes[b]], p2[b, :sizes[b]] = a, c
+    sizes[4], sizes[11] = 0, 4                 # solve() refuses
+    good = [b for b in range(B) if b not in (4, 11)]
+    seeds = [6100 + 37 * b for b in range(B)]
+    kw = dict(refine=5, estimator=2, max_hyp=2000, check_degeneracy=1, sprt_ms=6.0, sprt_tm=2736.0)
+    for b in (0, B - 1):                       # the choice of the seeds, checked where it was made
+        assert oracle.usac_essential_degen(p1[b, :sizes[b]], p2[b, :sizes[b]], th, seeds[b], check_degeneracy=1, refine=5, max_hyp=2000,
+                                           sprt_ms=6.0, sprt_tm=2736.0)["ok"]
+    dev = torch.device("cuda:0")
+    d1, d2 = torch.from_numpy(p1).to(dev), torch.from_numpy(p2).to(dev)
+
+    def last_stats(fn, n):
+        st = np.zeros(n, np.int64)
+        assert fn(ctx.handle, st.ctypes.data) == 0
+        return st
+
+    def run():
+        masks = torch.full((B, stride), 7, dtype=torch.uint8, device=dev)
+        got = pose.usac_essential_batch(d1, d2, sizes, th, seeds, event_cap=cap, masks_out=masks, ctx=ctx, **kw)
+        assert all(g["n_events"] <= cap for g in got)
+        return dict(E=np.stack([g["E"] for g in got]), final=np.stack([g["final"] for g in got]), status=np.array([g["ok"] for g in got]),
+                    degen=np.stack([np.concatenate([g["degen"], g["R_degen"]]) for g in got]),
+                    n_events=np.array([g["n_events"] for g in got], np.int32), events=np.concatenate([g["events"] for g in got]),
+                    masks=masks.cpu().numpy()), got
+
+    pose.arrsac_essential_batch(d1[:4], d2[:4], sizes[:4], th, ctx=ctx)
+    arr = last_stats(ctx.lib.mlpl_arrsac_last_stats, 12)
+    assert arr[8] > 0 and arr[9] > 0           # the hub's counters of that ARRSAC batch
+    ref, got = run()                           # the default setting: one cohort of 19
+    assert np.array_equal(last_stats(ctx.lib.mlpl_arrsac_last_stats, 12), arr)
+    assert ref["status"].tolist() == [b in good for b in range(B)]
+    for b in range(B):
+        n = sizes[b]
+        assert np.all(ref["masks"][b, n:] == 7), b
+        if b not in good:
+            continue
+        one = pose.usac_essential(p1[b, :n], p2[b, :n], th, seeds[b], event_cap=cap, ctx=ctx, **kw)
+        assert one["ok"], b
+        assert ref["E"][b].tobytes() == one["E"].tobytes() and ref["final"][b].tobytes() == one["final"].tobytes(), b
+        assert ref["masks"][b, :n].tobytes() == one["flags"].tobytes(), b
+        assert got[b]["n_events"] == one["n_events"] and got[b]["events"].tobytes() == one["events"].tobytes(), b
+        assert got[b]["degen"].tobytes() == one["degen"].tobytes() and got[b]["R_degen"].tobytes() == one["R_degen"].tobytes(), b
+    for lanes in (1, 2, 4):
+        for workers in (1, 3):
+            # cohorts of 8, 8 and 3 on one lane and on two (lane 1 serves one cohort, lane 0 two); asked for four lanes, hub_cohort_size
+            # keeps fewer than 8 problems per lane together: one cohort of 19
+            with option_guard.options(ctx, hub_cohort=8, hub_lanes=lanes, hub_workers=workers):
+                bt, _ = run()
+                us = last_stats(ctx.lib.mlpl_usac_last_stats, 8)
+            for key in ref:
+                assert bt[key].tobytes() == ref[key].tobytes(), (f"hub_lanes={lanes} hub_workers={workers}", key)
+            if lanes == 2:
+                assert us[6] == 2 and us[7] == 3, us
+    assert np.array_equal(last_stats(ctx.lib.mlpl_arrsac_last_stats, 12), arr)
+
+
 @pytest.mark.parametrize("opts", [dict(hub_lanes=1), dict(hub_lanes=2, hub_workers=3), dict(hub_lanes=4, hub_cohort=8, hub_workers=1),
                                   dict(hub_lanes=3, hub_cohort=16, hub_workers=64, hub_blocking_sync=0),
                                   dict(hub_lanes=8, hub_cohort=8), dict(hub_lanes=6, usac_lo5_fused_fit=0), dict(usac_lo5_fused_fit=0)])

@@ -25,6 +25,10 @@ What is NOT the reference's text or arithmetic (no SBA build stands behind this 
   * the 6 x 6 system is an unblocked upper Cholesky with sequential dot products and two triangular solves by division.
   * a failed run (fewer measurements than unknowns, i.e. fewer than 12 points; the almost-singular return) leaves info[] all zero here; the
     reference leaves it unwritten.
+
+Beside its results a run reports which way it went, for the tests that must know that a scene reaches the branch it is named for: `attempts`
+(per damping attempt the first V*_i that did not invert, a refused Cholesky, the verdict) and `branch` (MatToQuat's pivot, the two sign fixes,
+the case of |t|, the rules that refused).  None of it feeds back into the arithmetic.
 """
 import numpy as np
 
@@ -96,6 +100,19 @@ def mat_to_quat(R):
         q[j + 1] = (R[j, i] + R[i, j]) * root
         q[k + 1] = (R[k, i] + R[i, k]) * root
     return q
+
+
+def mat_to_quat_pivot(R):
+    """Which branch mat_to_quat takes: -1 for tr > 0, else the index i of the largest diagonal entry as that function picks it."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    if R[0, 0] + R[1, 1] + R[2, 2] > 0.0:
+        return -1
+    i = 0
+    if R[1, 1] > R[0, 0]:
+        i = 1
+    if R[2, 2] > R[i, i]:
+        i = 2
+    return i
 
 
 def quat_to_matrix(q):
@@ -284,11 +301,20 @@ def _chol_solve6(S, b):
     return True, x
 
 
+def jte_inf_norm(ea, eb):
+    """sba_levmar.c:943-944 walks eab with `if(eab_inf < tmp) eab_inf = tmp` from 0: a NaN entry never wins the comparison and is passed over
+    (np.max would hand it on); for entries without a NaN this is the plain maximum of the magnitudes."""
+    return float(np.fmax.reduce(np.concatenate([[0.0], np.abs(ea), np.abs(eb).reshape(-1)])))
+
+
 def sba_motstr(x1, x2, r0, t, M, th, itmax=MAXITER, opts=OPTS):
-    """sba_motstr_levmar_x for two frames with the first fixed -> dict(ok, v, t, M, info[10], mu, trace).  ok False = SBA_ERROR."""
+    """sba_motstr_levmar_x for two frames with the first fixed -> dict(ok, v, t, M, info[10], mu, trace, attempts).  ok False = SBA_ERROR.
+    attempts: one (itno, first_bad, chol_refused, accepted) per damping attempt; first_bad = the first point whose V*_i did not invert, or -1;
+    almost_singular: the run left through the error return behind the stop = 2 test."""
     n = M.shape[0]
     info = np.zeros(10)
-    out = dict(ok=False, v=np.zeros(3), t=np.array(t, np.float64), M=np.array(M, np.float64), info=info, mu=0.0, trace=[])
+    out = dict(ok=False, v=np.zeros(3), t=np.array(t, np.float64), M=np.array(M, np.float64), info=info, mu=0.0, trace=[], attempts=[],
+               almost_singular=False)
     nobs, nvars = 4 * n, 12 + 3 * n
     if nobs < nvars:
         return out
@@ -340,7 +366,7 @@ def sba_motstr(x1, x2, r0, t, M, th, itmax=MAXITER, opts=OPTS):
         for ii in range(6):
             for jj in range(3):
                 W[:, ii, jj] = A[:, 0, ii] * B1[:, 0, jj] + A[:, 1, ii] * B1[:, 1, jj]
-        eab_inf = max(np.abs(ea).max(), np.abs(eb).max())
+        eab_inf = jte_inf_norm(ea, eb)
         pvec = np.concatenate([np.zeros(6), v, t, M.reshape(-1)])
         p_L2 = float(seqsum(pvec * pvec))
         diagU, diagV, have_diag = np.diag(U).copy(), Vd.copy(), True
@@ -367,6 +393,7 @@ def sba_motstr(x1, x2, r0, t, M, th, itmax=MAXITER, opts=OPTS):
                 Vd[:f] = inv[:f][:, [0, 3, 5]]
                 Vd[f] = trial[f]
                 out["trace"].append((mu_used, p_eL2, False))
+                out["attempts"].append((itno, f, False, False))
             else:
                 Vd = inv[:, [0, 3, 5]].copy()
                 Y = np.zeros((n, 6, 3))
@@ -397,14 +424,17 @@ def sba_motstr(x1, x2, r0, t, M, th, itmax=MAXITER, opts=OPTS):
                     v_new, t_new, M_new = v + da[:3], t + da[3:], M + db
                     if dp_L2 <= eps2_sq * p_L2:
                         stop = 2
+                        out["attempts"].append((itno, -1, False, False))
                         break
                     if dp_L2 >= (p_L2 + eps2) / EPSILON_SQ:
+                        out["almost_singular"] = True
                         return out                      # "almost singular": SBA_ERROR, info unwritten
                     with np.errstate(all="ignore"):
                         e_new, pdp_eL2 = residual(v_new, t_new, M_new)
                     nfev += 1
                     if not np.isfinite(pdp_eL2):
                         stop = 7
+                        out["attempts"].append((itno, -1, False, False))
                         break
                     dL = float(seqsum(dp * (mu * dp + eab)))
                     dF = p_eL2 - pdp_eL2
@@ -418,8 +448,10 @@ def sba_motstr(x1, x2, r0, t, M, th, itmax=MAXITER, opts=OPTS):
                         v, t, M, e, p_eL2 = v_new, t_new, M_new, e_new, pdp_eL2
                         accepted = True
                     out["trace"].append((mu_used, pdp_eL2, accepted))
+                    out["attempts"].append((itno, -1, False, accepted))
                 else:
                     out["trace"].append((mu_used, p_eL2, False))
+                    out["attempts"].append((itno, -1, True, False))
                 if accepted:
                     break
             mu *= nu
@@ -454,11 +486,14 @@ def convert_threshold(K1, K2, huber_thresh=-1.0):
 
 
 def ba_oracle(p1, p2, R, t, Q, th, mask=None, angle_thresh=1.25, t_norm_thresh=0.05):
-    """mlpl_refine_stereo_ba: th in CAMERA units.  -> dict(accepted, R, t, Q, info, mu, trace); on rejection or failure R, t, Q equal the inputs."""
+    """mlpl_refine_stereo_ba: th in CAMERA units.  -> dict(accepted, R, t, Q, info, mu, trace, attempts, branch); on rejection or failure R, t, Q
+    equal the inputs.  branch: which way the wrapper went -- pivot (mat_to_quat_pivot), r0_flipped, and once the optimiser has ended normally
+    qn_flipped, t_case ("kept_unit": |t| within 1e-4 of 1, "kept_tiny": |t| < 1e-3, "normalised") and refused_by (a tuple out of "angle",
+    "t_norm", "stop", empty when accepted)."""
     p1, p2 = np.asarray(p1, np.float64).reshape(-1, 2), np.asarray(p2, np.float64).reshape(-1, 2)
     R0, t0 = np.array(R, np.float64).reshape(3, 3), np.array(t, np.float64).reshape(3)
     Q0 = np.array(Q, np.float64).reshape(-1, 3)
-    res = dict(accepted=False, R=R0.copy(), t=t0.copy(), Q=Q0.copy(), info=np.zeros(10), mu=0.0, trace=[])
+    res = dict(accepted=False, R=R0.copy(), t=t0.copy(), Q=Q0.copy(), info=np.zeros(10), mu=0.0, trace=[], attempts=[], branch={})
     n = p1.shape[0]
     idx = np.arange(n) if mask is None else np.flatnonzero(np.asarray(mask).reshape(-1))
     if n == 0 or idx.size == 0:
@@ -468,18 +503,25 @@ def ba_oracle(p1, p2, R, t, Q, th, mask=None, angle_thresh=1.25, t_norm_thresh=0
     mag = (1.0 if quat_old[0] >= 0.0 else -1.0) / mag
     r0 = quat_old * mag
     o = sba_motstr(p1[idx], p2[idx], r0, t0, Q0[idx], th)
-    res.update(info=o["info"], mu=o["mu"], trace=o["trace"])
+    branch = dict(pivot=mat_to_quat_pivot(R0), r0_flipped=bool(quat_old[0] < 0.0), almost_singular=o["almost_singular"])
+    res.update(info=o["info"], mu=o["mu"], trace=o["trace"], attempts=o["attempts"], branch=branch)
     if not o["ok"]:
         return res
     quat_new = quat_mult_fast(local_quat(o["v"]), r0)
+    branch["qn_flipped"] = bool(quat_new[0] < 0.0)
     if quat_new[0] < 0.0:
         quat_new = quat_new * -1.0
     t_new = o["t"].copy()
     t_norm = np.sqrt(t_new[0] * t_new[0] + t_new[1] * t_new[1] + t_new[2] * t_new[2])
     if not (-1e-3 < t_norm < 1e-3) and abs(t_norm - 1.0) > 1e-4:      # nearZero of pose_helper.h:82-87
         t_new = t_new / t_norm
+        branch["t_case"] = "normalised"
+    else:
+        branch["t_case"] = "kept_tiny" if -1e-3 < t_norm < 1e-3 else "kept_unit"
     r_diff, t_diff = rt_quality(quat_old, quat_new, t0, t_new)
     r_diff = r_diff / np.pi * 180.0
+    branch["refused_by"] = tuple(k for k, hit in (("angle", abs(r_diff) > angle_thresh), ("t_norm", t_diff > t_norm_thresh),
+                                                  ("stop", o["info"][6] > 5)) if hit)
     if abs(r_diff) > angle_thresh or t_diff > t_norm_thresh or o["info"][6] > 5:
         return res
     Qn = Q0.copy()

@@ -1,6 +1,7 @@
 """CPU only: pins tests/ba_oracle.py, the float64 restatement of poselib::refineStereoBA that the device is held to.  No build of the
 reference's SBA stands behind it, so it is held to what can be checked without one: its Jacobian against finite differences of its own
-projection, convergence on exact data, the wrapper's rules, and the permutation study that the device tolerances come from."""
+projection, convergence on exact data, the wrapper's rules, the permutation study that the device tolerances come from, and -- scene by
+scene -- that it takes the exit or branch each scene of ba_scenes.BRANCH_SCENES is named for."""
 import numpy as np
 import pytest
 
@@ -123,3 +124,141 @@ def test_tolerances_come_from_the_permutation_study():
     assert sp["stable"], "a scene changes its integers under a permutation: choose another seed"
     for const, key in ((S.TOL_POSE, "pose"), (S.TOL_Q, "q"), (S.TOL_INFO, "info"), (S.TOL_MU, "mu")):
         assert sp[key] > 0 and 10 * sp[key] <= const <= 100 * sp[key], (key, sp[key], const)
+    # the scenes of BRANCH_SCENES: the same rule, each scene on its own study; a spread of exactly 0 asks for a constant of exactly 0
+    for name, row in S.BRANCH_SCENES.items():
+        sp = S.branch_spread(name)
+        assert sp["stable"], (name, "changes its integers under a permutation: choose another seed")
+        for key, const in row["tol"].items():
+            assert np.isfinite(sp[key]) and 10 * sp[key] <= const <= 100 * sp[key], (name, key, sp[key], const)
+        if row["kind"] == "refused":
+            assert row["tol"]["pose"] == 0 and row["tol"]["q"] == 0, name       # the inputs come back byte for byte
+
+
+# sha256 over info, R, t, Q of ba_oracle on SCENES as they were BEFORE the oracle learnt to report its branches (attempts, branch) and to pass
+# over a NaN in ||J^T e||_inf: neither may move a bit of the existing results
+PINNED = {
+    "n7": "7639f689f0a90176aba7cf9376ceef75520a1b70bd2d225886969423969c2182",
+    "n64": "9cabadd646d72111c06c5db5cf38491090d365f7cc43703fc693e868fa3f1020",
+    "n65": "50a4e49d1d26bcfb49f2b7b0df929e7c34d1d7ac035c73fa4216c315b8fd43c6",
+    "n257": "bd2c0b5da89bf4de8eeb0dade50211155d92a7e66788375d51d8931e9f3477fd",
+    "n1000_masked": "d9a3ccb4d5155fc2b3149d9122d32965def56bd4ec2557eaef65df42f97bae0f",
+    "rejected": "a8546d1c1fc94abae7afefbb56b46315c7de3dde5d095179043bd5977af4f869",
+}
+
+
+def test_existing_results_are_pinned_bit_for_bit():
+    import hashlib
+
+    assert set(PINNED) == set(S.SCENES)
+    for name, want in PINNED.items():
+        o = S.oracle_result(name)
+        assert hashlib.sha256(o["info"].tobytes() + o["R"].tobytes() + o["t"].tobytes() + o["Q"].tobytes()).hexdigest() == want, name
+
+
+def test_make_scene_defaults_are_the_old_scenes():
+    """The parameters added to make_scene do nothing at their defaults, spelled out or not."""
+    a = S.make_scene(65, 65, 13, 0.3)
+    b = S.make_scene(65, 65, 13, 0.3, rot_axis=(0.2, 0.9, 0.1), rot_deg=5.0, t_true=None, t_err=0.01, start_rot_deg=None, t_scale=None,
+                     q_rows=None, th=S.TH)
+    for k in ("p1", "p2", "R", "t", "Q"):
+        assert a[k].tobytes() == b[k].tobytes() == S.scene("n65")[k].tobytes(), k
+    o = BAO.ba_oracle(a["p1"], a["p2"], a["R"], a["t"], a["Q"], a["th"])
+    assert o["info"].tobytes() == S.oracle_result("n65")["info"].tobytes()
+
+
+PLANTED = S.PLANTED_ROW
+
+
+def _longest_rejected_run(attempts):
+    """The most consecutive attempts of one outer iteration that did not end accepted."""
+    best = run = 0
+    last = None
+    for itno, _, _, accepted in attempts:
+        if itno != last:
+            run = 0
+        run = 0 if accepted else run + 1
+        last = itno
+        best = max(best, run)
+    return best
+
+
+def test_longest_rejected_run_counts_within_one_iteration():
+    A = [(0, -1, False, False), (0, -1, True, False), (0, -1, False, True), (1, -1, False, False), (2, 3, False, False), (2, -1, False, False),
+         (2, -1, False, False), (2, -1, False, True)]
+    assert _longest_rejected_run(A) == 3 and _longest_rejected_run(A[:4]) == 2 and _longest_rejected_run([]) == 0
+
+
+@pytest.mark.parametrize("name", list(S.BRANCH_SCENES))
+def test_branch_scene_takes_its_branch(name):
+    """Every scene of BRANCH_SCENES runs, in the oracle, through the exit or branch it is named for.  A scene that drifts off fails here, on
+    the CPU, and not silently on the device."""
+    row, s, o = S.BRANCH_SCENES[name], S.scene(name), S.oracle_result(name)
+    ex, br, att = row["expect"], o["branch"], o["attempts"]
+    n_valid = s["p1"].shape[0] if s["mask"] is None else np.count_nonzero(s["mask"])
+    assert (s["mask"] is None) == (not name.endswith("_of_40")) and o["accepted"] == ex["accepted"] == (row["kind"] == "accepted"), name
+    assert not br.get("almost_singular", False)
+    for key, at in (("itno", 5), ("stop", 6)):
+        if key in ex:
+            assert int(o["info"][at]) == ex[key], (name, key, o["info"])
+    if "min_rejected" in ex:
+        assert _longest_rejected_run(att) >= ex["min_rejected"] >= 2, (name, _longest_rejected_run(att))
+    if "min_refused_solves" in ex:
+        assert sum(1 for a in att if a[2]) >= ex["min_refused_solves"] >= 1, name
+    if "first_bad" in ex:
+        bad = [a[1] for a in att]
+        assert len(bad) == 30 and bad[0] == ex["first_bad"] and min(bad) >= 0 and int(o["info"][9]) == 0, (name, bad)   # no attempt got to a solve
+        assert 0 < PLANTED < n_valid - 1
+        if ex["first_bad"] == PLANTED:       # valid points before (they take their new inverse's diagonal) and after (untouched)
+            assert bad.count(PLANTED) >= 2 and set(bad) <= {0, PLANTED}, (name, bad)
+    for key in ("pivot", "r0_flipped", "qn_flipped", "t_case", "refused_by"):
+        if key in ex:
+            assert br[key] == ex[key], (name, key, br)
+    if o["accepted"]:
+        assert br["refused_by"] == () and int(o["info"][6]) in (1, 2, 3, 4, 5)
+        if ex.get("itno") != 0:
+            assert not np.array_equal(o["Q"], s["Q"]), name
+        t_len = np.sqrt(o["t"] @ o["t"])
+        if br["t_case"] == "kept_tiny":
+            assert t_len < 1e-3
+        elif ex.get("t_out_is_unit") is False:
+            assert 1e-9 < abs(t_len - 1) <= 1e-4                      # kept although it is measurably not 1
+        else:
+            assert abs(t_len - 1) < 1e-15
+        assert np.abs(o["R"] @ o["R"].T - np.eye(3)).max() < 1e-14
+    else:
+        assert o["R"].tobytes() == s["R"].tobytes() and o["t"].tobytes() == s["t"].tobytes() and o["Q"].tobytes() == s["Q"].tobytes(), name
+        if int(o["info"][6]) == 7 or n_valid < 12:
+            assert "refused_by" not in br                               # the wrapper never got to its rules
+    if name == "qn_flip_across_180":          # the refined rotation is on the other side of 180 degrees
+        assert (s["R"][1, 0] - s["R"][0, 1]) * (o["R"][1, 0] - o["R"][0, 1]) < 0
+    if name.startswith("stop7_start"):
+        assert not np.isfinite(o["info"][0]) and not np.isfinite(o["info"][1]) and (s["Q"][PLANTED, 2] == 0 or np.isnan(s["Q"][PLANTED]).any())
+    if name.startswith("stop7_midrun"):
+        assert np.isfinite(o["info"][:5]).all() and np.isfinite(s["Q"]).all()
+    if name in ("n11", "n11_of_40"):
+        assert n_valid == 11 and not o["info"].any() and o["mu"] == 0.0
+    if name in ("n12", "n12_of_40"):
+        assert n_valid == 12 and o["info"][5] > 0
+
+
+def test_branch_scenes_cover_every_exit_and_branch():
+    R = {name: S.oracle_result(name) for name in S.BRANCH_SCENES}
+    assert {int(o["info"][6]) for o in R.values()} == {0, 1, 2, 3, 4, 5, 6, 7}                       # 0: the optimiser refused to start
+    ran = [o["branch"] for o in R.values() if "refused_by" in o["branch"]]
+    assert {o["branch"]["pivot"] for o in R.values()} == {-1, 0, 1, 2} and {b["t_case"] for b in ran} == {"kept_unit", "kept_tiny", "normalised"}
+    assert {b["qn_flipped"] for b in ran} == {False, True}
+    assert {(o["branch"]["pivot"] >= 0, o["branch"]["r0_flipped"]) for o in R.values()} >= {(True, True), (True, False), (False, False)}
+    alone = {b["refused_by"] for b in ran} | {S.oracle_result("rejected")["branch"]["refused_by"]}
+    assert alone >= {("angle",), ("t_norm",), ("stop",), ()}                                          # each rule refuses on its own somewhere
+    sizes = {(s["p1"].shape[0] if s["mask"] is None else int(np.count_nonzero(s["mask"]))) for s in map(S.scene, S.BRANCH_SCENES)}
+    assert sizes >= {11, 12, 13, 255, 256, 512, 513} and max(sizes) == 513
+    mid = sorted(int(R[k]["info"][5]) for k in R if k.startswith("stop7_midrun"))
+    assert mid[0] > 0 and len(set(mid)) == 2
+
+
+def test_nan_in_jte_is_passed_over_as_the_reference_does():
+    """sba_levmar.c:943-944: `if(eab_inf < tmp) eab_inf = tmp`, from 0, never takes a NaN.  No scene reaches this with a finite ||e||^2 (a
+    Jacobian entry that is not finite makes the residual of the same point not finite first), so the reduction is pinned on its own."""
+    ea, eb = np.array([1.0, -3.0, 2.0, 0.5, 0.0, 1.0]), np.array([[np.nan, 7.0, -2.0], [1.0, np.nan, -9.0]])
+    assert BAO.jte_inf_norm(ea, eb) == 9.0 and BAO.jte_inf_norm(np.array([np.nan] * 6), eb[:, :1]) == 1.0
+    assert BAO.jte_inf_norm(np.full(6, np.nan), np.full((2, 3), np.nan)) == 0.0 and BAO.jte_inf_norm(ea, np.zeros((2, 3))) == 3.0

@@ -17,9 +17,12 @@
 #include <vector>
 
 #define CV_8U 0
+#define CV_8S 1
 #define CV_32F 5
 #define CV_64F 6
 #define CV_32FC1 CV_32F
+#define CV_8UC1 CV_8U
+#define CV_8SC1 CV_8S
 
 namespace cv {
 
@@ -84,7 +87,7 @@ class Mat {
     }
     int type() const { return type_; }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
-    size_t elemSize() const { return type_ == CV_8U ? 1 : (type_ == CV_32F ? 4 : 8); }
+    size_t elemSize() const { return (type_ == CV_8U || type_ == CV_8S) ? 1 : (type_ == CV_32F ? 4 : 8); }
     bool isContinuous() const { return step == (size_t)cols * elemSize(); }
     template <typename T>
     T &at(int r, int c = 0) { return *reinterpret_cast<T *>(data + (size_t)r * step + (size_t)c * sizeof(T)); }
@@ -106,27 +109,40 @@ class Mat {
 };
 
 // Proxy argument types with the member API of OpenCV's cv::_InputArray / _OutputArray / _InputOutputArray (core/mat.hpp) that the
-// facade uses -- getMat(), empty(), needed(), create(), clear(), type(), rows(), cols(), total() -- so that facade.cpp is written once against
+// facade uses -- getMat(), empty(), needed(), create(), clear(), type(), rows(), cols(), total(), and for a std::vector<cv::Mat> argument
+// isMatVector(), isMat(), getMatVector() -- so that facade.cpp is written once against
 // that API and compiles unchanged against the real classes (MLPL_WITH_OPENCV).  Same class names and the same
 // `typedef const _InputArray& InputArray` shape as OpenCV, so the facade's signatures read exactly like the reference's.
 class _InputArray {
    public:
     _InputArray() = default;
     _InputArray(const Mat &m) : m_(const_cast<Mat *>(&m)) {}  // NOLINT: implicit, as in OpenCV
+    _InputArray(const std::vector<Mat> &v) : v_(const_cast<std::vector<Mat> *>(&v)) {}  // NOLINT
     Mat getMat(int = -1) const { return m_ ? *m_ : Mat(); }
-    bool empty() const { return !m_ || m_->empty(); }
+    bool empty() const { return v_ ? v_->empty() : (!m_ || m_->empty()); }
+    bool isMat() const { return m_ != nullptr; }
+    bool isMatVector() const { return v_ != nullptr; }
+    // headers onto the same data, as OpenCV's getMatVector gives them
+    void getMatVector(std::vector<Mat> &mv) const {
+        if (v_)
+            mv = *v_;
+        else
+            mv.clear();
+    }
     int type(int = -1) const { return m_ ? m_->type() : 0; }
     int rows(int = -1) const { return m_ ? m_->rows : 0; }
     int cols(int = -1) const { return m_ ? m_->cols : 0; }
     size_t total(int = -1) const { return m_ ? (size_t)m_->rows * (size_t)m_->cols : 0; }
 
    protected:
-    Mat *m_ = nullptr;  // null = cv::noArray()
+    Mat *m_ = nullptr;  // null = cv::noArray() (or a vector)
+    std::vector<Mat> *v_ = nullptr;
 };
 class _OutputArray : public _InputArray {
    public:
     _OutputArray() = default;
     _OutputArray(Mat &m) : _InputArray(m) {}  // NOLINT
+    _OutputArray(std::vector<Mat> &v) : _InputArray(v) {}  // NOLINT
     bool needed() const { return m_ != nullptr; }
     void create(int rows, int cols, int type) const {
         if (m_) m_->create(rows, cols, type);
@@ -144,6 +160,7 @@ class _InputOutputArray : public _OutputArray {
    public:
     _InputOutputArray() = default;
     _InputOutputArray(Mat &m) : _OutputArray(m) {}  // NOLINT
+    _InputOutputArray(std::vector<Mat> &v) : _OutputArray(v) {}  // NOLINT
 };
 typedef const _InputArray &InputArray;
 typedef const _OutputArray &OutputArray;

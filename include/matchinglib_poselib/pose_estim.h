@@ -195,6 +195,29 @@ bool refineStereoBA(cv::InputArray p1, cv::InputArray p2, cv::InputOutputArray R
                     const bool optimFocalOnly = false, const bool optimMotionOnly = false, const bool fixCamMat = false,
                     cv::InputOutputArray dist1 = cv::noArray(), cv::InputOutputArray dist2 = cv::noArray());
 
+// poselib::refineMultCamBA (pose_estim.h:249-263, pose_estim.cpp:1384-1735): bundle adjustment of motion and structure over m cameras and
+// one shared structure, the FIRST camera fixed at the pose given, the pseudo-Huber cost.  Built: pointsInImgCoords == false and
+// optimMotionOnly == false -- ps: vector of m Mats, ps[j] the observations of camera j (k_j x 2 CV_64F, CAMERA coordinates) in ascending point
+// order for the non-zero entries of map3D[j]; map3D: vector of m Mats of type CV_8SC1 with n elements each; Rs (3 x 3), ts (3 x 1), Ks
+// (3 x 3): vectors of m CV_64F Mats; Qs: n x 3 CV_64F, n >= 15.  Ks are only read (the Huber threshold in pixels, 0.005 for a negative
+// huber_thresh, is divided by the mean of (K(1,1) + K(2,2)) / 2, the reference's indices); optimFocalOnly and fixCamMat are not read and dists
+// is only size-checked, as in the reference's branch.  At most MLPL_BA_MAX_CAMS = 16 cameras (more: cv::Exception).  Returns true with Qs
+// replaced, every R rewritten from its quaternion (camera 0's too: the round trip of its normalised quaternion) and every t as the optimiser
+// left it (NOT normalised).  Returns false with every t restored and R, Qs untouched when the optimiser fails (fewer measurements than
+// unknowns among the causes) or stops for a reason > 5, or when any camera's rotation moved by more than angleThresh degrees or its
+// normalised translation by more than t_norm_tresh; false with one line on std::cerr, nothing touched, for the reference's input checks in
+// the reference's order (empty inputs, not a vector of Mat, Qs not a Mat, fewer than 15 points, vector sizes, mask sizes, map size / count /
+// type, dists size).
+// masks: the reference compacts ps[j] by masks[j] but keeps requiring map3D[j] to hold as many ones as masks[j] has ELEMENTS
+// (pose_estim.cpp:1456-1470), so with any zero entry its perform_sba reads past the compacted list (:1517-1535, BA_driver.cpp:2136-2157).
+// Absent or all non-zero masks are accepted; masks with a zero are refused.  NOT built, refused with one line on std::cout and false,
+// every argument untouched: pointsInImgCoords == true, optimMotionOnly, a zero in masks.
+bool refineMultCamBA(cv::InputArray ps, cv::InputArray map3D, cv::InputOutputArray Rs, cv::InputOutputArray ts, cv::InputOutputArray Qs,
+                     cv::InputOutputArray Ks, bool pointsInImgCoords = false, cv::InputArray masks = cv::noArray(),
+                     const double angleThresh = 1.25, const double t_norm_tresh = 0.05, const double huber_thresh = -1.0,
+                     const bool optimFocalOnly = false, const bool optimMotionOnly = false, const bool fixCamMat = false,
+                     cv::InputOutputArray dists = cv::noArray());
+
 // Convenience named in BASELINE.json: estimateEssentialMat(..., "RANSAC", ...) followed by getPoseTriangPts, the
 // sequence the reference's README prescribes (README.md:497-521).
 bool estimateRelativePose(cv::InputArray p1, cv::InputArray p2, cv::OutputArray E, cv::OutputArray R, cv::OutputArray t,

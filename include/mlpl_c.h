@@ -132,7 +132,7 @@ int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value);
  * When enabled, the launches of the dominant kernel of each path are bracketed with hipEvents on the stream
  * they run on.  mlpl_profile_read() synchronises those events and returns the summed duration and the
  * launch count since the last reset.  kernel_id: 0 = Hamming partial top-2 (matrix-core or VALU kernel), 1 = knn_l2 (exact or
- * MFMA), 2 = 5-point solver, 3 = Sampson scoring, 4 = recover_pose, 6 = bundle adjustment.  mlpl_profile_enable(ctx, N): 0 = off, 1 = every launch,
+ * MFMA), 2 = 5-point solver, 3 = Sampson scoring, 4 = recover_pose, 6 = bundle adjustment, 7 = multi-camera bundle adjustment.  mlpl_profile_enable(ctx, N): 0 = off, 1 = every launch,
  * N > 1 = every Nth launch (sampling: the two event records cost ~10 us of stream time per bracketed launch). */
 #define MLPL_PROF_KNN_HAMMING 0
 #define MLPL_PROF_KNN_L2 1
@@ -141,7 +141,8 @@ int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value);
 #define MLPL_PROF_RECOVER_POSE 4
 #define MLPL_PROF_COUNT 5         /* the inlier-counting kernel of a RANSAC pass alone (MLPL_PROF_SCORE brackets the whole scoring pass: it, the candidate selection and the candidates' error sums) */
 #define MLPL_PROF_BUNDLE_ADJUST 6 /* the bundle-adjustment kernel (mlpl_refine_stereo_ba*): one launch per call */
-#define MLPL_PROF_NUM 7
+#define MLPL_PROF_BA_MULTICAM 7  /* the multi-camera bundle-adjustment kernel (mlpl_refine_multicam_ba*): one launch per call */
+#define MLPL_PROF_NUM 8
 int mlpl_profile_enable(mlpl_ctx *ctx, int on);
 int mlpl_profile_reset(mlpl_ctx *ctx);
 int mlpl_profile_read(mlpl_ctx *ctx, int kernel_id, double *total_ms, int *launches);
@@ -1071,6 +1072,36 @@ int mlpl_refine_stereo_ba_dev(mlpl_ctx *ctx, const double *d_p1, const double *d
 int mlpl_refine_stereo_ba_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                                     const uint8_t *d_masks, double *d_Q, double *R, double *t, const double *th, double angle_thresh,
                                     double t_norm_thresh, int32_t *accepted, double *info, void *stream);
+
+/* Bundle adjustment of m cameras over one shared structure: poselib::refineMultCamBA with pointsInImgCoords == false and optimMotionOnly ==
+ * false (P/source/pose_estim.cpp:1384-1735) -- motion and structure, calibrated cameras, the FIRST camera fixed at the pose given, a
+ * visibility map per camera, the pseudo-Huber cost; SBAdriver::perform_sba (nconstframes = 1) around sba_motstr_levmar_x (mcon = 1) restated
+ * in float64 (tests/ba_multicam_oracle.py is the restatement; mlpl_refine_stereo_ba is its two-camera, full-visibility special case).  The
+ * layout is DENSE, not the reference's compacted lists (the C++ drop-in expands them): p: m x n x 2 in CAMERA coordinates, read where vis is
+ * nonzero; vis: m x n bytes; R: m x 9, t: m x 3, in / out; Q: n x 3, in / out; th: the Huber threshold in CAMERA units, ALREADY converted
+ * (th_px / mean_j((K_j(1,1) + K_j(2,2)) / 2), the reference's indices; the C++ drop-in converts); info: NULL or the optimiser's info[0..9]
+ * (all zero when the optimiser refuses the problem: fewer measurements than unknowns, 2 nvis < 6 m + 3 n, or its "almost singular" return).
+ * 2 <= m <= MLPL_BA_MAX_CAMS; a larger m returns MLPL_E_UNSUPPORTED, m < 2 MLPL_E_BAD_INPUT, and nothing is written.  Returns 1 = accepted:
+ * Q replaced whole (a point no camera sees keeps its coordinates), every R_j -- camera 0 included -- rewritten as quatToMatrix of its
+ * normalised, sign-fixed quaternion, every t_j as the optimiser left it (NOT normalised); 0 = rejected (any camera's |rotation change| >
+ * angle_thresh degrees or translation change, both translations normalised, > t_norm_thresh; stop reason > 5) or failed: R, t and Q
+ * untouched; negative: an MLPL_E_* error.  vis is never written.  One launch: the whole Levenberg-Marquardt iteration runs in one workgroup. */
+#define MLPL_BA_MAX_CAMS 16
+int mlpl_refine_multicam_ba(mlpl_ctx *ctx, const double *p, const uint8_t *vis, int m, int n, double *R, double *t, double *Q, double th,
+                            double angle_thresh, double t_norm_thresh, double info[10]);
+/* The same on device-resident d_p (m x n x 2), d_vis (m x n bytes), d_Q (n x 3, in / out); the poses stay on the host; only they and info are
+ * read back. */
+int mlpl_refine_multicam_ba_dev(mlpl_ctx *ctx, const double *d_p, const uint8_t *d_vis, int m, int n, double *R, double *t, double *d_Q,
+                                double th, double angle_thresh, double t_norm_thresh, double info[10], void *stream);
+/* A batch: problem b has n_cams[b] <= cams_stride cameras and counts[b] <= stride points; d_p [n_problems][cams_stride][stride][2], d_vis
+ * [n_problems][cams_stride][stride], d_Q [n_problems][stride][3] (in / out), host R [n_problems][cams_stride][9], t
+ * [n_problems][cams_stride][3] (in / out), th[b], accepted[b] (1 / 0 as above), info + 10 b (or NULL).  Points beyond counts[b], cameras
+ * beyond n_cams[b] and the visibility bytes are never written.  counts[b] == 0 or n_cams[b] < 2: not accepted, info zero, nothing touched;
+ * an n_cams[b] > MLPL_BA_MAX_CAMS fails the call with MLPL_E_UNSUPPORTED before anything runs.  One launch, one workgroup per problem; every
+ * problem's result is bit-identical to mlpl_refine_multicam_ba's.  Returns 0 or a negative error. */
+int mlpl_refine_multicam_ba_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p, const uint8_t *d_vis, int cams_stride, int stride,
+                                      const int32_t *n_cams, const int32_t *counts, double *d_Q, double *R, double *t, const double *th,
+                                      double angle_thresh, double t_norm_thresh, int32_t *accepted, double *info, void *stream);
 
 
 /* The diagnostics entry points (mlpl_debug_*: traces, clock stamps, solver statistics, self-tests -- exported by the same library, used by

@@ -135,6 +135,8 @@ int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int
 /* Tests: the damping term mu at exit of every problem of the calling thread's last mlpl_refine_stereo_ba* call (0 for a problem the optimiser
  * refused).  Writes min(problems, max_items) doubles and returns that number. */
 int mlpl_debug_ba_last_mu(double *mu, int max_items);
+/* The same for the calling thread's last mlpl_refine_multicam_ba* call. */
+int mlpl_debug_ba_multicam_last_mu(double *mu, int max_items);
 
 #ifdef __cplusplus
 }

@@ -242,6 +242,13 @@ _SIGNATURES = {
     "mlpl_refine_stereo_ba_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "mlpl_debug_ba_last_mu": (c_int, [c_void_p, c_int]),
+    "mlpl_refine_multicam_ba": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
+                                        c_void_p]),
+    "mlpl_refine_multicam_ba_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                            c_double, c_void_p, c_void_p]),
+    "mlpl_refine_multicam_ba_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "mlpl_debug_ba_multicam_last_mu": (c_int, [c_void_p, c_int]),
 }
 
 

@@ -68,6 +68,8 @@ enum WsSlot {
     WS_SUBPIX_SEP,      // cornerSubPix refinement (subpix_separate.hip): per-match records and positions, per-keypoint winners, per-list results and tickets
     WS_SUBPIX_SEP_MASK, // ... its eight mask profiles (uploaded when the context is created)
     WS_BA,              // bundle adjustment (bundle_adjust.hip): per-point state of every problem, then the compacted row lists
+    WS_BA_MULTICAM,     // multi-camera bundle adjustment (bundle_adjust_multicam.hip): per-point state of every problem
+    WS_BA_MULTICAM_IO,  // ... its per-problem input and result blocks
     WS_HOMOG,           // homography ARRSAC (homography_impl.h): packed correspondences, the models of every sample solved in a call, the compacted inliers
     WS_HOMOG_PLANES,    // estimateMultHomographys: the two point buffers the rounds alternate between, the round's mask, the planes' masks
     WS_HOMOG_ALIGN,     // homography alignment (homography_align_impl.h): the result block and the correspondences sorted by plane

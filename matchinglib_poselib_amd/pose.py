@@ -1053,6 +1053,101 @@ def refine_stereo_ba_batch(d_p1, d_p2, counts, R, t, d_Q, th, d_masks=None, angl
     return dict(accepted=acc.astype(bool), R=Rh.reshape(B, 3, 3), t=tv, info=info, mu=_ba_last_mu(ctx, B))
 
 
+def ba_threshold_multicam(Ks, huber_thresh: float = -1.0) -> float:
+    """The Huber threshold in camera units as poselib::refineMultCamBA converts it (pose_estim.cpp:1510-1514, :1566-1571): the threshold in
+    pixels over the mean of (K(1,1) + K(2,2)) / 2 -- fy and the 1.0 --, as the reference indexes."""
+    th = huber_thresh if huber_thresh >= 0 else ROBUST_THRESH
+    f_mean = 0.0
+    for K in Ks:
+        K = np.asarray(K, np.float64)
+        f_mean += (K[1, 1] + K[2, 2]) / 2.0
+    f_mean /= float(len(Ks))
+    return float(th / f_mean)
+
+
+def _ba_multicam_last_mu(ctx, n):
+    mu = np.zeros(n)
+    got = ctx.lib.mlpl_debug_ba_multicam_last_mu(mu.ctypes.data, n)
+    return mu if got == n else None
+
+
+def refine_multicam_ba(p, vis, R, t, Q, th: float, angle_thresh: float = 1.25, t_norm_thresh: float = 0.05,
+                       ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_multicam_ba: bundle adjustment of m cameras over one shared structure (motion and structure, the first camera fixed at the
+    pose given, pseudo-Huber cost).  p [m, n, 2] in camera coordinates (read where vis is nonzero), vis [m, n], R [m, 3, 3], t [m, 3],
+    Q [n, 3]; th in CAMERA units (ba_threshold_multicam).  -> dict(accepted, R [m, 3, 3], t [m, 3], Q [n, 3], info [10], mu); a rejected or
+    failed run returns R, t and Q as they came; an accepted one returns every t as the optimiser left it (not normalised)."""
+    ctx = ctx or default_context()
+    vh = np.ascontiguousarray(vis, np.uint8)
+    if vh.ndim != 2:
+        raise ValueError("vis must be [m, n]")
+    m, n = vh.shape
+    ph = np.ascontiguousarray(np.asarray(p, np.float64).reshape(m, n, 2))
+    Rh = np.ascontiguousarray(np.array(R, np.float64).reshape(m, 9)).copy()
+    tv = np.ascontiguousarray(np.array(t, np.float64).reshape(m, 3)).copy()
+    Qh = np.ascontiguousarray(np.array(Q, np.float64).reshape(-1, 3)).copy()
+    if Qh.shape[0] != n:
+        raise ValueError("vis and Q differ in the number of points")
+    info = np.zeros(10)
+    rc = ctx.lib.mlpl_refine_multicam_ba(ctx.handle, ph.ctypes.data, vh.ctypes.data, m, n, Rh.ctypes.data, tv.ctypes.data, Qh.ctypes.data,
+                                         float(th), float(angle_thresh), float(t_norm_thresh), info.ctypes.data)
+    if rc < 0:
+        raise MlplError(rc, "mlpl_refine_multicam_ba", _lib.last_error())
+    mu = _ba_multicam_last_mu(ctx, 1) if n > 0 else None
+    return dict(accepted=bool(rc), R=Rh.reshape(m, 3, 3), t=tv, Q=Qh, info=info, mu=0.0 if mu is None else float(mu[0]))
+
+
+def refine_multicam_ba_device(d_p, d_vis, R, t, d_Q, th: float, angle_thresh: float = 1.25, t_norm_thresh: float = 0.05,
+                              ctx: Optional[Context] = None, stream: Optional[int] = None) -> dict:
+    """mlpl_refine_multicam_ba_dev on device-resident torch tensors (d_p float64 [m, n, 2], d_vis uint8 [m, n], d_Q float64 [n, 3] refined in
+    place when accepted) -> dict(accepted, R, t, info, mu).  Only the poses and info are read back."""
+    import torch
+
+    m, n = d_vis.shape
+    assert d_p.is_cuda and d_p.dtype == torch.float64 and d_p.shape == (m, n, 2) and d_p.is_contiguous()
+    assert d_vis.is_cuda and d_vis.dtype == torch.uint8 and d_vis.is_contiguous()
+    assert d_Q.is_cuda and d_Q.dtype == torch.float64 and d_Q.shape == (n, 3) and d_Q.is_contiguous()
+    ctx = ctx or default_context(d_p.device.index or 0)
+    Rh = np.ascontiguousarray(np.array(R, np.float64).reshape(m, 9)).copy()
+    tv = np.ascontiguousarray(np.array(t, np.float64).reshape(m, 3)).copy()
+    info = np.zeros(10)
+    st = torch.cuda.current_stream(d_p.device).cuda_stream if stream is None else stream
+    rc = ctx.lib.mlpl_refine_multicam_ba_dev(ctx.handle, d_p.data_ptr(), d_vis.data_ptr(), m, n, Rh.ctypes.data, tv.ctypes.data, d_Q.data_ptr(),
+                                             float(th), float(angle_thresh), float(t_norm_thresh), info.ctypes.data, st)
+    if rc < 0:
+        raise MlplError(rc, "mlpl_refine_multicam_ba_dev", _lib.last_error())
+    mu = _ba_multicam_last_mu(ctx, 1) if n > 0 else None
+    return dict(accepted=bool(rc), R=Rh.reshape(m, 3, 3), t=tv, info=info, mu=0.0 if mu is None else float(mu[0]))
+
+
+def refine_multicam_ba_batch(d_p, d_vis, n_cams, counts, R, t, d_Q, th, angle_thresh: float = 1.25, t_norm_thresh: float = 0.05,
+                             ctx: Optional[Context] = None) -> dict:
+    """mlpl_refine_multicam_ba_batch_dev: d_p float64 [B, cams_stride, stride, 2], d_vis uint8 [B, cams_stride, stride], d_Q float64
+    [B, stride, 3] (refined in place for the accepted problems; rows beyond counts[b] untouched), n_cams [B], counts [B], R
+    [B, cams_stride, 3, 3], t [B, cams_stride, 3] (host), th a scalar or [B].  One launch.
+    -> dict(accepted [B], R [B, cams_stride, 3, 3], t [B, cams_stride, 3], info [B, 10], mu [B])."""
+    import torch
+
+    B, cams_stride, stride = d_vis.shape
+    assert d_p.is_cuda and d_p.dtype == torch.float64 and d_p.shape == (B, cams_stride, stride, 2) and d_p.is_contiguous()
+    assert d_vis.is_cuda and d_vis.dtype == torch.uint8 and d_vis.is_contiguous()
+    assert d_Q.is_cuda and d_Q.dtype == torch.float64 and d_Q.shape == (B, stride, 3) and d_Q.is_contiguous()
+    ctx = ctx or default_context(d_p.device.index or 0)
+    nc = np.ascontiguousarray(n_cams, np.int32).reshape(B)
+    cn = np.ascontiguousarray(counts, np.int32).reshape(B)
+    Rh = np.ascontiguousarray(np.array(R, np.float64).reshape(B, cams_stride, 9)).copy()
+    tv = np.ascontiguousarray(np.array(t, np.float64).reshape(B, cams_stride, 3)).copy()
+    thv = np.ascontiguousarray(np.broadcast_to(np.asarray(th, np.float64), (B,))).copy()
+    acc, info = np.zeros(B, np.int32), np.zeros((B, 10))
+    rc = ctx.lib.mlpl_refine_multicam_ba_batch_dev(ctx.handle, B, d_p.data_ptr(), d_vis.data_ptr(), cams_stride, stride, nc.ctypes.data,
+                                                   cn.ctypes.data, d_Q.data_ptr(), Rh.ctypes.data, tv.ctypes.data, thv.ctypes.data,
+                                                   float(angle_thresh), float(t_norm_thresh), acc.ctypes.data, info.ctypes.data,
+                                                   torch.cuda.current_stream(d_p.device).cuda_stream)
+    if rc != 0:
+        raise MlplError(rc, "mlpl_refine_multicam_ba_batch_dev", _lib.last_error())
+    return dict(accepted=acc.astype(bool), R=Rh.reshape(B, cams_stride, 3, 3), t=tv, info=info, mu=_ba_multicam_last_mu(ctx, B))
+
+
 def ImgToCamCoordTrans(points, K, ctx: Optional[Context] = None) -> np.ndarray:
     """poselib::ImgToCamCoordTrans (pose_helper.cpp:1100-1109): float32 n x 2 pixel points -> camera coordinates."""
     ctx = ctx or default_context()

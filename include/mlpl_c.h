@@ -127,6 +127,12 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx);
 int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value);
 /* The current value of a tuning knob: every name mlpl_set_option takes.  Returns 0, MLPL_E_BAD_INPUT for a name it does not know. */
 int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value);
+/* The option table without a context (and without a device): the name and the default of option `index`, 0 <= index < the number of
+ * options, in the table's order.  Returns 0, MLPL_E_BAD_INPUT past either end or for a NULL output; walk it from 0 until it refuses. */
+int mlpl_option_info(int index, const char **name, int *default_value);
+/* 1 if mlpl_set_option would take `value` for `name`, 0 if it would refuse it (the same check); MLPL_E_BAD_INPUT for an unknown or
+ * NULL name. */
+int mlpl_option_accepts(const char *name, int value);
 
 /* ---- in-library kernel timing (for roofline accounting) ------------------------------------------------------
  * When enabled, the launches of the dominant kernel of each path are bracketed with hipEvents on the stream

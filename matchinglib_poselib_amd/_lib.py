@@ -50,6 +50,8 @@ _SIGNATURES = {
     "mlpl_ctx_synchronize": (c_int, [c_void_p]),
     "mlpl_set_option": (c_int, [c_void_p, C.c_char_p, c_int]),
     "mlpl_get_option": (c_int, [c_void_p, C.c_char_p, C.POINTER(c_int)]),
+    "mlpl_option_info": (c_int, [c_int, C.POINTER(C.c_char_p), C.POINTER(c_int)]),
+    "mlpl_option_accepts": (c_int, [C.c_char_p, c_int]),
     "mlpl_profile_enable": (c_int, [c_void_p, c_int]),
     "mlpl_profile_reset": (c_int, [c_void_p]),
     "mlpl_profile_read": (c_int, [c_void_p, c_int, C.POINTER(c_double), C.POINTER(c_int)]),

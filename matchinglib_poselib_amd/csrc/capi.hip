@@ -94,6 +94,87 @@ void prof_mark(mlpl_ctx *ctx, int id, int phase, hipStream_t s) {
 
 using namespace mlpl;
 
+// The tuning options: one row per opt_* field of mlpl_ctx, and nothing else to keep in step.  mlpl_ctx_create sets the defaults from
+// it, mlpl_set_option / mlpl_get_option / mlpl_option_info / mlpl_option_accepts look a name up in it, tests/option_guard.py takes its
+// names from it.  A value is accepted if lo <= value <= hi and `ok`, where a row has one, holds (the value sets that are no range).
+namespace {
+
+struct Option {
+    const char *name;
+    int mlpl_ctx::*field;
+    int def, lo, hi;
+    bool (*ok)(int) = nullptr;
+};
+const int kAnyCount = 0x7fffffff;   // hi of an option that takes every non-negative int
+const Option kOptions[] = {
+    {"l2_fold_counts", &mlpl_ctx::opt_l2_fold_counts, 1, 0, 1},
+    {"hamming_expand_inkernel", &mlpl_ctx::opt_hamming_expand_inkernel, 1, 0, 1},   // measured (tools/hamming_opt_ab.py, profiles/README.md): the step loses the expansion pass, the ring kernel gains less
+    {"hamming_block_top2", &mlpl_ctx::opt_hamming_block_top2, 4, 0, 4, [](int v) { return v % 4 == 0; }},   // 0 or 4.  Measured (tools/hamming_opt_ab.py, profiles/README.md): the step of 64 C2 pairs loses 15-27 us of 366-380
+    {"hamming_mfma_shape", &mlpl_ctx::opt_hamming_mfma_shape, 16, 16, 32, [](int v) { return v % 16 == 0; }},   // 16 or 32 (16 = the 16x16x128 form of the throughput instance: DESIGN 4.1 for the measurement behind the default)
+    {"vfc_store_u", &mlpl_ctx::opt_vfc_store_u, 0, 0, 1},   // not measured yet (tools/vfc_timing.py measures both settings)
+    {"hamming_variant", &mlpl_ctx::opt_hamming_variant, 3, 0, 3},
+    {"hamming_mfma_qt", &mlpl_ctx::opt_hamming_mfma_qt, 0, 0, 4, [](int v) { return v != 3; }},
+    {"hamming_mfma_blocks_per_cu", &mlpl_ctx::opt_hamming_mfma_blocks_per_cu, 3, 1, 64},
+    {"hamming_mfma_lds", &mlpl_ctx::opt_hamming_mfma_lds, 1, 0, 2},
+    {"hamming_expand_fine", &mlpl_ctx::opt_hamming_expand_fine, 1, 0, 1},
+    {"hamming_mfma_prio", &mlpl_ctx::opt_hamming_mfma_prio, 0, 0, 3, [](int v) { return v != 2; }},
+    {"hamming_mfma_prefetch", &mlpl_ctx::opt_hamming_mfma_prefetch, 0, 0, 6, [](int v) { return v % 2 == 0; }},
+    {"hamming_split_rows", &mlpl_ctx::opt_hamming_split_rows, 0, 0, 8192, [](int v) { return v % 4096 == 0; }},
+    {"hamming_mfma_waves", &mlpl_ctx::opt_hamming_mfma_waves, 0, 0, 16, [](int v) { return v % 4 == 0 && v != 12; }},
+    {"hamming_mfma_weighted", &mlpl_ctx::opt_hamming_mfma_weighted, 1, 0, 1},
+    {"hamming_fused_merge", &mlpl_ctx::opt_hamming_fused_merge, 1, 0, 1},
+    {"hamming_stamps", &mlpl_ctx::opt_hamming_stamps, 0, 0, 2},
+    {"hamming_train01", &mlpl_ctx::opt_hamming_train01, 0, 0, 1},
+    {"hamming_merge_emit", &mlpl_ctx::opt_hamming_merge_emit, 0, 0, 1},   // measured (tools/single_pair_probe.py): the launch it saves is what the chained look-back costs -- 21.2-22.2 against 20.8-21.4 us
+    {"l2_mfma_waves", &mlpl_ctx::opt_l2_mfma_waves, 0, 0, 8, [](int v) { return v % 4 == 0; }},
+    {"l2_mfma_blocks_per_cu", &mlpl_ctx::opt_l2_mfma_blocks_per_cu, 0, 0, 16},
+    {"hamming_qpl", &mlpl_ctx::opt_hamming_qpl, 1, 1, 2},
+    {"hamming_blocks_per_cu", &mlpl_ctx::opt_hamming_blocks_per_cu, 32, 1, 64},
+    {"ransac_lazy_sums", &mlpl_ctx::opt_ransac_lazy_sums, 1, 0, 1},
+    {"ransac_overlap", &mlpl_ctx::opt_ransac_overlap, 1, 0, 1},
+    {"ransac_dev_split", &mlpl_ctx::opt_ransac_dev_split, 0, 0, 900},
+    {"rand_cache_max", &mlpl_ctx::opt_rand_cache_max, 0, 0, kAnyCount},
+    {"ransac_f32_filter", &mlpl_ctx::opt_ransac_f32_filter, 1, 0, 1},
+    {"arrsac_refine_warm_start", &mlpl_ctx::opt_arrsac_refine_warm_start, 1, 0, 1},
+    {"ransac_count_mpl", &mlpl_ctx::opt_ransac_count_mpl, 2, 1, 2},
+    {"ransac_count_tiles", &mlpl_ctx::opt_ransac_count_tiles, 2, 1, 2},
+    {"ransac_count_threads", &mlpl_ctx::opt_ransac_count_threads, 256, 256, 512, [](int v) { return v % 256 == 0; }},   // round 6: 4-wave workgroups at 96 VGPRs, five per CU (C5 counting -6-8 %, C3 equal)
+    {"ransac_count_wpe", &mlpl_ctx::opt_ransac_count_wpe, 5, 5, 6},
+    {"ransac_count_defer", &mlpl_ctx::opt_ransac_count_defer, 1, 0, 1},
+    {"ransac_event_cap", &mlpl_ctx::opt_ransac_event_cap, 0, 0, 1024},
+    {"solver_polish", &mlpl_ctx::opt_solver_polish, 1, 0, 1},   // the solver's accuracy safeguard stays on: measured CLOSER to the CPU path than the plain root path (tools/polish_default_ab.py)
+    {"solver_wave3", &mlpl_ctx::opt_solver_wave3, 1, 0, 1},
+    {"ransac_device_draw", &mlpl_ctx::opt_ransac_device_draw, 1, 0, 1},
+    {"l2_float_mfma", &mlpl_ctx::opt_l2_float_mfma, 1, 0, 2},
+    {"arrsac_flag_points", &mlpl_ctx::opt_arrsac_flag_points, 0, 0, 1024, [](int v) { return v == 0 || (v >= 128 && v % 64 == 0); }},
+    {"pair_batch", &mlpl_ctx::opt_pair_batch, 0, 0, 1024},
+    {"hub_lanes", &mlpl_ctx::opt_hub_lanes, 0, 0, 8},
+    {"eig_inverse_iteration", &mlpl_ctx::opt_eig_inverse_iteration, 1, 0, 1},
+    {"hub_blocking_sync", &mlpl_ctx::opt_hub_blocking_sync, 1, 0, 1},
+    {"hub_workers", &mlpl_ctx::opt_hub_workers, 0, 0, 64},
+    {"hub_cohort", &mlpl_ctx::opt_hub_cohort, 0, 0, 512, [](int v) { return v == 0 || v >= 8; }},
+    {"pair_batch_seq", &mlpl_ctx::opt_pair_batch_seq, 0, 0, 1024},
+    {"pair_batch_feed", &mlpl_ctx::opt_pair_batch_feed, 1, 0, 1},
+    {"pair_batch_raw_cap", &mlpl_ctx::opt_pair_batch_raw_cap, 0, 0, 1 << 22, [](int v) { return v == 0 || v >= 64; }},
+    {"usac_lo_stepwise", &mlpl_ctx::opt_usac_lo_stepwise, 0, 0, 1},
+    {"usac_lo_warm_start", &mlpl_ctx::opt_usac_lo_warm_start, 1, 0, 1},
+    {"usac_first_batch", &mlpl_ctx::opt_usac_first_batch, 0, 0, 128},
+    {"usac_lo5_fused_fit", &mlpl_ctx::opt_usac_lo5_fused_fit, 1, 0, 1},
+    {"usac_sprt_fast", &mlpl_ctx::opt_usac_sprt_fast, 1, 0, 1},
+    {"ransac_host_table", &mlpl_ctx::opt_ransac_host_table, 0, 0, 1},
+    {"ransac_chunk", &mlpl_ctx::opt_ransac_chunk, 0, 0, 32768},
+};
+
+const Option *find_option(const char *name) {
+    for (const Option &o : kOptions)
+        if (!std::strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
+bool option_accepts(const Option &o, int value) { return value >= o.lo && value <= o.hi && (!o.ok || o.ok(value)); }
+
+}  // namespace
+
 extern "C" {
 
 const char *mlpl_last_error(void) { return g_err; }
@@ -129,41 +210,7 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
     std::memset(ctx, 0, sizeof(*ctx));
     ctx->device = device_ordinal;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    ctx->opt_hamming_variant = 3;
-    ctx->opt_hamming_qpl = 1;
-    ctx->opt_hamming_blocks_per_cu = 32;
-    ctx->opt_hamming_mfma_blocks_per_cu = 3;
-    ctx->opt_hamming_mfma_qt = 0;
-    ctx->opt_hamming_mfma_lds = 1;
-    ctx->opt_hamming_mfma_weighted = 1;
-    ctx->opt_hamming_mfma_prio = 0;
-    ctx->opt_hamming_fused_merge = 1;
-    ctx->opt_hamming_expand_fine = 1;
-    ctx->opt_hamming_expand_inkernel = 1;  // measured (tools/hamming_opt_ab.py, profiles/README.md): the step loses the expansion pass, the ring kernel gains less
-    ctx->opt_hamming_block_top2 = 4;   // measured (tools/hamming_opt_ab.py, profiles/README.md): the step of 64 C2 pairs loses 15-27 us of 366-380
-    ctx->opt_hamming_mfma_shape = 16;   // (16 = the 16x16x128 form of the throughput instance: DESIGN 4.1 for the measurement behind the default)
-    ctx->opt_hamming_merge_emit = 0;  // measured (tools/single_pair_probe.py): the launch it saves is what the chained look-back costs -- 21.2-22.2 against 20.8-21.4 us
-    ctx->opt_ransac_lazy_sums = 1;
-    ctx->opt_ransac_overlap = 1;
-    ctx->opt_ransac_f32_filter = 1;
-    ctx->opt_ransac_count_mpl = 2;
-    ctx->opt_ransac_count_tiles = 2;
-    ctx->opt_ransac_count_wpe = 5;
-    ctx->opt_ransac_count_threads = 256;   // round 6: 4-wave workgroups at 96 VGPRs, five per CU (C5 counting -6-8 %, C3 equal)
-    ctx->opt_ransac_count_defer = 1;
-    ctx->opt_pair_batch_feed = 1;
-    ctx->opt_solver_polish = 1;   // the solver's accuracy safeguard stays on: measured CLOSER to the CPU path than the plain root path (tools/polish_default_ab.py)
-    ctx->opt_solver_wave3 = 1;
-    ctx->opt_ransac_device_draw = 1;
-    ctx->opt_usac_lo_warm_start = 1;
-    ctx->opt_usac_lo5_fused_fit = 1;
-    ctx->opt_hub_blocking_sync = 1;
-    ctx->opt_eig_inverse_iteration = 1;
-    ctx->opt_arrsac_refine_warm_start = 1;
-    ctx->opt_usac_sprt_fast = 1;
-    ctx->opt_l2_float_mfma = 1;
-    ctx->opt_l2_fold_counts = 1;
-    ctx->opt_vfc_store_u = 0;   // not measured yet (tools/vfc_timing.py measures both settings)
+    for (const Option &o : kOptions) ctx->*(o.field) = o.def;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -221,155 +268,39 @@ int mlpl_ctx_synchronize(mlpl_ctx *ctx) {
     return MLPL_OK;
 }
 
-// Knobs kept in a table: one row serves mlpl_set_option and mlpl_get_option (name, field, accepted range).  The chains below are the
-// older knobs, whose value sets are not all ranges; tests/option_guard.py mirrors exactly those.
-static const struct {
-    const char *name;
-    int mlpl_ctx::*field;
-    int lo, hi;
-} kRangeOptions[] = {
-    {"l2_fold_counts", &mlpl_ctx::opt_l2_fold_counts, 0, 1},
-    {"hamming_expand_inkernel", &mlpl_ctx::opt_hamming_expand_inkernel, 0, 1},
-    {"hamming_block_top2", &mlpl_ctx::opt_hamming_block_top2, 0, 4},   // (0 or 4: checked below)
-    {"hamming_mfma_shape", &mlpl_ctx::opt_hamming_mfma_shape, 16, 32},   // (16 or 32: checked below)
-    {"vfc_store_u", &mlpl_ctx::opt_vfc_store_u, 0, 1},
-};
-
 int mlpl_set_option(mlpl_ctx *ctx, const char *name, int value) {
     if (!ctx || !name) return MLPL_E_BAD_INPUT;
-    for (const auto &o : kRangeOptions)
-        if (!std::strcmp(name, o.name)) {
-            const bool bad_block = o.field == &mlpl_ctx::opt_hamming_block_top2 && value != 0 && value != 4;
-            const bool bad_shape = o.field == &mlpl_ctx::opt_hamming_mfma_shape && value != 16 && value != 32;
-            if (value < o.lo || value > o.hi || bad_block || bad_shape) {
-                set_error("mlpl_set_option: unknown option or bad value: %s=%d", name, value);
-                return MLPL_E_BAD_INPUT;
-            }
-            ctx->*(o.field) = value;
-            return MLPL_OK;
-        }
-    if (!std::strcmp(name, "hamming_variant") && value >= 0 && value <= 3) ctx->opt_hamming_variant = value;
-    else if (!std::strcmp(name, "hamming_mfma_qt") && (value == 0 || value == 1 || value == 2 || value == 4)) ctx->opt_hamming_mfma_qt = value;
-    else if (!std::strcmp(name, "hamming_mfma_blocks_per_cu") && value >= 1 && value <= 64) ctx->opt_hamming_mfma_blocks_per_cu = value;
-    else if (!std::strcmp(name, "hamming_mfma_lds") && (value >= 0 && value <= 2)) ctx->opt_hamming_mfma_lds = value;
-    else if (!std::strcmp(name, "hamming_expand_fine") && (value == 0 || value == 1)) ctx->opt_hamming_expand_fine = value;
-    else if (!std::strcmp(name, "hamming_mfma_prio") && (value == 0 || value == 1 || value == 3)) ctx->opt_hamming_mfma_prio = value;
-    else if (!std::strcmp(name, "hamming_mfma_prefetch") && (value == 0 || value == 2 || value == 4 || value == 6)) ctx->opt_hamming_mfma_prefetch = value;
-    else if (!std::strcmp(name, "hamming_split_rows") && (value == 0 || value == 4096 || value == 8192)) ctx->opt_hamming_split_rows = value;
-    else if (!std::strcmp(name, "hamming_mfma_waves") && (value == 0 || value == 4 || value == 8 || value == 16)) ctx->opt_hamming_mfma_waves = value;
-    else if (!std::strcmp(name, "hamming_mfma_weighted") && (value == 0 || value == 1)) ctx->opt_hamming_mfma_weighted = value;
-    else if (!std::strcmp(name, "hamming_fused_merge") && (value == 0 || value == 1)) ctx->opt_hamming_fused_merge = value;
-    else if (!std::strcmp(name, "hamming_stamps") && (value >= 0 && value <= 2)) ctx->opt_hamming_stamps = value;
-    else if (!std::strcmp(name, "hamming_train01") && (value == 0 || value == 1)) ctx->opt_hamming_train01 = value;
-    else if (!std::strcmp(name, "hamming_merge_emit") && (value == 0 || value == 1)) ctx->opt_hamming_merge_emit = value;
-    else if (!std::strcmp(name, "l2_mfma_waves") && (value == 0 || value == 4 || value == 8)) ctx->opt_l2_mfma_waves = value;
-    else if (!std::strcmp(name, "l2_mfma_blocks_per_cu") && value >= 0 && value <= 16) ctx->opt_l2_mfma_blocks_per_cu = value;
-    else if (!std::strcmp(name, "hamming_qpl") && (value == 1 || value == 2)) ctx->opt_hamming_qpl = value;
-    else if (!std::strcmp(name, "hamming_blocks_per_cu") && value >= 1 && value <= 64) ctx->opt_hamming_blocks_per_cu = value;
-    else if (!std::strcmp(name, "ransac_lazy_sums") && (value == 0 || value == 1)) ctx->opt_ransac_lazy_sums = value;
-    else if (!std::strcmp(name, "ransac_overlap") && (value == 0 || value == 1)) ctx->opt_ransac_overlap = value;
-    else if (!std::strcmp(name, "ransac_dev_split") && value >= 0 && value <= 900) ctx->opt_ransac_dev_split = value;
-    else if (!std::strcmp(name, "rand_cache_max") && value >= 0) ctx->opt_rand_cache_max = value;
-    else if (!std::strcmp(name, "ransac_f32_filter") && (value == 0 || value == 1)) ctx->opt_ransac_f32_filter = value;
-    else if (!std::strcmp(name, "arrsac_refine_warm_start") && (value == 0 || value == 1)) ctx->opt_arrsac_refine_warm_start = value;
-    else if (!std::strcmp(name, "ransac_count_mpl") && (value == 1 || value == 2)) ctx->opt_ransac_count_mpl = value;
-    else if (!std::strcmp(name, "ransac_count_tiles") && (value == 1 || value == 2)) ctx->opt_ransac_count_tiles = value;
-    else if (!std::strcmp(name, "ransac_count_threads") && (value == 256 || value == 512)) ctx->opt_ransac_count_threads = value;
-    else if (!std::strcmp(name, "ransac_count_wpe") && (value == 5 || value == 6)) ctx->opt_ransac_count_wpe = value;
-    else if (!std::strcmp(name, "ransac_count_defer") && (value == 0 || value == 1)) ctx->opt_ransac_count_defer = value;
-    else if (!std::strcmp(name, "ransac_event_cap") && value >= 0 && value <= 1024) ctx->opt_ransac_event_cap = value;
-    else if (!std::strcmp(name, "solver_polish") && (value == 0 || value == 1)) ctx->opt_solver_polish = value;
-    else if (!std::strcmp(name, "solver_wave3") && (value == 0 || value == 1)) ctx->opt_solver_wave3 = value;
-    else if (!std::strcmp(name, "ransac_device_draw") && (value == 0 || value == 1)) ctx->opt_ransac_device_draw = value;
-    else if (!std::strcmp(name, "l2_float_mfma") && value >= 0 && value <= 2) ctx->opt_l2_float_mfma = value;
-    else if (!std::strcmp(name, "arrsac_flag_points") && (value == 0 || (value >= 128 && value <= 1024 && value % 64 == 0))) ctx->opt_arrsac_flag_points = value;
-    else if (!std::strcmp(name, "pair_batch") && value >= 0 && value <= 1024) ctx->opt_pair_batch = value;
-    else if (!std::strcmp(name, "hub_lanes") && value >= 0 && value <= 8) ctx->opt_hub_lanes = value;
-    else if (!std::strcmp(name, "eig_inverse_iteration") && (value == 0 || value == 1)) ctx->opt_eig_inverse_iteration = value;
-    else if (!std::strcmp(name, "hub_blocking_sync") && (value == 0 || value == 1)) ctx->opt_hub_blocking_sync = value;
-    else if (!std::strcmp(name, "hub_workers") && value >= 0 && value <= 64) ctx->opt_hub_workers = value;
-    else if (!std::strcmp(name, "hub_cohort") && (value == 0 || (value >= 8 && value <= 512))) ctx->opt_hub_cohort = value;
-    else if (!std::strcmp(name, "pair_batch_seq") && value >= 0 && value <= 1024) ctx->opt_pair_batch_seq = value;
-    else if (!std::strcmp(name, "pair_batch_feed") && (value == 0 || value == 1)) ctx->opt_pair_batch_feed = value;
-    else if (!std::strcmp(name, "pair_batch_raw_cap") && (value == 0 || (value >= 64 && value <= (1 << 22)))) ctx->opt_pair_batch_raw_cap = value;
-    else if (!std::strcmp(name, "usac_lo_stepwise") && (value == 0 || value == 1)) ctx->opt_usac_lo_stepwise = value;
-    else if (!std::strcmp(name, "usac_lo_warm_start") && (value == 0 || value == 1)) ctx->opt_usac_lo_warm_start = value;
-    else if (!std::strcmp(name, "usac_first_batch") && value >= 0 && value <= 128) ctx->opt_usac_first_batch = value;
-    else if (!std::strcmp(name, "usac_lo5_fused_fit") && (value == 0 || value == 1)) ctx->opt_usac_lo5_fused_fit = value;
-    else if (!std::strcmp(name, "usac_sprt_fast") && (value == 0 || value == 1)) ctx->opt_usac_sprt_fast = value;
-    else if (!std::strcmp(name, "ransac_host_table") && (value == 0 || value == 1)) ctx->opt_ransac_host_table = value;
-    else if (!std::strcmp(name, "ransac_chunk") && value >= 0 && value <= 32768) ctx->opt_ransac_chunk = value;
-    else {
+    const Option *o = find_option(name);
+    if (!o || !option_accepts(*o, value)) {
         set_error("mlpl_set_option: unknown option or bad value: %s=%d", name, value);
         return MLPL_E_BAD_INPUT;
     }
+    ctx->*(o->field) = value;
     return MLPL_OK;
 }
 
 int mlpl_get_option(mlpl_ctx *ctx, const char *name, int *value) {
     if (!ctx || !name || !value) return MLPL_E_BAD_INPUT;
-    for (const auto &o : kRangeOptions)
-        if (!std::strcmp(name, o.name)) {
-            *value = ctx->*(o.field);
-            return MLPL_OK;
-        }
-    // every name mlpl_set_option accepts, in its order
-    if (!std::strcmp(name, "hamming_variant")) *value = ctx->opt_hamming_variant;
-    else if (!std::strcmp(name, "hamming_mfma_qt")) *value = ctx->opt_hamming_mfma_qt;
-    else if (!std::strcmp(name, "hamming_mfma_blocks_per_cu")) *value = ctx->opt_hamming_mfma_blocks_per_cu;
-    else if (!std::strcmp(name, "hamming_mfma_lds")) *value = ctx->opt_hamming_mfma_lds;
-    else if (!std::strcmp(name, "hamming_expand_fine")) *value = ctx->opt_hamming_expand_fine;
-    else if (!std::strcmp(name, "hamming_mfma_prio")) *value = ctx->opt_hamming_mfma_prio;
-    else if (!std::strcmp(name, "hamming_mfma_prefetch")) *value = ctx->opt_hamming_mfma_prefetch;
-    else if (!std::strcmp(name, "hamming_split_rows")) *value = ctx->opt_hamming_split_rows;
-    else if (!std::strcmp(name, "hamming_mfma_waves")) *value = ctx->opt_hamming_mfma_waves;
-    else if (!std::strcmp(name, "hamming_mfma_weighted")) *value = ctx->opt_hamming_mfma_weighted;
-    else if (!std::strcmp(name, "hamming_fused_merge")) *value = ctx->opt_hamming_fused_merge;
-    else if (!std::strcmp(name, "hamming_stamps")) *value = ctx->opt_hamming_stamps;
-    else if (!std::strcmp(name, "hamming_train01")) *value = ctx->opt_hamming_train01;
-    else if (!std::strcmp(name, "hamming_merge_emit")) *value = ctx->opt_hamming_merge_emit;
-    else if (!std::strcmp(name, "l2_mfma_waves")) *value = ctx->opt_l2_mfma_waves;
-    else if (!std::strcmp(name, "l2_mfma_blocks_per_cu")) *value = ctx->opt_l2_mfma_blocks_per_cu;
-    else if (!std::strcmp(name, "hamming_qpl")) *value = ctx->opt_hamming_qpl;
-    else if (!std::strcmp(name, "hamming_blocks_per_cu")) *value = ctx->opt_hamming_blocks_per_cu;
-    else if (!std::strcmp(name, "ransac_lazy_sums")) *value = ctx->opt_ransac_lazy_sums;
-    else if (!std::strcmp(name, "ransac_overlap")) *value = ctx->opt_ransac_overlap;
-    else if (!std::strcmp(name, "ransac_dev_split")) *value = ctx->opt_ransac_dev_split;
-    else if (!std::strcmp(name, "rand_cache_max")) *value = ctx->opt_rand_cache_max;
-    else if (!std::strcmp(name, "ransac_f32_filter")) *value = ctx->opt_ransac_f32_filter;
-    else if (!std::strcmp(name, "arrsac_refine_warm_start")) *value = ctx->opt_arrsac_refine_warm_start;
-    else if (!std::strcmp(name, "ransac_count_mpl")) *value = ctx->opt_ransac_count_mpl;
-    else if (!std::strcmp(name, "ransac_count_tiles")) *value = ctx->opt_ransac_count_tiles;
-    else if (!std::strcmp(name, "ransac_count_threads")) *value = ctx->opt_ransac_count_threads;
-    else if (!std::strcmp(name, "ransac_count_wpe")) *value = ctx->opt_ransac_count_wpe;
-    else if (!std::strcmp(name, "ransac_count_defer")) *value = ctx->opt_ransac_count_defer;
-    else if (!std::strcmp(name, "ransac_event_cap")) *value = ctx->opt_ransac_event_cap;
-    else if (!std::strcmp(name, "solver_polish")) *value = ctx->opt_solver_polish;
-    else if (!std::strcmp(name, "solver_wave3")) *value = ctx->opt_solver_wave3;
-    else if (!std::strcmp(name, "ransac_device_draw")) *value = ctx->opt_ransac_device_draw;
-    else if (!std::strcmp(name, "l2_float_mfma")) *value = ctx->opt_l2_float_mfma;
-    else if (!std::strcmp(name, "arrsac_flag_points")) *value = ctx->opt_arrsac_flag_points;
-    else if (!std::strcmp(name, "pair_batch")) *value = ctx->opt_pair_batch;
-    else if (!std::strcmp(name, "hub_lanes")) *value = ctx->opt_hub_lanes;
-    else if (!std::strcmp(name, "eig_inverse_iteration")) *value = ctx->opt_eig_inverse_iteration;
-    else if (!std::strcmp(name, "hub_blocking_sync")) *value = ctx->opt_hub_blocking_sync;
-    else if (!std::strcmp(name, "hub_workers")) *value = ctx->opt_hub_workers;
-    else if (!std::strcmp(name, "hub_cohort")) *value = ctx->opt_hub_cohort;
-    else if (!std::strcmp(name, "pair_batch_seq")) *value = ctx->opt_pair_batch_seq;
-    else if (!std::strcmp(name, "pair_batch_feed")) *value = ctx->opt_pair_batch_feed;
-    else if (!std::strcmp(name, "pair_batch_raw_cap")) *value = ctx->opt_pair_batch_raw_cap;
-    else if (!std::strcmp(name, "usac_lo_stepwise")) *value = ctx->opt_usac_lo_stepwise;
-    else if (!std::strcmp(name, "usac_lo_warm_start")) *value = ctx->opt_usac_lo_warm_start;
-    else if (!std::strcmp(name, "usac_first_batch")) *value = ctx->opt_usac_first_batch;
-    else if (!std::strcmp(name, "usac_lo5_fused_fit")) *value = ctx->opt_usac_lo5_fused_fit;
-    else if (!std::strcmp(name, "usac_sprt_fast")) *value = ctx->opt_usac_sprt_fast;
-    else if (!std::strcmp(name, "ransac_host_table")) *value = ctx->opt_ransac_host_table;
-    else if (!std::strcmp(name, "ransac_chunk")) *value = ctx->opt_ransac_chunk;
-    else {
+    const Option *o = find_option(name);
+    if (!o) {
         set_error("mlpl_get_option: unknown option: %s", name);
         return MLPL_E_BAD_INPUT;
     }
+    *value = ctx->*(o->field);
     return MLPL_OK;
+}
+
+int mlpl_option_info(int index, const char **name, int *default_value) {
+    const int count = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
+    if (index < 0 || index >= count || !name || !default_value) return MLPL_E_BAD_INPUT;
+    *name = kOptions[index].name;
+    *default_value = kOptions[index].def;
+    return MLPL_OK;
+}
+
+int mlpl_option_accepts(const char *name, int value) {
+    const Option *o = name ? find_option(name) : nullptr;
+    return o ? (int)option_accepts(*o, value) : MLPL_E_BAD_INPUT;
 }
 
 int mlpl_debug_last_kernels(mlpl_ctx *ctx, int out[13]) {

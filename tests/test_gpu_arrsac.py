@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from matchinglib_poselib_amd import pose, synth
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -21,8 +22,7 @@ SCENES = [(5000, 0.5, 20260103), (5000, 0.3, 20260104), (5000, 0.8, 20260105), (
 @pytest.mark.parametrize("n,frac,seed", SCENES)
 def test_arrsac_equals_the_sequential_oracle(ctx, oracle, n, frac, seed, polish):
     p1, p2, R, t, truth, th = synth.pose_scene(n, frac, seed=seed)
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         for refine in (False, True):
             st_g = np.array(pose.ARRSAC_RNG_FRESH, np.uint64)
             g = pose.arrsac_essential(p1, p2, th, refine=refine, rng_state=st_g, ctx=ctx)
@@ -36,8 +36,6 @@ def test_arrsac_equals_the_sequential_oracle(ctx, oracle, n, frac, seed, polish)
                 assert np.array_equal(g["mask"], o["mask"])
             if g["ok"]:
                 assert e_dist(g["E"], o["E"]) < 1e-7, e_dist(g["E"], o["E"])   # with and without the solver's safeguard
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 @pytest.mark.parametrize("polish", [1, 0])
@@ -45,8 +43,7 @@ def test_arrsac_fixture_on_the_device(ctx, polish):
     """The committed oracle fixture (tests/golden/arrsac_trace.npz): result, statistics, stream positions and the first 60 turns."""
     import os
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "arrsac_trace.npz"))
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         for ci in range(len(g["cases"])):
             buf = np.zeros(20 * 4000, np.int32)
             ctx.lib.mlpl_debug_arrsac_trace(ctx.handle, buf.ctypes.data, len(buf))
@@ -57,16 +54,13 @@ def test_arrsac_fixture_on_the_device(ctx, polish):
             assert np.array_equal(st, g[f"c{ci}_rng"]) and np.array_equal(np.packbits(r["mask"]), g[f"c{ci}_mask"])
             assert e_dist(r["E"], g[f"c{ci}_E"]) < 1e-7
             assert np.array_equal(buf[:ln].reshape(-1, 20)[:60], g[f"c{ci}_turns"])
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 @pytest.mark.parametrize("polish", [1, 0])
 def test_arrsac_streams_carry_over_and_default_method(ctx, oracle, polish):
     """Second call of a process = the reference's second call (static cv::RNGs); estimateEssentialMat's default method is ARRSAC."""
     p1, p2, R, t, truth, th = synth.pose_scene(1500, 0.5, seed=6)
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         st_g, st_o = np.array(pose.ARRSAC_RNG_FRESH, np.uint64), np.array(pose.ARRSAC_RNG_FRESH, np.uint64)
         for call in range(3):
             g = pose.arrsac_essential(p1, p2, th, refine=False, rng_state=st_g, ctx=ctx)
@@ -78,8 +72,6 @@ def test_arrsac_streams_carry_over_and_default_method(ctx, oracle, polish):
         o = oracle.arrsac_essential(p1, p2, th, refine=True)
         assert ok and o["ok"] and np.array_equal(mask, o["mask"]) and e_dist(E, o["E"]) < 1e-7
         assert np.array_equal(pose._arrsac_rng_state, o["rng_state"])
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 @pytest.mark.parametrize("polish", [1, 0])
@@ -87,8 +79,7 @@ def test_arrsac_generation_in_the_preemptive_stage(ctx, oracle, polish):
     """Scenes whose first block is almost all inliers make the preemptive stage generate more hypotheses (uniform sampler over ALL
     correspondences, sequential test over the first i+1): large device batches, scores that double-count, the n == 1 exit."""
     hit = 0
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         for seed in range(40, 60):
             p1, p2, R, t, truth, th = synth.pose_scene(1200, 0.97, seed=seed)
             o = oracle.arrsac_essential(p1, p2, th, refine=False)
@@ -102,8 +93,6 @@ def test_arrsac_generation_in_the_preemptive_stage(ctx, oracle, polish):
             if hit == 4:
                 break
         assert hit >= 1, "no scene reached the generation branch"
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 def test_arrsac_bad_arguments_and_failure(ctx):
@@ -128,8 +117,7 @@ def test_arrsac_forty_scenes_on_one_stream_pair(ctx, oracle, polish):
     st_g = np.array(pose.ARRSAC_RNG_FRESH, np.uint64)
     st_o = st_g.copy()
     exact = 0
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         for it in range(40):
             n = int(rng.choice([60, 99, 100, 101, 150, 250, 600, 1500, 4000]))
             frac = float(rng.choice([0.2, 0.35, 0.5, 0.7, 0.85, 0.95, 1.0]))
@@ -144,8 +132,6 @@ def test_arrsac_forty_scenes_on_one_stream_pair(ctx, oracle, polish):
             if g["ok"]:
                 assert e_dist(g["E"], o["E"]) < 1e-7, it
         assert exact >= 36, exact
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 def test_arrsac_device_variant_equals_host_api(ctx):
@@ -168,8 +154,7 @@ def test_arrsac_tiny_inputs(ctx, oracle, n, polish):
     """Fewer correspondences than one block: the first stage alone decides (arrsac.h:388-401); the result fails the final
     plausibility test below 15 inliers (modelest.cpp:275-278) -- both sides must say so alike."""
     p1, p2, R, t, truth, th = synth.pose_scene(n, 0.9, seed=500 + n)
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         st = np.array(pose.ARRSAC_RNG_FRESH, np.uint64)
         g = pose.arrsac_essential(p1, p2, th, refine=True, rng_state=st, ctx=ctx)
         o = oracle.arrsac_essential(p1, p2, th, refine=True)
@@ -179,8 +164,6 @@ def test_arrsac_tiny_inputs(ctx, oracle, n, polish):
             assert np.array_equal(g["mask"], o["mask"])
         if g["ok"]:
             assert e_dist(g["E"], o["E"]) < 1e-7
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 def test_robust_essential_refine_on_the_device(ctx, oracle):
@@ -213,8 +196,7 @@ def test_arrsac_estimators_on_single_samples(ctx, oracle, polish):
     while the device's stay on them -- those are counted, not compared."""
     p1, p2, R, t, truth, th = synth.pose_scene(400, 0.8, seed=91, noise_px=1.0)
     rng = np.random.default_rng(7)
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_polish=polish):
         compared = off = 0
         for trial in range(60):
             m = 6 + (trial & 1)
@@ -243,8 +225,6 @@ def test_arrsac_estimators_on_single_samples(ctx, oracle, polish):
                 ok, F = oracle.cv_fm_8point(p1[idx], p2[idx])
                 assert ok and len(Eg) == 1 and np.abs(Eg[0] - F).max() < 1e-8 * np.abs(F).max(), (m, trial)
                 assert vg[0] == oracle.valid_model(p1[idx], p2[idx], F)
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 def test_arrsac_preemptive_stage_past_the_up_front_rows(ctx, oracle):
@@ -254,19 +234,16 @@ def test_arrsac_preemptive_stage_past_the_up_front_rows(ctx, oracle):
     so the test lowers the up-front row length to 256 and 128 (option arrsac_flag_points) on scenes whose stage ends at 419..819:
     statistics (stats[6] = where the stage ended), stream positions, inlier counts and masks equal to the oracle's, refinement on and off."""
     past = 0
-    try:
-        for frac, noise, seed in ((0.9808375976373475, 0.3, 1218), (0.9937940121440533, 0.3, 1743), (0.9953357108295809, 0.01, 3073),
-                                  (0.9948514566031564, 0.05, 3193), (0.9881629620106517, 1.5, 1010), (0.9942391333394867, 0.02, 3152)):
-            p1, p2, R, t, truth, th = synth.pose_scene(2500, frac, seed=seed, noise_px=noise)
-            for refine in (False, True):
-                o = oracle.arrsac_essential(p1, p2, th, refine=refine)
-                for fp in (256, 128, 0):
-                    ctx.set_option("arrsac_flag_points", fp)
+    for frac, noise, seed in ((0.9808375976373475, 0.3, 1218), (0.9937940121440533, 0.3, 1743), (0.9953357108295809, 0.01, 3073),
+                              (0.9948514566031564, 0.05, 3193), (0.9881629620106517, 1.5, 1010), (0.9942391333394867, 0.02, 3152)):
+        p1, p2, R, t, truth, th = synth.pose_scene(2500, frac, seed=seed, noise_px=noise)
+        for refine in (False, True):
+            o = oracle.arrsac_essential(p1, p2, th, refine=refine)
+            for fp in (256, 128, 0):
+                with options(ctx, arrsac_flag_points=fp):
                     st_g = np.array(pose.ARRSAC_RNG_FRESH, np.uint64)
                     g = pose.arrsac_essential(p1, p2, th, refine=refine, rng_state=st_g, ctx=ctx)
                     assert g["ok"] == o["ok"] and g["stats"][:8].tolist() == o["stats"].tolist(), (frac, noise, fp, g["stats"], o["stats"])
                     assert st_g.tolist() == o["rng_state"].tolist() and g["n_inliers"] == o["n_inliers"] and np.array_equal(g["mask"], o["mask"])
-                past += int(o["stats"][6] >= 256)
-    finally:
-        ctx.set_option("arrsac_flag_points", 0)
+            past += int(o["stats"][6] >= 256)
     assert past >= 8, past      # the scenes do run past the shortened rows

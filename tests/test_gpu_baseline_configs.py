@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from matchinglib_poselib_amd import pose, synth
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -90,13 +91,8 @@ def test_ransac_record_list_overflow_takes_the_serial_path(ctx, oracle, cap, con
     those paths on ordinary data: the run must not change."""
     p1, p2, R, t, mask, th = synth.pose_scene(2500, inlier_frac=0.45, seed=77)
     want = oracle.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, lesqu=False, seed=9)
-    ctx.set_option("ransac_event_cap", cap)
-    ctx.set_option("ransac_host_table", host_table)
-    try:
+    with options(ctx, ransac_event_cap=cap, ransac_host_table=host_table):
         g = pose.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, refit=False, seed=9, ctx=ctx)
-    finally:
-        ctx.set_option("ransac_event_cap", 0)
-        ctx.set_option("ransac_host_table", 0)
     assert_same_run(g, want, p1, p2, oracle)
 
 
@@ -104,8 +100,7 @@ def test_ransac_record_list_overflow_takes_the_serial_path(ctx, oracle, cap, con
 def test_rand_stream_cache_across_calls_seeds_and_its_cap(ctx, oracle, cache_max):
     """The context keeps the raw rand() stream of the last seed.  Calls with the same seed and different n, a changed seed, LMedS in
     between, and a cache far too small for a call (a private generator continues behind it) must all see the stream srand(seed) gives."""
-    ctx.set_option("rand_cache_max", cache_max)
-    try:
+    with options(ctx, rand_cache_max=cache_max):
         for n, seed, iters in [(900, 5, 800), (1300, 5, 1500), (700, 6, 600), (900, 5, 800), (2000, 5, 5000)]:
             p1, p2, R, t, mask, th = synth.pose_scene(n, inlier_frac=0.5, seed=n)
             g = pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=iters, refit=False, seed=seed, ctx=ctx)
@@ -114,8 +109,6 @@ def test_rand_stream_cache_across_calls_seeds_and_its_cap(ctx, oracle, cache_max
             gl = pose.lmeds_essential(p1, p2, seed=seed + 1, ctx=ctx)
             ol = oracle.lmeds_essential(p1, p2, seed=seed + 1)
             assert gl["ok"] == ol["ok"] and gl["n_inliers"] == ol["n_inliers"]
-    finally:
-        ctx.set_option("rand_cache_max", 0)
 
 
 def test_ransac_tiny_inlier_fraction_uses_every_iteration(ctx, oracle):
@@ -183,11 +176,8 @@ def test_solver_polish_off_is_the_plain_root_path(ctx, oracle):
     p1, p2, R, t, mask, th = synth.pose_scene(5000, seed=20260103)
     samples = oracle.sample_table(12345, p1, p2, 2000)
     E1, n1 = pose.solve_5pt(p1, p2, samples, ctx=ctx)
-    ctx.set_option("solver_polish", 0)
-    try:
+    with options(ctx, solver_polish=0):
         E0, n0 = pose.solve_5pt(p1, p2, samples, ctx=ctx)
-    finally:
-        ctx.set_option("solver_polish", 1)
     assert np.array_equal(n0, n1)
     d = np.abs(E0 - E1).reshape(len(samples), -1).max(axis=1)
     assert d.max() < 1e-3 and (d > 1e-8).sum() < 40 and np.median(d) < 1e-13
@@ -220,11 +210,8 @@ def test_the_safeguard_is_what_keeps_the_device_on_the_cpu_path(ctx, oracle):
 
     assert ctx.get_option("solver_polish") == 1
     m1, d1, o1, g1 = tally()
-    ctx.set_option("solver_polish", 0)
-    try:
+    with options(ctx, solver_polish=0):
         m0, d0, o0, g0 = tally()
-    finally:
-        ctx.set_option("solver_polish", 1)
     print(f"\nsafeguard on: {d1} of {m1} models differ by > 1e-8 (oracle's model the inaccurate one: {o1}, the device's: {g1}); "
           f"off: {d0} of {m0} (oracle's {o0}, device's {g0})")
     assert d1 == o1 and g1 == 0 and d1 <= 0.006 * m1

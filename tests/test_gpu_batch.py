@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from matchinglib_poselib_amd import batch, synth
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -93,11 +94,8 @@ def test_batched_pairs_equal_the_single_pair_pipeline(ctx):
     assert stats[0] == 2 and 70 < stats[1] < 140, stats      # a second pass ran, and only for part of the pairs
     assert stats[6] >= 70 * 20 and stats[4] > stats[6] and stats[5] > 100 * stats[4], stats   # iterations, matrices scored, evaluations
     # smaller internal batches (16 + 16 + 16 + 16 + 6) give the same records
-    ctx.set_option("pair_batch", 16)
-    try:
+    with options(ctx, pair_batch=16):
         assert batch.process_pairs_batched(ctx, dq, dt, k1, k2, K, K, seeds).tobytes() == bat.tobytes()
-    finally:
-        ctx.set_option("pair_batch", 0)
 
 
 def test_batched_pairs_edge_cases(ctx, oracle):
@@ -145,11 +143,8 @@ def test_batched_pairs_few_matches_and_short_raw_streams(ctx):
     dq, dt, k1, k2 = _stack(sps, dev)
     stats = np.zeros(8, np.int64)
     for cap, redone in ((0, False), (1500, True), (2200, True), (400, True)):
-        ctx.set_option("pair_batch_raw_cap", cap)
-        try:
+        with options(ctx, pair_batch_raw_cap=cap):
             bat = batch.process_pairs_batched(ctx, dq, dt, k1, k2, K, K, seeds)
-        finally:
-            ctx.set_option("pair_batch_raw_cap", 0)
         ctx.lib.mlpl_pair_batch_last_stats(ctx.handle, stats.ctypes.data)
         for i in range(12):
             assert bat[i].tobytes() == one[i].tobytes(), (cap, i, bat[i], one[i])
@@ -186,11 +181,8 @@ def test_batched_correspondence_sets_equal_the_single_problem_entries(ctx, recov
     # reuse the context's pinned block: ADVICE r3), with the same records and masks
     masks2 = torch.zeros((40, stride), dtype=torch.uint8, device=dev)
     stats = np.zeros(8, np.int64)
-    ctx.set_option("pair_batch_raw_cap", 1700)
-    try:
+    with options(ctx, pair_batch_raw_cap=1700):
         got2 = batch.ransac_pose_batched(ctx, d1, d2, sizes, seeds, ths, recover_pose=recover, masks_out=masks2)
-    finally:
-        ctx.set_option("pair_batch_raw_cap", 0)
     ctx.lib.mlpl_pair_batch_last_stats(ctx.handle, stats.ctypes.data)
     assert stats[2] >= 2, stats
     for g, h in zip(got, got2):

@@ -278,3 +278,26 @@ def test_every_option_round_trips(ctx):
                 with pytest.raises(_lib.MlplError):
                     ctx.set_option(name, bad)
                 assert ctx.get_option(name) == values[-1], (name, bad)
+
+
+def test_a_fresh_context_has_the_defaults_and_the_guard_puts_every_option_back(monkeypatch):
+    """No kernel runs: a new context reads the written-down default of every option; a block that sets ALL of them to something else and
+    then fails leaves all of them at their defaults; a refused value (a range option, a closed-set option) raises and changes nothing."""
+    import matchinglib_poselib_amd as mpa
+    from option_guard import DEFAULTS, SETTABLE
+    monkeypatch.delenv("MLPL_OPTIONS", raising=False)
+    c = mpa.Context(0)
+    try:
+        assert len(DEFAULTS) == 56 and {name: c.get_option(name) for name in DEFAULTS} == DEFAULTS
+        other = {name: next(v for v in SETTABLE[name] if v != DEFAULTS[name]) for name in DEFAULTS}
+        with pytest.raises(ZeroDivisionError):
+            with options(c, **other):
+                assert {name: c.get_option(name) for name in DEFAULTS} == other
+                1 / 0
+        assert {name: c.get_option(name) for name in DEFAULTS} == DEFAULTS
+        for name, bad in (("hamming_mfma_blocks_per_cu", 65), ("hamming_mfma_blocks_per_cu", 0), ("hamming_block_top2", 2)):
+            with pytest.raises(_lib.MlplError):
+                c.set_option(name, bad)
+            assert c.get_option(name) == DEFAULTS[name], (name, bad)
+    finally:
+        c.close()

@@ -10,7 +10,6 @@ the same build), and every call asserts through mlpl_debug_last_kernels that the
 expansion.  As in test_gpu_hamming_ring_unrolled.py each case runs in two forms: `single_pair` (one pair of 1024 queries: the launcher cuts
 the train set into one split per tile -- prologue, ragged tile, partial table and ticket merge) and `one_split` (2 x CUs pairs through the
 batched device entry: one split per pair, a workgroup walks through all tiles; the oracle checks 8 of the pairs)."""
-import contextlib
 import functools
 
 import numpy as np
@@ -30,24 +29,12 @@ FULL = 8192   # rows of a full split
 N_CHECK = 8   # pairs of a batch the oracle checks
 
 
-@contextlib.contextmanager
-def expand_options(ctx, inkernel, **settings):
-    """option_guard.options plus hamming_expand_inkernel, which the guard's list does not carry: put back on the way out."""
-    before = ctx.get_option("hamming_expand_inkernel")
-    with options(ctx, **settings):
-        try:
-            ctx.set_option("hamming_expand_inkernel", inkernel)
-            yield
-        finally:
-            ctx.set_option("hamming_expand_inkernel", before)
-
-
 def _assert_instance(rec, inkernel):
     assert (rec[KIND], rec[QT], rec[NWV], rec[PD], rec[INKERNEL]) == (4, 4, 8, 2, inkernel), rec
 
 
 def _knn(ctx, q, t, k, inkernel, **extra):
-    with expand_options(ctx, inkernel, **FORCE, **extra):
+    with options(ctx, **FORCE, **extra, hamming_expand_inkernel=inkernel):
         idx, dist = mpa.knn_hamming(q, t, k=k, ctx=ctx)
         rec = ctx.last_kernels()
     _assert_instance(rec, inkernel)
@@ -66,7 +53,7 @@ def _single_pair(ctx, oracle, q, t, k=2, **extra):
 
 
 def _batched(ctx, dq, dt, inkernel, k, **extra):
-    with expand_options(ctx, inkernel, **FORCE, hamming_mfma_blocks_per_cu=1, **extra):
+    with options(ctx, **FORCE, hamming_mfma_blocks_per_cu=1, **extra, hamming_expand_inkernel=inkernel):
         out = match_hamming_device(dq, dt, ratio_test=k == 2, ctx=ctx)
         rec = ctx.last_kernels()
         out = {key: v.cpu().numpy() for key, v in out.items()}

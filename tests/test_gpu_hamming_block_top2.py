@@ -19,7 +19,6 @@ second are members of one cluster.  A tile carries these clusters (local rows; h
     (24, 26 | 32 + 25), (32 + 14, 32 + 15 | 12)   the same tie against a row of the SAME lane column in the next / the previous tile.
 Which cluster, which of its rows and how many flipped bits a query gets follows from its index (the cluster count is odd, so all lanes and
 all four query tiles of a wave meet all clusters); the oracle alone decides what the right answer is."""
-import contextlib
 import functools
 
 import numpy as np
@@ -40,18 +39,6 @@ NQ = 1024
 TRAIN_SIZES = (2, 32, 33, 64, 96, 98, 129, 160, 197, 256, 288)
 
 TILE_CLUSTERS = ((0, 1), (28, 29, 30), (2, 10), (3, 7), (8, 9, 4), (17, 18, 21), (5, 32 + 6), (24, 26, 32 + 25), (32 + 14, 32 + 15, 12))
-
-
-@contextlib.contextmanager
-def block_options(ctx, block, **settings):
-    """option_guard.options plus hamming_block_top2, which the guard's list does not carry: put back on the way out."""
-    before = ctx.get_option("hamming_block_top2")
-    with options(ctx, **FORCE, **settings):
-        try:
-            ctx.set_option("hamming_block_top2", block)
-            yield
-        finally:
-            ctx.set_option("hamming_block_top2", before)
 
 
 def _assert_instance(ctx, block):
@@ -100,7 +87,7 @@ def clustered_pair(nq, nt, seed, identical_train=False):
 
 
 def _knn(ctx, q, t, k, block, **extra):
-    with block_options(ctx, block, **extra):
+    with options(ctx, **FORCE, **extra, hamming_block_top2=block):
         idx, dist = mpa.knn_hamming(q, t, k=k, ctx=ctx)
         rec = _assert_instance(ctx, block)
     return idx, dist, rec
@@ -116,7 +103,7 @@ def _single_pair(ctx, oracle, q, t, block, k=2, **extra):
 
 
 def _batched(ctx, dq, dt, block, k=2, **extra):
-    with block_options(ctx, block, **extra):
+    with options(ctx, **FORCE, **extra, hamming_block_top2=block):
         out = match_hamming_device(dq, dt, ratio_test=k == 2, ctx=ctx)
         rec = _assert_instance(ctx, block)
     return {name: v.cpu().numpy() for name, v in out.items()}, rec
@@ -239,8 +226,7 @@ def test_one_pair_8192_by_8192(ctx, oracle, block):
 
 def test_option_values(ctx):
     """0 and the block sizes are accepted, anything else is refused and leaves the option as it was."""
-    before = ctx.get_option("hamming_block_top2")
-    try:
+    with options(ctx):
         for v in (0,) + BLOCKS:
             ctx.set_option("hamming_block_top2", v)
             assert ctx.get_option("hamming_block_top2") == v
@@ -248,5 +234,3 @@ def test_option_values(ctx):
             with pytest.raises(mpa.MlplError):
                 ctx.set_option("hamming_block_top2", v)
             assert ctx.get_option("hamming_block_top2") == BLOCKS[-1]
-    finally:
-        ctx.set_option("hamming_block_top2", before)

@@ -5,7 +5,6 @@ mlpl_debug_last_kernels which of the two paths ran (a silent fallback would make
 The throughput instance is forced (hamming_mfma_qt = 4, hamming_mfma_waves = 8).  The launcher cuts a small train set into one split per
 tile, so the small shapes mostly exercise the prologue, the ragged tile and the ticket merge; the deep-split cases (eight pairs of 8192
 queries) are the ones in which a workgroup walks through several tiles, wraps both rings and ends on a ragged tile."""
-import contextlib
 import functools
 
 import numpy as np
@@ -21,20 +20,6 @@ pytestmark = pytest.mark.gpu
 
 KIND, QT, NWV, PD, NSPLIT, INKERNEL = 2, 3, 5, 6, 10, 12
 FORCE = dict(hamming_mfma_qt=4, hamming_mfma_waves=8)
-
-
-
-@contextlib.contextmanager
-def expand_options(ctx, inkernel, **settings):
-    """option_guard.options plus the knob under test, which lives in the library's option table and not in the guard's list: it is put
-    back to what it was on the way out, exception or not."""
-    before = ctx.get_option("hamming_expand_inkernel")
-    with options(ctx, **settings):
-        try:
-            ctx.set_option("hamming_expand_inkernel", inkernel)
-            yield
-        finally:
-            ctx.set_option("hamming_expand_inkernel", before)
 
 
 NT = [32, 64, 96, 160, 33, 95, 129, 4097]
@@ -60,7 +45,7 @@ def _reference(oracle, nq, nt):
 
 
 def _knn(ctx, q, t, k, inkernel, expect_inkernel, **extra):
-    with expand_options(ctx, inkernel, **FORCE, **extra):
+    with options(ctx, **FORCE, **extra, hamming_expand_inkernel=inkernel):
         idx, dist = mpa.knn_hamming(q, t, k=k, ctx=ctx)
         rec = ctx.last_kernels()
     assert (rec[KIND], rec[QT], rec[NWV], rec[PD]) == (4, 4, 8, 2), rec
@@ -109,7 +94,7 @@ def test_inkernel_expand_on_the_shared_case_list(ctx, oracle):
             assert (rec[KIND], rec[QT], rec[NWV]) == (4, 4, 8), rec
         seen.add(eligible)
 
-    with expand_options(ctx, 1, **FORCE):
+    with options(ctx, **FORCE, hamming_expand_inkernel=1):
         check_hamming_cases(ctx, oracle, "inkernel", after_call)
     assert seen == {True, False}
 
@@ -130,7 +115,7 @@ def test_inkernel_expand_deep_splits(ctx, oracle, nt):
         dt = torch.from_numpy(np.stack(tset)).to(dev)
         res = []
         for on in (1, 0):
-            with expand_options(ctx, on, **FORCE):
+            with options(ctx, **FORCE, hamming_expand_inkernel=on):
                 out = match_hamming_device(dq, dt, ctx=ctx)
                 rec = ctx.last_kernels()
             assert (rec[KIND], rec[NWV], rec[INKERNEL]) == (4, 8, on), rec
@@ -161,7 +146,7 @@ def test_inkernel_expand_batched_device_entry_with_padded_batch_stride(ctx, orac
     assert dt.stride(0) > nt * 32
     res = []
     for on in (1, 0):
-        with expand_options(ctx, on, **FORCE):
+        with options(ctx, **FORCE, hamming_expand_inkernel=on):
             out = match_hamming_device(dq, dt, ctx=ctx)
             rec = ctx.last_kernels()
         assert (rec[KIND], rec[NWV], rec[INKERNEL]) == (4, 8, on), rec
@@ -196,7 +181,7 @@ def test_inkernel_expand_falls_back(ctx, oracle, case):
     nbytes = 64 if case == "bytes64" else 32
     extra = {"train01": dict(hamming_train01=1), "waves4": dict(hamming_mfma_waves=4), "prefetch4": dict(hamming_mfma_prefetch=4)}.get(case, {})
     q, t = _pair(300, 700, nbytes)
-    with expand_options(ctx, 1, **{**FORCE, **extra}):
+    with options(ctx, **{**FORCE, **extra}, hamming_expand_inkernel=1):
         idx, dist = mpa.knn_hamming(q, t, ctx=ctx)
         rec = ctx.last_kernels()
     assert rec[INKERNEL] == 0, rec

@@ -136,7 +136,7 @@ def test_l2_matrix_core_blocks_per_cu(ctx, oracle, bpc):
             _lib.check(ctx.lib.mlpl_set_l2_path(ctx.handle, 0), "set_l2_path")
         oi, od = oracle.knn_l2sq(qi[sub], ti)
         assert np.array_equal(idx[sub], oi) and dist[sub].tobytes() == od.tobytes()
-        ctx.set_option("l2_float_mfma", 2)
-        idx, dist = mpa.knn_l2sq(qf, tf, ctx=ctx)
+        with options(ctx, l2_float_mfma=2):
+            idx, dist = mpa.knn_l2sq(qf, tf, ctx=ctx)
         oi, od = oracle.knn_l2sq(qf[sub], tf)
         assert np.array_equal(idx[sub], oi) and dist[sub].tobytes() == od.tobytes()

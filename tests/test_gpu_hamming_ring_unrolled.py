@@ -9,7 +9,6 @@ gets one split per tile whatever hamming_mfma_blocks_per_cu says (the ring kerne
 `single_pair` are therefore prologue / ragged-tile / ticket-merge cases; the cases named `one_split` run the same train sizes on 2 x CUs pairs
 through the batched device entry, where the chip is full with one split per pair and a workgroup really walks through T tiles -- the record's
 split count is asserted, so that they cannot turn vacuous."""
-import contextlib
 import ctypes as C
 import functools
 
@@ -29,25 +28,13 @@ NQ = 1024
 T_MAX = 9
 
 
-@contextlib.contextmanager
-def expand_options(ctx, inkernel, **settings):
-    """option_guard.options plus hamming_expand_inkernel, which the guard's list does not carry: put back on the way out."""
-    before = ctx.get_option("hamming_expand_inkernel")
-    with options(ctx, **settings):
-        try:
-            ctx.set_option("hamming_expand_inkernel", inkernel)
-            yield
-        finally:
-            ctx.set_option("hamming_expand_inkernel", before)
-
-
 def _assert_instance(rec, inkernel):
     assert (rec[KIND], rec[QT], rec[NWV], rec[PD]) == (4, 4, 8, 2), rec
     assert rec[INKERNEL] == inkernel, rec
 
 
 def _knn(ctx, q, t, k, inkernel, **extra):
-    with expand_options(ctx, inkernel, **FORCE, **extra):
+    with options(ctx, **FORCE, **extra, hamming_expand_inkernel=inkernel):
         idx, dist = mpa.knn_hamming(q, t, k=k, ctx=ctx)
         rec = ctx.last_kernels()
     _assert_instance(rec, inkernel)
@@ -65,7 +52,7 @@ def _both(ctx, oracle, q, t, k=2, **extra):
 
 
 def _batched(ctx, dq, dt, inkernel, k=2, **extra):
-    with expand_options(ctx, inkernel, **FORCE, **extra):
+    with options(ctx, **FORCE, **extra, hamming_expand_inkernel=inkernel):
         out = match_hamming_device(dq, dt, ratio_test=k == 2, ctx=ctx)
         rec = ctx.last_kernels()
     _assert_instance(rec, inkernel)
@@ -236,7 +223,7 @@ def test_stamps_keep_their_per_tile_records(ctx, oracle):
     dq, dt_all, hq, ht = _full_chip_batch()
     B = len(hq)
     plain, _ = _batched(ctx, dq, dt_all, 1)
-    with expand_options(ctx, 1, **FORCE, hamming_stamps=1):
+    with options(ctx, **FORCE, hamming_stamps=1, hamming_expand_inkernel=1):
         out = match_hamming_device(dq, dt_all, ctx=ctx)
         rec = ctx.last_kernels()
         _assert_instance(rec, 1)

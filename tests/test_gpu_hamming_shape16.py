@@ -15,7 +15,6 @@ zero-distance rows on the first and last row of a full split, ragged last tiles 
 neighbour hidden in the best row's block at each of the three other offsets, in the same lane's other row half (+16) and in another lane
 group (+4), the clusters of test_gpu_hamming_block_top2.py, zero / one pair of tiles with and without an odd tile, four pairs with a rolled
 tail and a ragged tile, a ragged query group, a padded batch stride, one neighbour, and the benchmark's pair shape."""
-import contextlib
 import functools
 
 import numpy as np
@@ -36,18 +35,6 @@ FULL = 8192   # rows of a full split
 N_CHECK = 8   # pairs of a batch the oracle checks
 
 
-@contextlib.contextmanager
-def shape_options(ctx, shape, **settings):
-    """option_guard.options plus hamming_mfma_shape, which the guard's list does not carry: put back on the way out."""
-    before = ctx.get_option("hamming_mfma_shape")
-    with options(ctx, **FORCE, **settings):
-        try:
-            ctx.set_option("hamming_mfma_shape", shape)
-            yield
-        finally:
-            ctx.set_option("hamming_mfma_shape", before)
-
-
 def _assert_instance(ctx, shape):
     rec = ctx.last_kernels()
     assert (rec[KIND], rec[QT], rec[NWV], rec[PD], rec[INKERNEL]) == (4, 4, 8, 2, 1), rec
@@ -57,7 +44,7 @@ def _assert_instance(ctx, shape):
 
 
 def _knn(ctx, q, t, k, shape, **extra):
-    with shape_options(ctx, shape, **extra):
+    with options(ctx, **FORCE, **extra, hamming_mfma_shape=shape):
         idx, dist = mpa.knn_hamming(q, t, k=k, ctx=ctx)
         rec = _assert_instance(ctx, shape)
     return idx, dist, rec
@@ -75,7 +62,7 @@ def _single_pair(ctx, oracle, q, t, k=2, **extra):
 
 
 def _batched(ctx, dq, dt, shape, k, **extra):
-    with shape_options(ctx, shape, hamming_mfma_blocks_per_cu=1, **extra):
+    with options(ctx, **FORCE, hamming_mfma_blocks_per_cu=1, **extra, hamming_mfma_shape=shape):
         out = match_hamming_device(dq, dt, ratio_test=k == 2, ctx=ctx)
         rec = _assert_instance(ctx, shape)
         out = {key: v.cpu().numpy() for key, v in out.items()}
@@ -335,17 +322,12 @@ def test_one_neighbour_single_pair(ctx, oracle):
 
 def test_shape_ignored_by_the_stamped_and_the_per_candidate_instances(ctx):
     hq, ht0, _, _ = _random_batch()
-    before = ctx.get_option("hamming_block_top2")
-    with shape_options(ctx, 16, hamming_stamps=1):
+    with options(ctx, **FORCE, hamming_stamps=1, hamming_mfma_shape=16):
         mpa.knn_hamming(hq[1], ht0[1, :N_SMALL], k=2, ctx=ctx)
         assert ctx.last_hamming_shape() == 32
-    try:
-        ctx.set_option("hamming_block_top2", 0)
-        with shape_options(ctx, 16):
-            mpa.knn_hamming(hq[1], ht0[1, :N_SMALL], k=2, ctx=ctx)
-            assert ctx.last_hamming_shape() == 32
-    finally:
-        ctx.set_option("hamming_block_top2", before)
+    with options(ctx, hamming_block_top2=0, **FORCE, hamming_mfma_shape=16):
+        mpa.knn_hamming(hq[1], ht0[1, :N_SMALL], k=2, ctx=ctx)
+        assert ctx.last_hamming_shape() == 32
 
 
 def test_option_values(ctx):

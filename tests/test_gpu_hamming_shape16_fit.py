@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 from matchinglib_poselib_amd.matching import match_hamming_device
-from test_gpu_hamming_shape16 import FULL, NQ, _assert_instance, _batch_size, _check_pairs, _dev, _random_batch, shape_options
+from option_guard import options
+from test_gpu_hamming_shape16 import FORCE, FULL, NQ, _assert_instance, _batch_size, _check_pairs, _dev, _random_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,7 @@ FORMS = ["single_pair", "one_split"]
 
 
 def _run(ctx, dq, dt, shape, k):
-    with shape_options(ctx, shape, hamming_mfma_blocks_per_cu=1):
+    with options(ctx, **FORCE, hamming_mfma_blocks_per_cu=1, hamming_mfma_shape=shape):
         out = match_hamming_device(dq, dt, ratio_test=k == 2, ctx=ctx)
         rec = _assert_instance(ctx, shape)
         assert ctx.last_hamming_block_rows() == BLOCK_ROWS[shape], (ctx.last_hamming_block_rows(), shape)

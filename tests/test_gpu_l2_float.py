@@ -6,6 +6,7 @@ import pytest
 
 import matchinglib_poselib_amd as mpa
 from matchinglib_poselib_amd import _lib, synth
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -82,16 +83,13 @@ def test_auto_mode_hint_and_always_modes(ctx):
     qi, ti = synth.sift_pair(500, 900, seed=3)
     exi = run(ctx, qi, ti, 1)
     for opt in (1, 2, 0):
-        ctx.set_option("l2_float_mfma", opt)
-        try:
+        with options(ctx, l2_float_mfma=opt):
             for _ in range(3):
                 assert same(run(ctx, q, t, 0), ex), opt
                 ctx.synchronize()
             assert same(run(ctx, qi, ti, 0), exi), opt
             ctx.synchronize()
             assert same(run(ctx, q, t, 0), ex), opt
-        finally:
-            ctx.set_option("l2_float_mfma", 1)
 
 
 def test_general_floats_negative_values_and_scales(ctx):
@@ -123,11 +121,8 @@ def test_many_near_ties_overflow_the_candidate_list(ctx):
     before = full_scans(ctx)
     assert same(ex, run(ctx, q, t, 3))
     assert full_scans(ctx) - before == len(q)   # every query sees all 600 rows inside its window
-    ctx.set_option("l2_float_mfma", 2)
-    try:
+    with options(ctx, l2_float_mfma=2):
         assert same(ex, run(ctx, q, t, 0))
-    finally:
-        ctx.set_option("l2_float_mfma", 1)
 
 
 def test_distances_below_the_resolution_of_the_fp16_products(ctx):
@@ -171,21 +166,15 @@ def test_rows_outside_the_range_are_scanned_exhaustively(ctx):
         else:
             t2[17, 3] = bad
         ex = run(ctx, q, t2, 1)
-        ctx.set_option("l2_float_mfma", 2)
-        try:
+        with options(ctx, l2_float_mfma=2):
             assert same(ex, run(ctx, q, t2, 0)), bad
-        finally:
-            ctx.set_option("l2_float_mfma", 1)
         with pytest.raises(RuntimeError):
             run(ctx, q, t2, 3)
     big = np.random.default_rng(1).random((40, 200)).astype(np.float32)  # dim > 128: not on this path
     with pytest.raises(RuntimeError):
         run(ctx, big, big, 3)
-    ctx.set_option("l2_float_mfma", 2)
-    try:
+    with options(ctx, l2_float_mfma=2):
         assert same(run(ctx, big, big, 1), run(ctx, big, big, 0))
-    finally:
-        ctx.set_option("l2_float_mfma", 1)
 
 
 def test_device_batched_float_descriptors(ctx):

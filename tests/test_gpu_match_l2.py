@@ -13,6 +13,7 @@ import pytest
 import matchinglib_poselib_amd as mpa
 from matchinglib_poselib_amd import _lib, synth
 from matchinglib_poselib_amd.matching import match_l2_device
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -128,34 +129,32 @@ def test_match_l2_equals_knn_then_ratio_compact_on_every_path(ctx, case, integer
     try:
         for path, fmfma in paths:
             _set_l2(ctx, path)
-            ctx.set_option("l2_float_mfma", fmfma)
-            for ratio_test in (1, 0):
-                ctx.set_option("l2_fold_counts", 1)
-                want = _chain(ctx, dq, dt, ratio_test)
-                for fold in (1, 0, 1):
-                    ctx.set_option("l2_fold_counts", fold)
-                    got = _match(ctx, dq, dt, ratio_test)
-                    dbg = ctx.last_l2_match()
-                    cnt = _same(got, want, (SHAPES[case], integer, path, fmfma, ratio_test, fold))
-                    if nq == 0:
-                        assert (cnt == 0).all() and dbg == [0, 0, 0, 0]
-                        continue
-                    seen.add(dbg[0])
-                    assert dbg[2] == (1 if fold and dbg[0] != 4 else 0), dbg
-                    if path in (1, 2, 3):
-                        assert dbg[0] == {1: 1, 2: 2, 3: 4}[path], dbg
-                    if ratio_test and nq > 1:    # the query on the duplicated train rows never passes; somebody else does
-                        m = got["matches"].cpu().numpy()
-                        for b in range(B):
-                            assert nq - 1 not in m[b, :cnt[b], 0], (b, "d0 == d1 passed the ratio test")
-                        idx = got["idx"].cpu().numpy()
-                        assert (idx[:, nq - 1, 0] == 0).all() and (idx[:, nq - 1, 1] == 1).all()
-                    if not ratio_test:
-                        assert (cnt == nq).all()
+            with options(ctx, l2_float_mfma=fmfma):
+                for ratio_test in (1, 0):
+                    with options(ctx, l2_fold_counts=1):
+                        want = _chain(ctx, dq, dt, ratio_test)
+                    for fold in (1, 0, 1):
+                        with options(ctx, l2_fold_counts=fold):
+                            got = _match(ctx, dq, dt, ratio_test)
+                            dbg = ctx.last_l2_match()
+                            cnt = _same(got, want, (SHAPES[case], integer, path, fmfma, ratio_test, fold))
+                            if nq == 0:
+                                assert (cnt == 0).all() and dbg == [0, 0, 0, 0]
+                                continue
+                            seen.add(dbg[0])
+                            assert dbg[2] == (1 if fold and dbg[0] != 4 else 0), dbg
+                            if path in (1, 2, 3):
+                                assert dbg[0] == {1: 1, 2: 2, 3: 4}[path], dbg
+                            if ratio_test and nq > 1:    # the query on the duplicated train rows never passes; somebody else does
+                                m = got["matches"].cpu().numpy()
+                                for b in range(B):
+                                    assert nq - 1 not in m[b, :cnt[b], 0], (b, "d0 == d1 passed the ratio test")
+                                idx = got["idx"].cpu().numpy()
+                                assert (idx[:, nq - 1, 0] == 0).all() and (idx[:, nq - 1, 1] == 1).all()
+                            if not ratio_test:
+                                assert (cnt == nq).all()
     finally:
         _set_l2(ctx, 0)
-        ctx.set_option("l2_float_mfma", 1)
-        ctx.set_option("l2_fold_counts", 1)
     if nq:
         assert seen, "no path ran"
 
@@ -177,22 +176,21 @@ def test_fold_kernel_group_counts(ctx, case):
             dist = torch.empty((B, nq, 2), dtype=torch.float32, device="cuda")
             torch.cuda.synchronize()
             _set_l2(ctx, path)
-            ctx.set_option("l2_float_mfma", 0)
-            for ratio_test in (1, 0):
-                counts = np.full((B, ncnt), -7, np.int32)
-                n = ctx.lib.mlpl_debug_l2_fold_counts(ctx.handle, dq.data_ptr(), nq, dim, nq * dim, dt.data_ptr(), nt, dim, nt * dim, dim, ratio_test, 0.75, B,
-                                                      idx.data_ptr(), dist.data_ptr(), counts.ctypes.data)
-                assert n == B * ncnt, (n, _lib.last_error())
-                k = 2 if ratio_test else 1
-                d = dist.cpu().numpy().reshape(-1)[: B * nq * k].reshape(B, nq, k)
-                ok = (d[:, :, 0] < np.float32(0.75) * d[:, :, 1]) if ratio_test else np.ones((B, nq), bool)
-                want = np.add.reduceat(ok.astype(np.int32), np.arange(0, nq, 64), axis=1)
-                assert np.array_equal(counts, want), (SHAPES[case], integer, path, ratio_test, counts[0][:8], want[0][:8])
-                if ratio_test and nq > 1:
-                    assert not ok[:, nq - 1].any()      # d0 == d1 on the duplicated rows: `<`, not `<=`
+            with options(ctx, l2_float_mfma=0):
+                for ratio_test in (1, 0):
+                    counts = np.full((B, ncnt), -7, np.int32)
+                    n = ctx.lib.mlpl_debug_l2_fold_counts(ctx.handle, dq.data_ptr(), nq, dim, nq * dim, dt.data_ptr(), nt, dim, nt * dim, dim, ratio_test, 0.75, B,
+                                                          idx.data_ptr(), dist.data_ptr(), counts.ctypes.data)
+                    assert n == B * ncnt, (n, _lib.last_error())
+                    k = 2 if ratio_test else 1
+                    d = dist.cpu().numpy().reshape(-1)[: B * nq * k].reshape(B, nq, k)
+                    ok = (d[:, :, 0] < np.float32(0.75) * d[:, :, 1]) if ratio_test else np.ones((B, nq), bool)
+                    want = np.add.reduceat(ok.astype(np.int32), np.arange(0, nq, 64), axis=1)
+                    assert np.array_equal(counts, want), (SHAPES[case], integer, path, ratio_test, counts[0][:8], want[0][:8])
+                    if ratio_test and nq > 1:
+                        assert not ok[:, nq - 1].any()      # d0 == d1 on the duplicated rows: `<`, not `<=`
     finally:
         _set_l2(ctx, 0)
-        ctx.set_option("l2_float_mfma", 1)
 
 
 def test_negative_and_bad_arguments_are_refused(ctx):
@@ -215,17 +213,14 @@ def test_debug_entry_reports_the_fold_and_one_launch_less(ctx, path):
     dq, dt = torch.from_numpy(q[None]).cuda(), torch.from_numpy(t[None]).cuda()
     try:
         _set_l2(ctx, path)
-        ctx.set_option("l2_float_mfma", 0)   # auto mode: the fused kernel whatever kind of data this context saw last (the hint word)
-        ctx.set_option("l2_fold_counts", 0)
-        _match(ctx, dq, dt, 1)
-        off = ctx.last_l2_match()
-        ctx.set_option("l2_fold_counts", 1)
-        _match(ctx, dq, dt, 1)
-        on = ctx.last_l2_match()
+        with options(ctx, l2_float_mfma=0, l2_fold_counts=0):   # auto mode: the fused kernel whatever kind of data this context saw last (the hint word)
+            _match(ctx, dq, dt, 1)
+            off = ctx.last_l2_match()
+        with options(ctx, l2_float_mfma=0, l2_fold_counts=1):
+            _match(ctx, dq, dt, 1)
+            on = ctx.last_l2_match()
     finally:
         _set_l2(ctx, 0)
-        ctx.set_option("l2_float_mfma", 1)
-        ctx.set_option("l2_fold_counts", 1)
     assert on[0] == off[0] == {0: 3, 1: 1, 2: 2}[path]
     assert on[1] == off[1] >= 1
     assert off[2] == 0 and on[2] == 1
@@ -257,8 +252,7 @@ def test_matches_equal_the_oracle_bit_for_bit(ctx, oracle, fold):
     td[450:] = td[:450]             # every train row twice: d0 == d1 for every query whose neighbour is exact, the smaller row first
     qd[:100] = td[:100]
     sets.append(("duplicates", qd, td))
-    ctx.set_option("l2_fold_counts", fold)
-    try:
+    with options(ctx, l2_fold_counts=fold):
         for name, q, t in sets:
             dq, dt = torch.from_numpy(np.ascontiguousarray(q[None])).cuda(), torch.from_numpy(np.ascontiguousarray(t[None])).cuda()
             for rep in range(2):    # (auto mode: the second call on non-integer data takes the fp16 path)
@@ -270,8 +264,6 @@ def test_matches_equal_the_oracle_bit_for_bit(ctx, oracle, fold):
                 assert (idx[:100, 0] == np.arange(100)).all() and (idx[:100, 1] == np.arange(100) + 450).all()
             if name == "golden128":
                 assert np.array_equal(np.sort(mo["queryIdx"]), np.sort(g["sift128_match_q"]))
-    finally:
-        ctx.set_option("l2_fold_counts", 1)
 
 
 def test_batch_of_64_c4_pairs_against_the_oracle_on_four_of_them(ctx, oracle):

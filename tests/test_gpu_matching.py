@@ -222,15 +222,14 @@ def test_l2_matrix_core_many_groups_per_split_and_extreme_values(ctx, oracle, nq
     sub = np.unique(np.concatenate([np.arange(0, 8), np.arange(0, nq, max(1, nq // 97)), [nq - 1]]))
     oi, od = oracle.knn_l2sq(q[sub], t)
     assert od[2, 0] == 0.0 and oi[2, 0] == nt // 2 and oi[2, 1] == nt - 1
-    ctx.set_option("l2_mfma_waves", waves)
-    try:
-        for mode in (2, 0):
-            _set_l2(ctx, mode)
-            idx, dist = mpa.knn_l2sq(q, t, ctx=ctx)
-            assert np.array_equal(idx[sub], oi) and dist[sub].tobytes() == od.tobytes(), (mode, waves)
-    finally:
-        _set_l2(ctx, 0)
-        ctx.set_option("l2_mfma_waves", 0)
+    with options(ctx, l2_mfma_waves=waves):
+        try:
+            for mode in (2, 0):
+                _set_l2(ctx, mode)
+                idx, dist = mpa.knn_l2sq(q, t, ctx=ctx)
+                assert np.array_equal(idx[sub], oi) and dist[sub].tobytes() == od.tobytes(), (mode, waves)
+        finally:
+            _set_l2(ctx, 0)
 
 
 @pytest.mark.parametrize("dim", [256, 200, 144])
@@ -383,27 +382,19 @@ HAMMING_VARIANTS = {
     "mfma_fp4_train_pm1": (3, 0, 0), "mfma_fp4_qt2_train_pm1": (3, 2, 0),
 }
 HAMMING_DEFAULT = (3, 0)   # the library default: matrix-core kernel, automatic query tiles per wave
-HAMMING_TRAIN01_DEFAULT = None   # the library's default encoding of the train operand (1 = {0, +1}; 0 = +-1): read from the context
 
 
-def _set_hamming(ctx, cfg):
-    ctx.set_option("hamming_variant", cfg[0])
-    ctx.set_option("hamming_mfma_qt", cfg[1])
-    global HAMMING_TRAIN01_DEFAULT
-    if HAMMING_TRAIN01_DEFAULT is None:   # the library's default encoding of the train operand, read before the first change
-        HAMMING_TRAIN01_DEFAULT = ctx.get_option("hamming_train01")
-    ctx.set_option("hamming_train01", cfg[2] if len(cfg) > 2 else HAMMING_TRAIN01_DEFAULT)
+def _hamming(cfg):
+    """The settings of a HAMMING_VARIANTS entry for options(): a pair leaves the train operand's encoding at the library default."""
+    return dict(zip(("hamming_variant", "hamming_mfma_qt", "hamming_train01"), cfg))
 
 
 @pytest.mark.parametrize("variant", sorted(HAMMING_VARIANTS))
 def test_hamming_every_kernel_variant_bit_exact(ctx, oracle, variant):
     """Every selectable Hamming kernel gives the oracle's (distance, index) pairs bit for bit: shapes around the tile sizes
     (32-row MFMA tiles, 128-row LDS tiles), descriptor widths around the K-step (8 bytes), ties, ragged last tiles, k = 1."""
-    _set_hamming(ctx, HAMMING_VARIANTS[variant])
-    try:
+    with options(ctx, **_hamming(HAMMING_VARIANTS[variant])):
         check_hamming_cases(ctx, oracle, variant)
-    finally:
-        _set_hamming(ctx, HAMMING_DEFAULT)
 
 
 _C2 = {}
@@ -431,12 +422,9 @@ C2_INSTANCES = {
 def test_c2_full_size_matrix_core_equals_valu(ctx, oracle, variant):
     """BASELINE C2 (8192 x 8192 x 256 bit): the matrix-core kernel against the VALU kernel and against the oracle on EVERY row."""
     q, t, (oi, od) = _c2_oracle(oracle)
-    with options(ctx):
-        _set_hamming(ctx, HAMMING_VARIANTS["valu_lds_tiled"])
+    with options(ctx, **_hamming(HAMMING_VARIANTS["valu_lds_tiled"])):
         idx0, dist0 = mpa.knn_hamming(q, t, ctx=ctx)
-    with options(ctx, **(C2_INSTANCES[variant][0] if variant in C2_INSTANCES else {})):
-        if variant not in C2_INSTANCES:
-            _set_hamming(ctx, HAMMING_VARIANTS[variant])
+    with options(ctx, **(C2_INSTANCES[variant][0] if variant in C2_INSTANCES else _hamming(HAMMING_VARIANTS[variant]))):
         idx3, dist3 = mpa.knn_hamming(q, t, ctx=ctx)
         if variant in C2_INSTANCES:
             rec = ctx.last_kernels()
@@ -450,11 +438,8 @@ def test_hamming_many_splits_large_train_set(ctx, oracle, variant):
     """Train sets far beyond one split (the matrix-core kernel caps a split at 4096 rows, i.e. 18 splits here, the last one
     ragged) and a query count that is not a multiple of anything; checked on a sample of queries against the oracle."""
     q, t = synth.orb_pair(3001, 70001, seed=77)
-    _set_hamming(ctx, HAMMING_VARIANTS[variant])
-    try:
+    with options(ctx, **_hamming(HAMMING_VARIANTS[variant])):
         idx, dist = mpa.knn_hamming(q, t, ctx=ctx)
-    finally:
-        _set_hamming(ctx, HAMMING_DEFAULT)
     rows = np.random.default_rng(5).choice(3001, 48, replace=False)
     oi, od = oracle.knn_hamming(q[rows], t)
     assert np.array_equal(idx[rows], oi) and np.array_equal(dist[rows], od)
@@ -480,8 +465,8 @@ def test_hamming_property_random_shapes_and_ties(ctx, oracle):
         oi, od = oracle.knn_hamming(q, t, k=k)
         assert np.array_equal(dist, od) and np.array_equal(idx, oi), (nq, nt, nbytes, k, alphabet, seed)
 
-    _set_hamming(ctx, HAMMING_DEFAULT)
-    check()
+    with options(ctx, **_hamming(HAMMING_DEFAULT)):
+        check()
 
 
 def test_hamming_fused_epilogue_survives_a_dynamic_split_call_between_two_fused_calls(ctx, oracle):
@@ -490,15 +475,12 @@ def test_hamming_fused_epilogue_survives_a_dynamic_split_call_between_two_fused_
     all three return the oracle's pairs."""
     q, t = synth.orb_pair(2048, 6000, seed=4242)     # 64 query tiles: several train splits on 256 CUs
     oi, od = oracle.knn_hamming(q[::16], t)
-    try:
-        for lds in (1, 2, 1, 2, 1):
-            ctx.set_option("hamming_mfma_lds", lds)
+    for lds in (1, 2, 1, 2, 1):
+        with options(ctx, hamming_mfma_lds=lds):
             idx, dist = mpa.knn_hamming(q, t, ctx=ctx)
             assert np.array_equal(idx[::16], oi) and np.array_equal(dist[::16], od), lds
             err, m = mpa.getMatches([None] * 2048, [None] * 6000, q, t, matcher_name="LINEAR", ctx=ctx)
             assert err == 0 and np.array_equal(m["trainIdx"], idx[m["queryIdx"], 0])
-    finally:
-        ctx.set_option("hamming_mfma_lds", 1)
 
 
 @pytest.mark.parametrize("nq,nt,nbytes,B", [(8192, 8192, 32, 1), (1000, 5000, 32, 1), (100, 3000, 32, 1), (1, 40, 32, 1), (8191, 8200, 32, 1), (3000, 4000, 16, 1),
@@ -514,9 +496,8 @@ def test_matches_emitted_by_the_merge_kernel(ctx, oracle, nq, nt, nbytes, B):
     qs, ts = zip(*[synth.orb_pair(nq, nt, nbytes=nbytes, seed=7000 + nq + nt + b) for b in range(B)])
     q, t = torch.from_numpy(np.stack(qs)).cuda(), torch.from_numpy(np.stack(ts)).cuda()
     outs = {}
-    try:
-        for emit in (1, 0, 1):
-            ctx.set_option("hamming_merge_emit", emit)
+    for emit in (1, 0, 1):
+        with options(ctx, hamming_merge_emit=emit):
             for rep in range(3):
                 o = match_hamming_device(q, t, ctx=ctx)
                 torch.cuda.synchronize()
@@ -526,8 +507,6 @@ def test_matches_emitted_by_the_merge_kernel(ctx, oracle, nq, nt, nbytes, B):
                     outs[emit] = (cur, rows)
                 else:
                     assert all(np.array_equal(a, c) for a, c in zip(outs[emit][0], cur)) and all(np.array_equal(a, c) for a, c in zip(outs[emit][1], rows))
-    finally:
-        ctx.set_option("hamming_merge_emit", 0)
     assert all(np.array_equal(a, c) for a, c in zip(outs[1][0], outs[0][0])) and all(np.array_equal(a, c) for a, c in zip(outs[1][1], outs[0][1]))
     for b in range(B):
         oi, od = oracle.knn_hamming(qs[b], ts[b])
@@ -570,14 +549,11 @@ def test_hamming_one_split_of_8192_rows_is_exact(ctx, oracle):
     ts[3][0], ts[3][n - 1] = flipped(3, 7), flipped(3, 8)
     dq, dt = torch.from_numpy(np.stack(qs)).cuda(), torch.from_numpy(np.stack(ts)).cuda()
     res = {}
-    try:
-        for cap in (8192, 4096):
-            ctx.set_option("hamming_split_rows", cap)
+    for cap in (8192, 4096):
+        with options(ctx, hamming_split_rows=cap):
             out = match_hamming_device(dq, dt, ctx=ctx)
             torch.cuda.synchronize()
             res[cap] = (out["idx"].cpu().numpy().copy(), out["dist"].cpu().numpy().copy(), out["count"].cpu().numpy().copy())
-    finally:
-        ctx.set_option("hamming_split_rows", 0)
     for a, b in zip(res[8192], res[4096]):
         assert np.array_equal(a, b)
     idx, dist, _ = res[8192]
@@ -607,18 +583,11 @@ def test_hamming_long_splits_other_descriptor_widths(ctx, nbytes):
     t[3, :] = t[3, 0]                      # one pair with every train row equal: (0, 1) everywhere
     dq, dt = torch.from_numpy(np.ascontiguousarray(q)).cuda(), torch.from_numpy(np.ascontiguousarray(t)).cuda()
     res = {}
-    try:
-        for name, variant, cap in (("valu", 0, 0), ("mfma", 3, 0), ("mfma4096", 3, 4096)):
-            ctx.set_option("hamming_variant", variant)
-            ctx.set_option("hamming_split_rows", cap)
-            ctx.set_option("hamming_mfma_blocks_per_cu", 1)
+    for name, variant, cap in (("valu", 0, 0), ("mfma", 3, 0), ("mfma4096", 3, 4096)):
+        with options(ctx, hamming_variant=variant, hamming_split_rows=cap, hamming_mfma_blocks_per_cu=1):
             out = match_hamming_device(dq, dt, ctx=ctx)
             torch.cuda.synchronize()
             res[name] = [out[k].cpu().numpy().copy() for k in ("idx", "dist", "count")]
-    finally:
-        ctx.set_option("hamming_variant", 3)
-        ctx.set_option("hamming_split_rows", 0)
-        ctx.set_option("hamming_mfma_blocks_per_cu", 3)   # the library default
     for name in ("mfma", "mfma4096"):
         for a, b in zip(res["valu"], res[name]):
             assert np.array_equal(a, b), (name, nbytes)

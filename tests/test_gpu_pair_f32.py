@@ -8,6 +8,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from option_guard import options
+
 pytestmark = pytest.mark.gpu
 
 TH = lambda K: 0.8 * 4.0 / (np.sqrt(2.0) * (2 * K[0] + 2 * K[1]))  # noqa: E731   (stereo_pose_refinement.h:280-286)
@@ -146,14 +148,10 @@ def test_usac_batch_equals_the_single_problem_entries_and_does_not_depend_on_the
     seeds = [300 + 7 * i for i in range(B)]
     kw = dict(estimator=2, refine=refine, sprt_ms=6.0, sprt_tm=2736.0)
     rec, raw = batch.process_pairs_batched_usac(ctx, *stk, K, K, seeds, prosac=prosac, **kw)
-    ctx.set_option("hub_cohort", 8)
-    try:
+    with options(ctx, hub_cohort=8):
         fed = batch.process_pairs_batched_usac(ctx, *stk, K, K, seeds, prosac=prosac, **kw)[1]
-        ctx.set_option("pair_batch_feed", 0)
-        unfed = batch.process_pairs_batched_usac(ctx, *stk, K, K, seeds, prosac=prosac, **kw)[1]
-    finally:
-        ctx.set_option("hub_cohort", 0)
-        ctx.set_option("pair_batch_feed", 1)
+        with options(ctx, pair_batch_feed=0):
+            unfed = batch.process_pairs_batched_usac(ctx, *stk, K, K, seeds, prosac=prosac, **kw)[1]
     assert fed.tobytes() == unfed.tobytes() == raw.tobytes()
     for i in range(B):
         cnt, mm, d1, d2 = _match_and_gather(ctx, stk[0][i], stk[1][i], stk[2][i], stk[3][i], K)
@@ -185,15 +183,11 @@ def test_arrsac_batch_equals_the_single_problem_entries_and_does_not_depend_on_t
     states = np.array([[0xFFFFFFFF + 11 * b, 0xFFFFFFFF + 5 * b] for b in range(B)], np.uint64)
     st_batch = states.copy()
     rec, raw = batch.process_pairs_batched_arrsac(ctx, *stk, K, K, refine=True, rng_states=st_batch)
-    ctx.set_option("hub_cohort", 8)
-    try:
+    with options(ctx, hub_cohort=8):
         st2, st3 = states.copy(), states.copy()
         fed = batch.process_pairs_batched_arrsac(ctx, *stk, K, K, refine=True, rng_states=st2)[1]
-        ctx.set_option("pair_batch_feed", 0)
-        unfed = batch.process_pairs_batched_arrsac(ctx, *stk, K, K, refine=True, rng_states=st3)[1]
-    finally:
-        ctx.set_option("hub_cohort", 0)
-        ctx.set_option("pair_batch_feed", 1)
+        with options(ctx, pair_batch_feed=0):
+            unfed = batch.process_pairs_batched_arrsac(ctx, *stk, K, K, refine=True, rng_states=st3)[1]
     assert fed.tobytes() == unfed.tobytes() == raw.tobytes() and np.array_equal(st2, st_batch) and np.array_equal(st3, st_batch)
     for i in range(B):
         cnt, mm, d1, d2 = _match_and_gather(ctx, stk[0][i], stk[1][i], stk[2][i], stk[3][i], K)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from matchinglib_poselib_amd import pose, synth
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -57,16 +58,13 @@ def test_plain_root_path_ab_over_the_same_seeds(ctx, oracle):
     """A/B, solver_polish = 0 (the plain elimination + root path): the same 126 runs are identical to the CPU path's as well -- the safeguard
     decides nothing at the level of a RANSAC run on these seeds; what it does decide is measured per model (tools/polish_default_ab.py,
     tests/test_gpu_baseline_configs.py)."""
-    ctx.set_option("solver_polish", 0)
-    try:
+    with options(ctx, solver_polish=0):
         for n, scene_seed, seed in CASES:
             p1, p2, R, t, truth, th = synth.pose_scene(n, 0.5, seed=scene_seed)
             o = oracle.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, lesqu=False, seed=seed)
             g = pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, refit=False, seed=seed, ctx=ctx)
             assert g["iters"] == o["iters"] and g["n_inliers"] == o["n_inliers"] and np.array_equal(g["mask"], o["mask"]), (n, scene_seed, seed)
             assert e_dist(g["E"], o["E"]) < 1e-7
-    finally:
-        ctx.set_option("solver_polish", 1)
 
 
 def test_refit_mask_flips_are_correspondences_at_the_threshold(ctx, oracle):

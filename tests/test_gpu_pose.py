@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from matchinglib_poselib_amd import pose, synth
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -145,19 +146,17 @@ def test_estimate_relative_pose_end_to_end(ctx):
 def test_ransac_multi_chunk_replay(ctx, oracle):
     """max_iters above the per-pass capacity: the replay state (best model, niters, iteration count) is carried across
     device passes.  A small pass size forces many passes; results must not depend on it."""
-    from matchinglib_poselib_amd import _lib
     p1, p2, R, t, mask, th = synth.pose_scene(1500, seed=41)
     o = oracle.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, lesqu=True, seed=9)
     o1 = oracle.ransac_essential(p1, p2, th, confidence=1.0, max_iters=700, lesqu=False, seed=10)
     for chunk in (64, 100, 0):
-        _lib.check(ctx.lib.mlpl_set_option(ctx.handle, b"ransac_chunk", chunk), "set_option")
-        g = pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, refit=True, seed=9, ctx=ctx)
-        assert g["iters"] == o["iters"] and g["n_inliers"] == o["n_inliers"], chunk
-        assert e_dist(g["E"], o["E"]) < 1e-7
-        g1 = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=700, refit=False, seed=10, ctx=ctx)
-        assert g1["iters"] == 700 and g1["n_inliers"] == o1["n_inliers"] and e_dist(g1["E"], o1["E"]) < 1e-8
-        assert np.array_equal(g1["mask"], o1["mask"])
-    _lib.check(ctx.lib.mlpl_set_option(ctx.handle, b"ransac_chunk", 0), "set_option")
+        with options(ctx, ransac_chunk=chunk):
+            g = pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, refit=True, seed=9, ctx=ctx)
+            assert g["iters"] == o["iters"] and g["n_inliers"] == o["n_inliers"], chunk
+            assert e_dist(g["E"], o["E"]) < 1e-7
+            g1 = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=700, refit=False, seed=10, ctx=ctx)
+            assert g1["iters"] == 700 and g1["n_inliers"] == o1["n_inliers"] and e_dist(g1["E"], o1["E"]) < 1e-8
+            assert np.array_equal(g1["mask"], o1["mask"])
 
 
 def test_large_shapes_sampled(ctx, oracle):
@@ -286,11 +285,8 @@ def test_ransac_device_iteration_bounds_equal_host_table(ctx, oracle, n):
     """The adaptive iteration bound is evaluated on the device and verified by the host; forcing the host table must give the
     same iteration count, model and mask -- and both equal the oracle (varying n: the table would be rebuilt per call)."""
     p1, p2, R, t, mask, th = synth.pose_scene(n, seed=500 + n)
-    ctx.set_option("ransac_host_table", 1)
-    try:
+    with options(ctx, ransac_host_table=1):
         a = pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, refit=False, seed=n, ctx=ctx)
-    finally:
-        ctx.set_option("ransac_host_table", 0)
     b = pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, refit=False, seed=n, ctx=ctx)
     o = oracle.ransac_essential(p1, p2, th, confidence=0.999, max_iters=1000, lesqu=False, seed=n)
     assert a["iters"] == b["iters"] == o["iters"] and a["n_inliers"] == b["n_inliers"] == o["n_inliers"]
@@ -345,11 +341,8 @@ def test_fp32_prefilter_counts_at_every_scale(ctx, oracle, scale, escale):
         want = (ref_err <= t2).sum(axis=1)
         got = {}
         for f in (1, 0):
-            ctx.set_option("ransac_f32_filter", f)
-            try:
+            with options(ctx, ransac_f32_filter=f):
                 got[f] = pose.count_models(q1, q2, Es, t2, shape=1, ctx=ctx)
-            finally:
-                ctx.set_option("ransac_f32_filter", 1)
         assert np.array_equal(got[1], got[0]), (scale, escale, frac, np.nonzero(got[1] != got[0])[0][:5])
         assert np.array_equal(got[1], want), (scale, escale, frac, got[1][:5], want[:5])
 
@@ -376,11 +369,8 @@ def test_count_kernel_deferred_queue_equals_inline_and_the_cpu(ctx, oracle, scal
             want = (ref_err <= t2).sum(axis=1)
             got = {}
             for d in (1, 0):
-                ctx.set_option("ransac_count_defer", d)
-                try:
+                with options(ctx, ransac_count_defer=d):
                     got[d] = pose.count_models(q1, q2, Es, t2, shape=1, ctx=ctx)
-                finally:
-                    ctx.set_option("ransac_count_defer", 1)
             assert np.array_equal(got[1], got[0]), (scale, escale, nm, t2)
             assert np.array_equal(got[1], want), (scale, escale, nm, t2, got[1][:5], want[:5])
 
@@ -390,13 +380,8 @@ def test_ransac_with_and_without_the_fp32_prefilter(ctx, oracle, seed):
     p1, p2, R, t, mask, th = synth.pose_scene(4000, inlier_frac=0.35, seed=900 + seed)
     runs = []
     for f, d in ((1, 1), (0, 1), (1, 0)):   # packed-fp32 filter with the deferred queue (default), pure fp64, filter with the inline fp64 path
-        ctx.set_option("ransac_f32_filter", f)
-        ctx.set_option("ransac_count_defer", d)
-        try:
+        with options(ctx, ransac_f32_filter=f, ransac_count_defer=d):
             runs.append(pose.ransac_essential(p1, p2, th, confidence=0.999, max_iters=6000, refit=False, seed=seed, ctx=ctx))
-        finally:
-            ctx.set_option("ransac_f32_filter", 1)
-            ctx.set_option("ransac_count_defer", 1)
     a, b, c = runs
     assert a["iters"] == c["iters"] and a["n_inliers"] == c["n_inliers"] and np.array_equal(a["E"], c["E"]) and np.array_equal(a["mask"], c["mask"])
     assert a["iters"] == b["iters"] and a["n_inliers"] == b["n_inliers"] and np.array_equal(a["E"], b["E"]) and np.array_equal(a["mask"], b["mask"])
@@ -410,21 +395,17 @@ def test_ransac_lazy_error_sums_equal_full_sums(ctx, oracle, n, chunk):
     iteration count, model, mask as with sums for every model, for adaptive and exhaustive runs, tiny n (ties on the inlier
     count everywhere) and multi-pass replays."""
     p1, p2, R, t, mask, th = synth.pose_scene(n, seed=900 + n)
-    ctx.set_option("ransac_chunk", chunk)
-    try:
+    with options(ctx, ransac_chunk=chunk):
         for conf, iters, seed in ((0.999, 1000, 3), (1.0, 700, 4), (0.99, 300, 5)):
-            ctx.set_option("ransac_lazy_sums", 0)
-            a = pose.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, refit=True, seed=seed, ctx=ctx)
-            ctx.set_option("ransac_lazy_sums", 1)
-            b = pose.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, refit=True, seed=seed, ctx=ctx)
+            with options(ctx, ransac_lazy_sums=0):
+                a = pose.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, refit=True, seed=seed, ctx=ctx)
+            with options(ctx, ransac_lazy_sums=1):
+                b = pose.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, refit=True, seed=seed, ctx=ctx)
             assert a["ok"] == b["ok"] and a["iters"] == b["iters"] and a["n_inliers"] == b["n_inliers"], (n, conf)
             assert np.array_equal(a["E"], b["E"]) and np.array_equal(a["mask"], b["mask"])
             o = oracle.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, lesqu=False, seed=seed)
             c = pose.ransac_essential(p1, p2, th, confidence=conf, max_iters=iters, refit=False, seed=seed, ctx=ctx)
             assert c["iters"] == o["iters"] and c["n_inliers"] == o["n_inliers"] and np.array_equal(c["mask"], o["mask"])
-    finally:
-        ctx.set_option("ransac_lazy_sums", 1)
-        ctx.set_option("ransac_chunk", 0)
 
 
 def test_ransac_random_small_scenes_vs_oracle(ctx, oracle):

@@ -4,6 +4,8 @@ whole RANSAC runs.  Reference arithmetic: five-point.cpp:366-471."""
 import numpy as np
 import pytest
 
+from option_guard import options
+
 pytestmark = pytest.mark.gpu
 
 
@@ -11,21 +13,14 @@ pytestmark = pytest.mark.gpu
 def ctx():
     import matchinglib_poselib_amd as mpa
 
-    c = mpa.Context(0)
-    yield c
-    c.set_option("solver_wave3", 1)
+    return mpa.Context(0)
 
 
 def _models(ctx, p1, p2, samples, wave3, polish):
     from matchinglib_poselib_amd import pose
 
-    ctx.set_option("solver_wave3", wave3)
-    ctx.set_option("solver_polish", polish)
-    try:
+    with options(ctx, solver_wave3=wave3, solver_polish=polish):
         return pose.solve_5pt(p1, p2, samples, ctx=ctx)
-    finally:
-        ctx.set_option("solver_wave3", 1)
-        ctx.set_option("solver_polish", 1)
 
 
 @pytest.mark.parametrize("n_samples", [1, 2, 3, 4, 5, 7, 64, 1000, 4099])
@@ -68,9 +63,8 @@ def test_ransac_runs_bit_identical(ctx, refit):
         p1, p2, R, t, mask, th = synth.pose_scene(n, inlier_frac=frac, seed=seed)
         out = []
         for w3 in (0, 1):
-            ctx.set_option("solver_wave3", w3)
-            out.append(pose.ransac_essential(p1, p2, th, confidence=0.999 if iters == 1000 else 1.0, max_iters=iters, refit=refit, seed=seed, ctx=ctx))
-        ctx.set_option("solver_wave3", 1)
+            with options(ctx, solver_wave3=w3):
+                out.append(pose.ransac_essential(p1, p2, th, confidence=0.999 if iters == 1000 else 1.0, max_iters=iters, refit=refit, seed=seed, ctx=ctx))
         a, b = out
         assert a["iters"] == b["iters"] and a["n_inliers"] == b["n_inliers"]
         assert np.array_equal(a["mask"], b["mask"])
@@ -93,13 +87,10 @@ def test_device_drawn_samples_equal_the_host_drawn(ctx, n, frac, iters):
     p1, p2, R, t, mask, th = synth.pose_scene(n, inlier_frac=frac, seed=3 * n + 1)
     out = []
     for dd in (0, 1):
-        ctx.set_option("ransac_device_draw", dd)
-        try:
+        with options(ctx, ransac_device_draw=dd):
             f0, _ = _draw_stats(ctx)
             r = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=iters, refit=False, seed=77 + n, ctx=ctx)
             f1, used = _draw_stats(ctx)
-        finally:
-            ctx.set_option("ransac_device_draw", 1)
         eligible = min(iters, 32768) * 60.0 / n < 3072      # few enough redrawing samples for the candidate list (else the host draws)
         assert used == (dd if eligible else 0) and f1 == f0, (dd, used, f0, f1)     # the device path ran (and did not fall back) exactly when asked
         out.append(r)
@@ -115,17 +106,14 @@ def test_device_drawing_falls_back_when_samples_redraw_too_often(ctx):
     p1, p2, R, t, mask, th = synth.pose_scene(3000, inlier_frac=0.5, seed=5)
     ref = {}
     for seed in (1, 2, 1):
-        ctx.set_option("ransac_device_draw", 0)
-        h = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=6000, refit=False, seed=seed, ctx=ctx)
-        ctx.set_option("ransac_device_draw", 1)
-        d = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=6000, refit=False, seed=seed, ctx=ctx)
+        with options(ctx, ransac_device_draw=0):
+            h = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=6000, refit=False, seed=seed, ctx=ctx)
+        with options(ctx, ransac_device_draw=1):
+            d = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=6000, refit=False, seed=seed, ctx=ctx)
         assert _draw_stats(ctx)[1] == 1
         assert h["n_inliers"] == d["n_inliers"] and np.array_equal(h["mask"], d["mask"])
         ref.setdefault(seed, d["n_inliers"])
         assert ref[seed] == d["n_inliers"]
-    ctx.set_option("rand_cache_max", 20000)   # fewer values than 6000 samples need: the call is not eligible
-    try:
+    with options(ctx, rand_cache_max=20000):   # fewer values than 6000 samples need: the call is not eligible
         d = pose.ransac_essential(p1, p2, th, confidence=1.0, max_iters=6000, refit=False, seed=1, ctx=ctx)
         assert _draw_stats(ctx)[1] == 0 and d["n_inliers"] == ref[1]
-    finally:
-        ctx.set_option("rand_cache_max", 0)

@@ -8,6 +8,8 @@ import sys
 import numpy as np
 import pytest
 
+from option_guard import options
+
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
 import make_golden  # noqa: E402
@@ -27,13 +29,10 @@ def dev_run(ctx):
 def test_device_follows_the_reference_built_traces(ctx, stepwise):
     """The fixture of the REFERENCE's USAC.h compiled in place, held directly against the device path (32 runs, 8 scenes x uniform / PROSAC
     x 2 seeds); stepwise = 1 takes every local-optimisation step through the resume path."""
-    ctx.set_option("usac_lo_stepwise", stepwise)
-    try:
+    with options(ctx, usac_lo_stepwise=stepwise):
         for g, k, n, frac, seed, prosac, usac_seed, agree in fixture_cases():
             if agree:
                 check_against_fixture(dev_run(ctx), g, k, n, frac, seed, prosac, usac_seed, e5_max=1e-4)
-    finally:
-        ctx.set_option("usac_lo_stepwise", 0)
 
 
 def test_device_follows_the_reference_running_its_default_stewenius_solver(ctx):
@@ -62,12 +61,9 @@ def test_sequential_test_finished_on_bounds_takes_the_same_decisions(ctx):
             si = sc["order"] if prosac else None
             runs = []
             for fast in (1, 0):
-                ctx.set_option("usac_sprt_fast", fast)
-                try:
+                with options(ctx, usac_sprt_fast=fast):
                     runs.append(pose.usac_essential(sc["p1"], sc["p2"], sc["th"], 31337, sorted_idx=si, event_cap=120000, max_hyp=4000,
                                                     check_degeneracy=chk, ctx=ctx))
-                finally:
-                    ctx.set_option("usac_sprt_fast", 1)
             a, b = runs
             assert a["n_events"] == b["n_events"] and np.array_equal(a["events"], b["events"]), sc["name"]
             assert np.array_equal(a["final"], b["final"]) and np.array_equal(a["flags"], b["flags"]) and np.array_equal(a["E"], b["E"])
@@ -187,8 +183,7 @@ def test_device_follows_the_reference_with_the_five_point_refinements(ctx, refin
     decisions event by event, refined models to 1e-8.  stepwise = 1: every step of a local-optimisation chain through the resume path."""
     from matchinglib_poselib_amd import pose
 
-    ctx.set_option("usac_lo_stepwise", stepwise)
-    try:
+    with options(ctx, usac_lo_stepwise=stepwise):
         run = stewenius_run(lambda *a, **k: pose.usac_essential(*a, estimator=2 if refine in (4, 5) else 0, refine=refine, ctx=ctx, **k))
         checked = 0
         for g, k, n, frac, seed, prosac, usac_seed, agree, rf in refine_fixture_cases():
@@ -196,8 +191,6 @@ def test_device_follows_the_reference_with_the_five_point_refinements(ctx, refin
                 check_against_fixture(run, g, k, n, frac, seed, prosac, usac_seed, e5_max=5e-3, kept=make_golden.USAC_REFINE_EVENTS_KEPT)
                 checked += 1
         assert checked >= 12
-    finally:
-        ctx.set_option("usac_lo_stepwise", 0)
 
 
 @pytest.mark.parametrize("refine", [5, 7, 4, 6])

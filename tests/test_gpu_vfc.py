@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import vfc_oracle as VO
+from option_guard import options
 
 pytestmark = pytest.mark.gpu
 
@@ -119,19 +120,13 @@ def test_seed_moves_the_control_points_only(ctx):
 
 
 def test_store_u_instance_gives_the_same_bits(ctx):
-    from matchinglib_poselib_amd import _lib, synth
-    import ctypes as C
+    from matchinglib_poselib_amd import synth
 
     s = synth.vfc_scene("graded", 1025, 2)
-    old = C.c_int(0)
-    _lib.check(ctx.lib.mlpl_get_option(ctx.handle, b"vfc_store_u", C.byref(old)), "get")
-    try:
-        res = []
-        for v in (0, 1):
-            _lib.check(ctx.lib.mlpl_set_option(ctx.handle, b"vfc_store_u", v), "set")
+    res = []
+    for v in (0, 1):
+        with options(ctx, vfc_store_u=v):
             res.append(single(ctx, s["x1"], s["x2"]))
-    finally:
-        _lib.check(ctx.lib.mlpl_set_option(ctx.handle, b"vfc_store_u", old.value), "set")
     assert res[0]["P"].tobytes() == res[1]["P"].tobytes() and res[0]["keep"].tobytes() == res[1]["keep"].tobytes()
     assert res[0]["iterations"] == res[1]["iterations"]
 

@@ -1,9 +1,15 @@
 // ba_common.h -- what the bundle-adjustment kernels share (bundle_adjust.hip: the stereo pair; bundle_adjust_multicam.hip: m cameras): the
 // quaternion algebra and projection of BA_driver.cpp / imgproj.c, the pseudo-Huber residual, the Jacobian blocks of one point in one frame,
-// the fixed-order workgroup reductions and the wrapper's helpers of pose_helper.cpp.  tests/ba_oracle.py is the float64 restatement all of it
-// follows operation by operation.
+// the fixed-order workgroup reductions, the Levenberg-Marquardt core (the slots of the per-point state both kernels use, the damped inverse
+// of V*_i with the reference's quirk, the repair after a V*_i that cannot be inverted, the point update, the optimiser's state with every
+// stop and the mu / nu rules), the wrapper's helpers of pose_helper.cpp and the host entries' batch checks.  tests/ba_oracle.py is the float64
+// restatement all of it follows operation by operation.  The core is device code without a barrier: what the kernels keep is how they gather
+// the Jacobian sums, build and solve S, and commit an accepted step.
 #pragma once
+#include <algorithm>
+#include <cfloat>
 #include <cmath>
+#include <vector>
 
 #include "mlpl_internal.h"
 
@@ -149,6 +155,156 @@ __device__ inline int block_min_int(int x, int *red) {
     return x;
 }
 
+// ---- the per-point state: kernel-independent slots first, the kernel's own (residuals, W) from kPCam on ---------------------------------------------
+constexpr int kPM = 0;     // 2 x 3: the point, current / trial
+constexpr int kPVu = 6;    // 3: V_i (0,1) (0,2) (1,2)
+constexpr int kPVd = 9;    // 3: V_i's working diagonal
+constexpr int kPEb = 12;   // 3
+constexpr int kPInv = 15;  // 2 x 6: (V*_i)^-1 as (00, 01, 02, 11, 12, 22)
+constexpr int kPCam = 27;
+
+// one problem's workspace, structure-of-arrays over the problem's stride: pw(slot, k) is point k's entry
+struct PointWs {
+    double *ws;
+    size_t stride;
+    __device__ double &operator()(int slot, int k) const { return ws[(size_t)slot * stride + k]; }
+};
+
+__device__ inline int inv_diag(int c) { return c == 0 ? 0 : c == 1 ? 3 : 5; }  // where (V*_i)^-1 keeps its diagonal
+
+// (V_i + mu I)^-1 of point k by cofactors, written beside the inverse it may read; false where the determinant is zero or not finite.
+// sba_levmar.c:1341-1355 (restoring V_i's diagonal after a rejected attempt) is compiled out in the reference, and V_i's lower triangle is
+// where it keeps the inverse: after a rejected attempt mu is added onto the DIAGONAL OF THAT ATTEMPT'S INVERSE (vd_from_inv), not onto V_i's.
+__device__ inline bool damped_inverse(const PointWs &pw, int k, bool vd_from_inv, int cur_inv, double mu, double inv[6]) {
+    double d[3];
+    for (int c = 0; c < 3; ++c) d[c] = (vd_from_inv ? pw(kPInv + cur_inv * 6 + inv_diag(c), k) : pw(kPVd + c, k)) + mu;
+    const double vb = pw(kPVu + 0, k), vc = pw(kPVu + 1, k), ve = pw(kPVu + 2, k);
+    const double c00 = d[1] * d[2] - ve * ve, c01 = vc * ve - vb * d[2], c02 = vb * ve - vc * d[1];
+    const double det = d[0] * c00 + vb * c01 + vc * c02;
+    if (!(isfinite(det) && det != 0)) return false;
+    const double idet = 1 / det;
+    inv[0] = c00 * idet, inv[1] = c01 * idet, inv[2] = c02 * idet;
+    inv[3] = (d[0] * d[2] - vc * vc) * idet, inv[4] = (vb * vc - d[0] * ve) * idet, inv[5] = (d[0] * d[1] - vb * vb) * idet;
+    for (int c = 0; c < 6; ++c) pw(kPInv + (cur_inv ^ 1) * 6 + c, k) = inv[c];
+    return true;
+}
+
+// The reference walks the points in order and leaves at the first V*_i it cannot invert: earlier points hold their new inverse's diagonal,
+// the failing one its augmented diagonal, later ones are untouched.  Afterwards the working diagonal lives in kPVd again.
+__device__ inline void repair_first_bad(const PointWs &pw, int n, int first_bad, bool vd_from_inv, int cur_inv, double mu) {
+    for (int k = threadIdx.x; k < n; k += kBaThreads)
+        for (int c = 0; c < 3; ++c) {
+            const double old = vd_from_inv ? pw(kPInv + cur_inv * 6 + inv_diag(c), k) : pw(kPVd + c, k);
+            pw(kPVd + c, k) = k < first_bad ? pw(kPInv + (cur_inv ^ 1) * 6 + inv_diag(c), k) : k == first_bad ? old + mu : old;
+        }
+}
+
+// the accepted attempt's inverse of point k; a caller issues it before it forms r, so that the loads wait behind that work
+__device__ inline void load_inverse(const PointWs &pw, int k, int cur_inv, double inv[6]) {
+    for (int c = 0; c < 6; ++c) inv[c] = pw(kPInv + cur_inv * 6 + c, k);
+}
+
+// db_i = (V*_i)^-1 r with r = eb_i - sum_j W_ij^T da_j from the caller; the trial point Mn beside the current one; ||db||^2 onto s3[0], this
+// point's share of dL onto s3[2]
+__device__ inline void point_update(const PointWs &pw, int k, int cur_m, const double inv[6], const double r[3], const double ebv[3], double mu,
+                                    double Mn[3], double s3[3]) {
+    const double im[3][3] = {{inv[0], inv[1], inv[2]}, {inv[1], inv[3], inv[4]}, {inv[2], inv[4], inv[5]}};
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii) {
+        const double db = im[ii][0] * r[0] + im[ii][1] * r[1] + im[ii][2] * r[2];
+        Mn[ii] = pw(kPM + cur_m * 3 + ii, k) + db;
+        pw(kPM + (cur_m ^ 1) * 3 + ii, k) = Mn[ii];
+        s3[0] += db * db;
+        s3[2] += db * (mu * db + ebv[ii]);
+    }
+}
+
+// ---- the optimiser's state and decisions (sba_levmar.c:449-1400); every value is workgroup-uniform, each lane holds its own copy -------------------
+enum LmVerdict { kLmAccepted, kLmRejected, kLmLeave };
+
+struct LmState {
+    double mu = 0.0, p_eL2 = 0.0, init_p_eL2 = 0.0, eab_inf = 0.0, dp_L2 = DBL_MAX, max_diag = 0.0;
+    int nu = 2, stop = 0, itno = 0, nfev = 1, njev = 0, nlss = 0;
+    bool have_diag = false, failed = false;
+
+    __device__ void start(double cost) {
+        p_eL2 = init_p_eL2 = cost;
+        if (!isfinite(p_eL2)) stop = 7;
+    }
+    // after the gradient sums: false = stop 1; the first mu
+    __device__ bool after_gradient(double mx_e, double mx_d) {
+        const double tau = 1e-3, eps1 = 1e-12;
+        eab_inf = mx_e;
+        max_diag = mx_d, have_diag = true;
+        if (eab_inf <= eps1) {
+            dp_L2 = 0.0;
+            stop = 1;
+            return false;
+        }
+        if (itno == 0) mu = tau * max_diag;
+        return true;
+    }
+    // a trial step: the cameras' part of ||dp||^2 and dL, s3 = ||db||^2, ||e(p + dp)||^2, dL over the points, p_L2 = ||p||^2.  On
+    // kLmAccepted the caller commits the trial; on kLmLeave it leaves the damping loop (stop or failed says why)
+    __device__ LmVerdict verdict(double cam_dp_L2, double cam_dL, const double s3[3], double p_L2) {
+        const double eps2 = 1e-12, eps2_sq = 1e-12 * 1e-12, eps4_sq = 1E-05 * 1E-05;
+        dp_L2 = cam_dp_L2 + s3[0];
+        const double dL = cam_dL + s3[2];
+        const double pdp_eL2 = s3[1];
+        if (dp_L2 <= eps2_sq * p_L2) {
+            stop = 2;
+            return kLmLeave;
+        }
+        if (dp_L2 >= (p_L2 + eps2) / (1E-12 * 1E-12)) {  // "almost singular": the optimiser fails, info stays unwritten
+            failed = true;
+            return kLmLeave;
+        }
+        ++nfev;
+        if (!isfinite(pdp_eL2)) {
+            stop = 7;
+            return kLmLeave;
+        }
+        const double dF = p_eL2 - pdp_eL2;
+        if (!(dL > 0.0 && dF > 0.0)) return kLmRejected;
+        double tmp = 2.0 * dF / dL - 1.0;
+        tmp = 1.0 - tmp * tmp * tmp;
+        mu = mu * ((tmp >= 0.3333333334) ? tmp : 0.3333333334);
+        nu = 2;
+        if (pdp_eL2 - 2.0 * sqrt(p_eL2 * pdp_eL2) < (eps4_sq - 1.0) * p_eL2) stop = 4;
+        p_eL2 = pdp_eL2;
+        return kLmAccepted;
+    }
+    // a rejected or refused attempt: false = stop 6
+    __device__ bool reject() {
+        mu *= nu;
+        if (nu >= (1 << 30)) {  // 2 nu no longer fits an int
+            stop = 6;
+            return false;
+        }
+        nu *= 2;
+        return true;
+    }
+    // the end of an outer step: false = the optimiser failed
+    __device__ bool end_step() {
+        const double eps3_sq = 1e-12 * 1e-12;
+        if (failed) return false;
+        if (p_eL2 <= eps3_sq) stop = 5;
+        return true;
+    }
+    // info as sba writes it; -> sba_ok.  A failed run leaves info unwritten and mu at 0.
+    __device__ bool finish(double info[10]) {
+        if (failed) {
+            mu = 0.0;
+            return false;
+        }
+        if (itno >= kBaMaxIter) stop = 3;
+        info[0] = init_p_eL2, info[1] = p_eL2, info[2] = eab_inf, info[3] = dp_L2;
+        if (have_diag) info[4] = mu / max_diag;
+        info[5] = itno, info[6] = stop, info[7] = nfev, info[8] = njev, info[9] = nlss;
+        return stop != 7;
+    }
+};
+
 // ---- the wrapper's quaternion helpers (P/source/pose_helper.cpp) ---------------------------------------------------------------------------------
 __device__ inline Quat mat_to_quat(const double R[9]) {
     const double tr = R[0] + R[4] + R[8];
@@ -220,6 +376,39 @@ __device__ inline void rt_quality(const Quat &a, const Quat &b, const double ta[
     const double e0 = u[0] - w[0], e1 = u[1] - w[1], e2 = u[2] - w[2];
     tdiff = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
 }
+
+// ---- host: what the batch entries check before they touch the device, and the debug store of mu -----------------------------------------------------
+// have_args: the entry's own pointers and strides; per_problem(b): its further checks of problem b, MLPL_OK to go on
+template <class F>
+int ba_check_batch(const char *who, bool have_args, int B, int stride, const int32_t *counts, F per_problem) {
+    if (!have_args || B < 1 || stride < 1 || !counts) {
+        set_error("%s: bad arguments", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    if (B > 65535) {
+        set_error("%s: at most 65535 problems per call", who);
+        return MLPL_E_BAD_INPUT;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > stride) {
+            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
+            return MLPL_E_BAD_INPUT;
+        }
+        if (int rc = per_problem(b)) return rc;
+    }
+    return MLPL_OK;
+}
+
+// mu at exit of the problems of the calling thread's last call, for the entry's mlpl_debug_*_last_mu
+struct LastMu {
+    std::vector<double> mu;
+    int get(double *out, int max_items) const {
+        if (!out || max_items < 0) return MLPL_E_BAD_INPUT;
+        const int n = std::min<int>((int)mu.size(), max_items);
+        for (int i = 0; i < n; ++i) out[i] = mu[(size_t)i];
+        return n;
+    }
+};
 
 }  // namespace
 }  // namespace mlpl

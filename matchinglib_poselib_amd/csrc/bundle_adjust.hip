@@ -12,15 +12,13 @@
 //
 // Per-point state (kBaSlots doubles per point, structure-of-arrays over the problem's stride): the point and the residual twice (the trial of
 // a damping attempt is written beside the current one and the two swap on acceptance), V_i's strict upper triangle and working diagonal, W_i,
-// eb_i, (V*_i)^-1 twice (a damping attempt reads the previous attempt's inverse: sba_levmar.c:1341-1355 is compiled out, so mu is added onto
-// the DIAGONAL OF THE INVERSE that the previous, rejected attempt left in V_i's lower triangle).  The blocks are kept and not recomputed per
-// pass: the simpler of the two options; recomputing them has not been measured.
-#include <algorithm>
-#include <cfloat>
+// eb_i, (V*_i)^-1 twice (a damping attempt reads the previous attempt's inverse).  The blocks are kept and not recomputed per pass: the simpler
+// of the two options; recomputing them has not been measured.
+//
+// ba_common.h holds what this kernel shares with bundle_adjust_multicam.hip: the geometry, the reductions, and the Levenberg-Marquardt core
+// (the slots up to kPCam, the damped inverse, the first_bad repair, the point update, the optimiser's state and every stop).
 #include <climits>
-#include <cmath>
 #include <cstring>
-#include <vector>
 
 #include "ba_common.h"
 #include "mlpl_internal.h"
@@ -28,15 +26,11 @@
 namespace mlpl {
 namespace {
 
-// slots of the per-point state
-constexpr int kSM = 0;     // 2 x 3: the point, current / trial
-constexpr int kSE = 6;     // 2 x 4: the residual (frame 0 x, y, frame 1 x, y), current / trial
-constexpr int kSVu = 14;   // 3: V_i (0,1) (0,2) (1,2)
-constexpr int kSVd = 17;   // 3: V_i's working diagonal
-constexpr int kSW = 20;    // 18: W_i, 6 x 3 row-major
-constexpr int kSEb = 38;   // 3
-constexpr int kSInv = 41;  // 2 x 6: (V*_i)^-1 as (00, 01, 02, 11, 12, 22)
-constexpr int kBaSlots = 53;
+// this kernel's slots of the per-point state, behind the shared ones
+constexpr int kSE = kPCam;    // 2 x 4: the residual (frame 0 x, y, frame 1 x, y), current / trial
+constexpr int kSW = kSE + 8;  // 18: W_i, 6 x 3 row-major
+constexpr int kBaSlots = kSW + 18;
+static_assert(kBaSlots == 53, "WS_BA is sized by it");
 constexpr int kBaIn = 16;   // per problem: R 9, t 3, th, angle_thresh, t_norm_thresh
 constexpr int kBaOut = 24;  // per problem: R 9, t 3, info 10, mu, accepted
 
@@ -89,9 +83,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
     double *po = out + (size_t)b * kBaOut;
     const size_t row0 = (size_t)b * stride;
     int32_t *idx = idx_all + row0;
-    double *ws = ws_all + row0 * kBaSlots;
-    const size_t S = (size_t)stride;
-#define WSV(slot, k) ws[(size_t)(slot)*S + (k)]
+    const PointWs pw{ws_all + row0 * kBaSlots, (size_t)stride};
 
     // ---- stable compaction of the mask into an ascending list
     int n = 0;
@@ -118,7 +110,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
 
     double info[10];
     for (int k = 0; k < 10; ++k) info[k] = 0.0;
-    double mu = 0.0;
+    LmState lm;
     bool sba_ok = false;
     double v[3] = {0.0, 0.0, 0.0}, t[3] = {t0[0], t0[1], t0[2]};
     int cur_m = 0;
@@ -132,7 +124,6 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
 
     // fewer measurements than unknowns (4 n < 12 + 3 n): the optimiser refuses, as does an empty problem
     if (n >= 12) {
-        const double tau = 1e-3, eps1 = 1e-12, eps2 = 1e-12, eps2_sq = 1e-12 * 1e-12, eps3_sq = 1e-12 * 1e-12, eps4_sq = 1E-05 * 1E-05;
         const double zero3[3] = {0.0, 0.0, 0.0};
         const Quat q_unit{1.0, 0.0, 0.0, 0.0};
         const Quat q_id = quat_mult_fast(local_quat(zero3), q_unit);
@@ -141,44 +132,38 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
 
         // the points into the workspace, the residual at the start
         int cur_e = 0;
-        double p_eL2;
         {
             const Quat q1 = quat_mult_fast(local_quat(v), r0);
             double acc[1] = {0.0};
             for (int k = tid; k < n; k += kBaThreads) {
                 const size_t at = row0 + idx[k];
                 double M[3], e[4];
-                for (int c = 0; c < 3; ++c) WSV(kSM + c, k) = M[c] = Q[at * 3 + c];
+                for (int c = 0; c < 3; ++c) pw(kPM + c, k) = M[c] = Q[at * 3 + c];
                 const double x1[2] = {p1[at * 2], p1[at * 2 + 1]}, x2[2] = {p2[at * 2], p2[at * 2 + 1]};
                 residual2(q_id, zero3, M, x1, th, e);
                 residual2(q1, t, M, x2, th, e + 2);
                 for (int c = 0; c < 4; ++c) {
-                    WSV(kSE + c, k) = e[c];
+                    pw(kSE + c, k) = e[c];
                     acc[0] += e[c] * e[c];
                 }
             }
             block_sum(acc, red);
-            p_eL2 = acc[0];
+            lm.start(acc[0]);
         }
-        const double init_p_eL2 = p_eL2;
-        int nfev = 1, njev = 0, nlss = 0, nu = 2, stop = 0, itno = 0;
-        double eab_inf = 0.0, dp_L2 = DBL_MAX, max_diag = 0.0;
-        bool have_diag = false, failed = false;
-        if (!isfinite(p_eL2)) stop = 7;
 
-        for (; itno < kBaMaxIter && !stop; ++itno) {
+        for (; lm.itno < kBaMaxIter && !lm.stop; ++lm.itno) {
             // ---- Jacobian blocks, V_i, W_i, eb_i; U, ea, ||J^T e||_inf, ||p||^2, the largest diagonal entry
             CamJ cam1;
             cam_setup(r0, v, t, true, cam1);
-            ++njev;
+            ++lm.njev;
             double sums[28];  // U upper 21, ea 6, ||points||^2
 #pragma unroll
             for (int k = 0; k < 28; ++k) sums[k] = 0.0;
             double mx_e = 0.0, mx_d = DBL_MIN;
             for (int k = tid; k < n; k += kBaThreads) {
                 double M[3], e[4], A[2][6], B0[2][3], B1[2][3];
-                for (int c = 0; c < 3; ++c) M[c] = WSV(kSM + cur_m * 3 + c, k);
-                for (int c = 0; c < 4; ++c) e[c] = WSV(kSE + cur_e * 4 + c, k);
+                for (int c = 0; c < 3; ++c) M[c] = pw(kPM + cur_m * 3 + c, k);
+                for (int c = 0; c < 4; ++c) e[c] = pw(kSE + cur_e * 4 + c, k);
                 jac_blocks<false>(cam0, M, A, B0);
                 jac_blocks<true>(cam1, M, A, B1);
                 int s = 0;
@@ -194,20 +179,20 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
                     for (int jj = ii; jj < 3; ++jj) {
                         const double val = (B0[0][ii] * B0[0][jj] + B0[1][ii] * B0[1][jj]) + (B1[0][ii] * B1[0][jj] + B1[1][ii] * B1[1][jj]);
                         if (ii == jj) {
-                            WSV(kSVd + ii, k) = val;
+                            pw(kPVd + ii, k) = val;
                             if (val > mx_d) mx_d = val;
                         } else {
-                            WSV(kSVu + ii + jj - 1, k) = val;
+                            pw(kPVu + ii + jj - 1, k) = val;
                         }
                     }
                     const double ebv = (B0[0][ii] * e[0] + B0[1][ii] * e[1]) + (B1[0][ii] * e[2] + B1[1][ii] * e[3]);
-                    WSV(kSEb + ii, k) = ebv;
+                    pw(kPEb + ii, k) = ebv;
                     mx_e = fmax(mx_e, fabs(ebv));
                 }
 #pragma unroll
                 for (int ii = 0; ii < 6; ++ii)
 #pragma unroll
-                    for (int jj = 0; jj < 3; ++jj) WSV(kSW + ii * 3 + jj, k) = A[0][ii] * B1[0][jj] + A[1][ii] * B1[1][jj];
+                    for (int jj = 0; jj < 3; ++jj) pw(kSW + ii * 3 + jj, k) = A[0][ii] * B1[0][jj] + A[1][ii] * B1[1][jj];
                 sums[27] += M[0] * M[0];
                 sums[27] += M[1] * M[1];
                 sums[27] += M[2] * M[2];
@@ -226,48 +211,32 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
                 mx_e = fmax(mx_e, fabs(ea[ii]));
                 if (U[ii][ii] > mx_d) mx_d = U[ii][ii];
             }
-            eab_inf = mx_e;
             double p_L2 = 0.0;
             for (int k = 0; k < 3; ++k) p_L2 += v[k] * v[k];
             for (int k = 0; k < 3; ++k) p_L2 += t[k] * t[k];
             p_L2 += sums[27];
-            max_diag = mx_d, have_diag = true;
-            if (eab_inf <= eps1) {
-                dp_L2 = 0.0;
-                stop = 1;
-                break;
-            }
-            if (itno == 0) mu = tau * max_diag;
+            if (!lm.after_gradient(mx_e, mx_d)) break;
 
             // ---- the damping loop
             bool vd_from_inv = false;  // V_i's diagonal currently lives in the previous attempt's inverse
             int cur_inv = 0;
             while (true) {
-                for (int i = 0; i < 6; ++i) U[i][i] += mu;
+                for (int i = 0; i < 6; ++i) U[i][i] += lm.mu;
                 double acc[27];  // sum Y W^T upper 21, sum Y eb 6
 #pragma unroll
                 for (int k = 0; k < 27; ++k) acc[k] = 0.0;
                 int first_bad = INT_MAX;
                 for (int k = tid; k < n; k += kBaThreads) {
-                    double d[3], W[6][3], ebv[3];
-                    for (int c = 0; c < 3; ++c)
-                        d[c] = (vd_from_inv ? WSV(kSInv + cur_inv * 6 + (c == 0 ? 0 : c == 1 ? 3 : 5), k) : WSV(kSVd + c, k)) + mu;
-                    const double vb = WSV(kSVu + 0, k), vc = WSV(kSVu + 1, k), ve = WSV(kSVu + 2, k);
-                    const double c00 = d[1] * d[2] - ve * ve, c01 = vc * ve - vb * d[2], c02 = vb * ve - vc * d[1];
-                    const double det = d[0] * c00 + vb * c01 + vc * c02;
-                    if (!(isfinite(det) && det != 0)) {
+                    double inv[6], W[6][3], ebv[3];
+                    if (!damped_inverse(pw, k, vd_from_inv, cur_inv, lm.mu, inv)) {
                         if (k < first_bad) first_bad = k;
                         continue;
                     }
-                    const double idet = 1 / det;
-                    double inv[6] = {c00 * idet, c01 * idet, c02 * idet, (d[0] * d[2] - vc * vc) * idet, (vb * vc - d[0] * ve) * idet,
-                                     (d[0] * d[1] - vb * vb) * idet};
-                    for (int c = 0; c < 6; ++c) WSV(kSInv + (cur_inv ^ 1) * 6 + c, k) = inv[c];
 #pragma unroll
                     for (int ii = 0; ii < 6; ++ii)
 #pragma unroll
-                        for (int jj = 0; jj < 3; ++jj) W[ii][jj] = WSV(kSW + ii * 3 + jj, k);
-                    for (int c = 0; c < 3; ++c) ebv[c] = WSV(kSEb + c, k);
+                        for (int jj = 0; jj < 3; ++jj) W[ii][jj] = pw(kSW + ii * 3 + jj, k);
+                    for (int c = 0; c < 3; ++c) ebv[c] = pw(kPEb + c, k);
                     const double im[3][3] = {{inv[0], inv[1], inv[2]}, {inv[1], inv[3], inv[4]}, {inv[2], inv[4], inv[5]}};
                     double Y[6][3];
 #pragma unroll
@@ -285,14 +254,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
                 first_bad = block_min_int(first_bad, red_i);
                 bool accepted = false;
                 if (first_bad != INT_MAX) {
-                    // the reference walks the points in order and leaves at the first V*_i it cannot invert: earlier points hold their new
-                    // inverse's diagonal, the failing one its augmented diagonal, later ones are untouched
-                    for (int k = tid; k < n; k += kBaThreads)
-                        for (int c = 0; c < 3; ++c) {
-                            const int dslot = c == 0 ? 0 : c == 1 ? 3 : 5;
-                            const double old = vd_from_inv ? WSV(kSInv + cur_inv * 6 + dslot, k) : WSV(kSVd + c, k);
-                            WSV(kSVd + c, k) = k < first_bad ? WSV(kSInv + (cur_inv ^ 1) * 6 + dslot, k) : k == first_bad ? old + mu : old;
-                        }
+                    repair_first_bad(pw, n, first_bad, vd_from_inv, cur_inv, lm.mu);
                     vd_from_inv = false;
                 } else {
                     cur_inv ^= 1, vd_from_inv = true;
@@ -305,7 +267,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
                     }
                     for (int ii = 0; ii < 6; ++ii) E[ii] = ea[ii] - acc[21 + ii];
                     const bool solved = chol_solve6(Sm, E, da);
-                    ++nlss;
+                    ++lm.nlss;
                     if (solved) {
                         // ---- db_i, the trial point, its residual; ||dp||^2, ||e(p + dp)||^2, dL
                         double vn[3], tn[3];
@@ -313,91 +275,46 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
                         const Quat q1 = quat_mult_fast(local_quat(vn), r0);
                         double s3[3] = {0.0, 0.0, 0.0};  // ||db||^2, ||e_new||^2, dL over the points
                         for (int k = tid; k < n; k += kBaThreads) {
-                            double inv[6], ebv[3], r[3], db[3], Mn[3], e[4];
-                            for (int c = 0; c < 6; ++c) inv[c] = WSV(kSInv + cur_inv * 6 + c, k);
-                            const double im[3][3] = {{inv[0], inv[1], inv[2]}, {inv[1], inv[3], inv[4]}, {inv[2], inv[4], inv[5]}};
+                            double inv[6], ebv[3], r[3], Mn[3], e[4];
+                            load_inverse(pw, k, cur_inv, inv);
 #pragma unroll
                             for (int ii = 0; ii < 3; ++ii) {
-                                ebv[ii] = WSV(kSEb + ii, k);
-                                double wt = WSV(kSW + ii, k) * da[0];
+                                ebv[ii] = pw(kPEb + ii, k);
+                                double wt = pw(kSW + ii, k) * da[0];
 #pragma unroll
-                                for (int jj = 1; jj < 6; ++jj) wt = wt + WSV(kSW + jj * 3 + ii, k) * da[jj];
+                                for (int jj = 1; jj < 6; ++jj) wt = wt + pw(kSW + jj * 3 + ii, k) * da[jj];
                                 r[ii] = ebv[ii] - wt;
                             }
-#pragma unroll
-                            for (int ii = 0; ii < 3; ++ii) {
-                                db[ii] = im[ii][0] * r[0] + im[ii][1] * r[1] + im[ii][2] * r[2];
-                                Mn[ii] = WSV(kSM + cur_m * 3 + ii, k) + db[ii];
-                                WSV(kSM + (cur_m ^ 1) * 3 + ii, k) = Mn[ii];
-                                s3[0] += db[ii] * db[ii];
-                                s3[2] += db[ii] * (mu * db[ii] + ebv[ii]);
-                            }
+                            point_update(pw, k, cur_m, inv, r, ebv, lm.mu, Mn, s3);
                             const size_t at = row0 + idx[k];
                             const double x1[2] = {p1[at * 2], p1[at * 2 + 1]}, x2[2] = {p2[at * 2], p2[at * 2 + 1]};
                             residual2(q_id, zero3, Mn, x1, th, e);
                             residual2(q1, tn, Mn, x2, th, e + 2);
                             for (int c = 0; c < 4; ++c) {
-                                WSV(kSE + (cur_e ^ 1) * 4 + c, k) = e[c];
+                                pw(kSE + (cur_e ^ 1) * 4 + c, k) = e[c];
                                 s3[1] += e[c] * e[c];
                             }
                         }
                         block_sum(s3, red);
-                        dp_L2 = 0.0;
-                        double dL = 0.0;
+                        double dp_L2 = 0.0, dL = 0.0;  // the camera's part
                         for (int k = 0; k < 6; ++k) {
                             dp_L2 += da[k] * da[k];
-                            dL += da[k] * (mu * da[k] + ea[k]);
+                            dL += da[k] * (lm.mu * da[k] + ea[k]);
                         }
-                        dp_L2 += s3[0];
-                        dL += s3[2];
-                        const double pdp_eL2 = s3[1];
-                        if (dp_L2 <= eps2_sq * p_L2) {
-                            stop = 2;
-                            break;
-                        }
-                        if (dp_L2 >= (p_L2 + eps2) / (1E-12 * 1E-12)) {  // "almost singular": the optimiser fails, info stays unwritten
-                            failed = true;
-                            break;
-                        }
-                        ++nfev;
-                        if (!isfinite(pdp_eL2)) {
-                            stop = 7;
-                            break;
-                        }
-                        const double dF = p_eL2 - pdp_eL2;
-                        if (dL > 0.0 && dF > 0.0) {
-                            double tmp = 2.0 * dF / dL - 1.0;
-                            tmp = 1.0 - tmp * tmp * tmp;
-                            mu = mu * ((tmp >= 0.3333333334) ? tmp : 0.3333333334);
-                            nu = 2;
-                            if (pdp_eL2 - 2.0 * sqrt(p_eL2 * pdp_eL2) < (eps4_sq - 1.0) * p_eL2) stop = 4;
+                        const LmVerdict verdict = lm.verdict(dp_L2, dL, s3, p_L2);
+                        if (verdict == kLmLeave) break;
+                        if (verdict == kLmAccepted) {
                             for (int k = 0; k < 3; ++k) v[k] = vn[k], t[k] = tn[k];
                             cur_m ^= 1, cur_e ^= 1;
-                            p_eL2 = pdp_eL2;
                             accepted = true;
                         }
                     }
                 }
-                if (accepted) break;
-                mu *= nu;
-                if (nu >= (1 << 30)) {  // 2 nu no longer fits an int
-                    stop = 6;
-                    break;
-                }
-                nu *= 2;
+                if (accepted || !lm.reject()) break;
             }
-            if (failed) break;
-            if (p_eL2 <= eps3_sq) stop = 5;
+            if (!lm.end_step()) break;
         }
-        if (!failed) {
-            if (itno >= kBaMaxIter) stop = 3;
-            info[0] = init_p_eL2, info[1] = p_eL2, info[2] = eab_inf, info[3] = dp_L2;
-            if (have_diag) info[4] = mu / max_diag;
-            info[5] = itno, info[6] = stop, info[7] = nfev, info[8] = njev, info[9] = nlss;
-            sba_ok = stop != 7;
-        } else {
-            mu = 0.0;
-        }
+        sba_ok = lm.finish(info);
     }
 
     // ---- the wrapper: the refined pose, the acceptance rule, the scatter of the points
@@ -424,43 +341,30 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(const double 
     if (accept)
         for (int k = tid; k < n; k += kBaThreads) {
             const size_t at = row0 + idx[k];
-            for (int c = 0; c < 3; ++c) Q[at * 3 + c] = WSV(kSM + cur_m * 3 + c, k);
+            for (int c = 0; c < 3; ++c) Q[at * 3 + c] = pw(kPM + cur_m * 3 + c, k);
         }
     if (tid == 0) {
         for (int k = 0; k < 9; ++k) po[k] = Rout[k];
         for (int k = 0; k < 3; ++k) po[9 + k] = tout[k];
         for (int k = 0; k < 10; ++k) po[12 + k] = info[k];
-        po[22] = mu;
+        po[22] = lm.mu;
         po[23] = accept ? 1.0 : 0.0;
     }
-#undef WSV
 }
 
-thread_local std::vector<double> g_last_mu;  // mu at exit of the problems of the calling thread's last call (mlpl_debug_ba_last_mu)
+thread_local LastMu g_last_mu;  // mlpl_debug_ba_last_mu
 
 // One launch for B problems.  R, t (host, in / out), th [B], accepted [B], info [B][10] or NULL.
 int ba_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
            const uint8_t *d_masks, double *d_Q, double *R, double *t, const double *th, double angle_thresh, double t_norm_thresh,
            int32_t *accepted, double *info, hipStream_t s) {
-    if (B < 1 || stride < 1 || !d_p1 || !d_p2 || !d_Q || !counts || !R || !t || !th || !accepted) {
-        set_error("%s: bad arguments", who);
-        return MLPL_E_BAD_INPUT;
-    }
-    if (B > 65535) {
-        set_error("%s: at most 65535 problems per call", who);
-        return MLPL_E_BAD_INPUT;
-    }
-    for (int b = 0; b < B; ++b)
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    int rc = ba_check_batch(who, d_p1 && d_p2 && d_Q && R && t && th && accepted, B, stride, counts, [](int) { return (int)MLPL_OK; });
+    if (rc) return rc;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     const size_t off_in = 0, off_out = off_in + (size_t)B * kBaIn * 8, off_counts = off_out + (size_t)B * kBaOut * 8,
                  small_bytes = off_counts + (size_t)B * 4;
     const size_t rows = (size_t)B * stride, off_idx = rows * kBaSlots * 8;
     void *d_small, *d_ws;
-    int rc;
     if ((rc = ws_get(ctx, WS_AUX2, small_bytes, &d_small))) return rc;
     if ((rc = ws_get(ctx, WS_BA, off_idx + rows * 4, &d_ws))) return rc;
     std::vector<char> h(small_bytes, 0);
@@ -484,7 +388,7 @@ int ba_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p1, const doub
     std::vector<double> ho((size_t)B * kBaOut);
     MLPL_HIP_TRY(hipMemcpyAsync(ho.data(), sm + off_out, ho.size() * 8, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
-    g_last_mu.resize((size_t)B);
+    g_last_mu.mu.resize((size_t)B);
     for (int b = 0; b < B; ++b) {
         const double *o = ho.data() + (size_t)b * kBaOut;
         accepted[b] = o[23] != 0.0;
@@ -493,7 +397,7 @@ int ba_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p1, const doub
             std::memcpy(t + 3 * b, o + 9, 24);
         }
         if (info) std::memcpy(info + 10 * b, o + 12, 80);
-        g_last_mu[(size_t)b] = o[22];
+        g_last_mu.mu[(size_t)b] = o[22];
     }
     return MLPL_OK;
 }
@@ -560,9 +464,4 @@ extern "C" int mlpl_refine_stereo_ba(mlpl_ctx *ctx, const double *p1, const doub
     return acc;
 }
 
-extern "C" int mlpl_debug_ba_last_mu(double *mu, int max_items) {
-    if (!mu || max_items < 0) return MLPL_E_BAD_INPUT;
-    const int n = std::min<int>((int)g_last_mu.size(), max_items);
-    for (int i = 0; i < n; ++i) mu[i] = g_last_mu[(size_t)i];
-    return n;
-}
+extern "C" int mlpl_debug_ba_last_mu(double *mu, int max_items) { return g_last_mu.get(mu, max_items); }

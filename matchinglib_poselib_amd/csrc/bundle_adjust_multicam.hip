@@ -19,14 +19,11 @@
 // unknown); the backward substitution's dot products run ascending from j + 1 in the oracle, which a column-oriented sweep would reverse, so
 // one lane walks them.  The only freedom taken against the oracle is therefore the association of the sums over points.
 //
-// The damping quirk of the reference (sba_levmar.c:1341-1355 compiled out) is kept as in bundle_adjust.hip: U's diagonal keeps every earlier
-// rejected mu, V_i's working diagonal is the diagonal of the previous attempt's inverse.
-#include <algorithm>
-#include <cfloat>
+// ba_common.h holds what this kernel shares with bundle_adjust.hip: the geometry, the reductions, and the Levenberg-Marquardt core (the slots
+// up to kPCam, the damped inverse of V*_i with the reference's damping quirk, the first_bad repair, the point update, the optimiser's state
+// and every stop).  U's diagonal keeps every earlier rejected mu here as it does there.
 #include <climits>
-#include <cmath>
 #include <cstring>
-#include <vector>
 
 #include "ba_common.h"
 #include "mlpl_internal.h"
@@ -35,13 +32,8 @@ namespace mlpl {
 namespace {
 
 constexpr int kMcMaxCams = MLPL_BA_MAX_CAMS;
-// slots of the per-point state (structure-of-arrays over the problem's stride)
-constexpr int kPM = 0;     // 2 x 3: the point, current / trial
-constexpr int kPVu = 6;    // 3: V_i (0,1) (0,2) (1,2)
-constexpr int kPVd = 9;    // 3: V_i's working diagonal
-constexpr int kPEb = 12;   // 3
-constexpr int kPInv = 15;  // 2 x 6: (V*_i)^-1 as (00, 01, 02, 11, 12, 22)
-constexpr int kPE = 27;    // per camera 2 x 2: the residual, current / trial; then per free camera 18: W_ij, 6 x 3 row-major
+// this kernel's slots of the per-point state, behind the shared ones
+constexpr int kPE = kPCam;  // per camera 2 x 2: the residual, current / trial; then per free camera 18: W_ij, 6 x 3 row-major
 __host__ __device__ constexpr int mc_slots(int cams) { return kPE + 4 * cams + 18 * cams; }
 __host__ __device__ constexpr int mc_in(int cams_stride) { return 4 + 12 * cams_stride; }    // th, angle_thresh, t_norm_thresh, -, R, t
 __host__ __device__ constexpr int mc_out(int cams_stride) { return 12 + 12 * cams_stride; }  // info 10, mu, accepted, R, t
@@ -73,11 +65,10 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
     double *U = qc + 4 * m, *Sm = U + 36 * (m - 1), *ea = Sm + dim * dim, *E = ea + dim, *da = E + dim;
     const size_t S = (size_t)stride;
     const size_t row0 = (size_t)b * stride;
-    double *ws = ws_all + row0 * mc_slots(cams_stride);
+    const PointWs pw{ws_all + row0 * mc_slots(cams_stride), S};
     const uint8_t *vis = vis_all + (size_t)b * cams_stride * S;
     const double *px = p + (size_t)b * cams_stride * S * 2;
     const int kPW = kPE + 4 * m;
-#define WSV(slot, k) ws[(size_t)(slot)*S + (k)]
 #define SLOT_E(j, which) (kPE + ((j)*2 + (which)) * 2)
 #define SLOT_W(j) (kPW + ((j)-1) * 18)
 #define SEEN(j, k) (vis[(size_t)(j)*S + (k)] != 0)
@@ -98,7 +89,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
 
     double info[10];
     for (int k = 0; k < 10; ++k) info[k] = 0.0;
-    double mu = 0.0;
+    LmState lm;
     bool sba_ok = false;
     int cur_m = 0;
 
@@ -112,11 +103,8 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
         nvis = (long long)cnt[0];
     }
     if (2 * nvis >= 6LL * m + 3LL * n) {
-        const double tau = 1e-3, eps1 = 1e-12, eps2 = 1e-12, eps2_sq = 1e-12 * 1e-12, eps3_sq = 1e-12 * 1e-12, eps4_sq = 1E-05 * 1E-05;
-
         // the points into the workspace, the residual at the start
         int cur_e = 0;
-        double p_eL2;
         if (tid < m) {
             double vv[3] = {v[3 * tid], v[3 * tid + 1], v[3 * tid + 2]};
             quat_lds(qc + 4 * tid, quat_mult_fast(local_quat(vv), lds_quat(r0 + 4 * tid)));
@@ -126,32 +114,27 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
             double acc[1] = {0.0};
             for (int k = tid; k < n; k += kBaThreads) {
                 double M[3], e[2];
-                for (int c = 0; c < 3; ++c) WSV(kPM + c, k) = M[c] = Q[(row0 + k) * 3 + c];
+                for (int c = 0; c < 3; ++c) pw(kPM + c, k) = M[c] = Q[(row0 + k) * 3 + c];
                 for (int j = 0; j < m; ++j) {
                     if (!SEEN(j, k)) continue;
                     const double x[2] = {px[((size_t)j * S + k) * 2], px[((size_t)j * S + k) * 2 + 1]};
                     const double tj[3] = {t[3 * j], t[3 * j + 1], t[3 * j + 2]};
                     residual2(lds_quat(qc + 4 * j), tj, M, x, th, e);
                     for (int c = 0; c < 2; ++c) {
-                        WSV(SLOT_E(j, 0) + c, k) = e[c];
+                        pw(SLOT_E(j, 0) + c, k) = e[c];
                         acc[0] += e[c] * e[c];
                     }
                 }
             }
             block_sum(acc, red);
-            p_eL2 = acc[0];
+            lm.start(acc[0]);
         }
-        const double init_p_eL2 = p_eL2;
-        int nfev = 1, njev = 0, nlss = 0, nu = 2, stop = 0, itno = 0;
-        double eab_inf = 0.0, dp_L2 = DBL_MAX, max_diag = 0.0;
-        bool have_diag = false, failed = false;
-        if (!isfinite(p_eL2)) stop = 7;
 
-        for (; itno < kBaMaxIter && !stop; ++itno) {
+        for (; lm.itno < kBaMaxIter && !lm.stop; ++lm.itno) {
             // ---- Jacobian blocks camera by camera: V_i, eb_i (all cameras), U_j, ea_j, W_ij (free cameras)
-            ++njev;
+            ++lm.njev;
             for (int k = tid; k < n; k += kBaThreads)
-                for (int c = 0; c < 3; ++c) WSV(kPVu + c, k) = 0.0, WSV(kPVd + c, k) = 0.0, WSV(kPEb + c, k) = 0.0;
+                for (int c = 0; c < 3; ++c) pw(kPVu + c, k) = 0.0, pw(kPVd + c, k) = 0.0, pw(kPEb + c, k) = 0.0;
             for (int j = 0; j < m; ++j) {
                 CamJ cam;
                 {
@@ -164,8 +147,8 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
                 for (int k = tid; k < n; k += kBaThreads) {
                     if (!SEEN(j, k)) continue;
                     double M[3], e[2], A[2][6], B[2][3];
-                    for (int c = 0; c < 3; ++c) M[c] = WSV(kPM + cur_m * 3 + c, k);
-                    for (int c = 0; c < 2; ++c) e[c] = WSV(SLOT_E(j, cur_e) + c, k);
+                    for (int c = 0; c < 3; ++c) M[c] = pw(kPM + cur_m * 3 + c, k);
+                    for (int c = 0; c < 2; ++c) e[c] = pw(SLOT_E(j, cur_e) + c, k);
                     if (j > 0) {
                         jac_blocks<true>(cam, M, A, B);
                         int s = 0;
@@ -178,7 +161,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
 #pragma unroll
                         for (int ii = 0; ii < 6; ++ii)
 #pragma unroll
-                            for (int jj = 0; jj < 3; ++jj) WSV(SLOT_W(j) + ii * 3 + jj, k) = A[0][ii] * B[0][jj] + A[1][ii] * B[1][jj];
+                            for (int jj = 0; jj < 3; ++jj) pw(SLOT_W(j) + ii * 3 + jj, k) = A[0][ii] * B[0][jj] + A[1][ii] * B[1][jj];
                     } else {
                         jac_blocks<false>(cam, M, A, B);
                     }
@@ -188,9 +171,9 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
                         for (int jj = ii; jj < 3; ++jj) {
                             const double val = B[0][ii] * B[0][jj] + B[1][ii] * B[1][jj];
                             const int slot = ii == jj ? kPVd + ii : kPVu + ii + jj - 1;
-                            WSV(slot, k) = WSV(slot, k) + val;
+                            pw(slot, k) = pw(slot, k) + val;
                         }
-                        WSV(kPEb + ii, k) = WSV(kPEb + ii, k) + (B[0][ii] * e[0] + B[1][ii] * e[1]);
+                        pw(kPEb + ii, k) = pw(kPEb + ii, k) + (B[0][ii] * e[0] + B[1][ii] * e[1]);
                     }
                 }
                 if (j > 0) {
@@ -213,12 +196,12 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
             double sq[1] = {0.0};
             for (int k = tid; k < n; k += kBaThreads) {
                 for (int c = 0; c < 3; ++c) {
-                    const double d = WSV(kPVd + c, k);
+                    const double d = pw(kPVd + c, k);
                     if (d > mx_d) mx_d = d;
-                    mx_e = fmax(mx_e, fabs(WSV(kPEb + c, k)));
+                    mx_e = fmax(mx_e, fabs(pw(kPEb + c, k)));
                 }
                 for (int c = 0; c < 3; ++c) {
-                    const double Mc = WSV(kPM + cur_m * 3 + c, k);
+                    const double Mc = pw(kPM + cur_m * 3 + c, k);
                     sq[0] += Mc * Mc;
                 }
             }
@@ -230,55 +213,29 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
                 const double d = U[36 * (i / 6) + (i % 6) * 7];
                 if (d > mx_d) mx_d = d;
             }
-            eab_inf = mx_e;
             double p_L2 = 0.0;
             for (int j = 0; j < m; ++j) {
                 for (int k = 0; k < 3; ++k) p_L2 += v[3 * j + k] * v[3 * j + k];
                 for (int k = 0; k < 3; ++k) p_L2 += t[3 * j + k] * t[3 * j + k];
             }
             p_L2 += sq[0];
-            max_diag = mx_d, have_diag = true;
-            if (eab_inf <= eps1) {
-                dp_L2 = 0.0;
-                stop = 1;
-                break;
-            }
-            if (itno == 0) mu = tau * max_diag;
+            if (!lm.after_gradient(mx_e, mx_d)) break;
 
             // ---- the damping loop
             bool vd_from_inv = false;  // V_i's diagonal currently lives in the previous attempt's inverse
             int cur_inv = 0;
             while (true) {
                 __syncthreads();
-                if (tid < dim) U[36 * (tid / 6) + (tid % 6) * 7] += mu;
+                if (tid < dim) U[36 * (tid / 6) + (tid % 6) * 7] += lm.mu;
                 int first_bad = INT_MAX;
                 for (int k = tid; k < n; k += kBaThreads) {
-                    double d[3];
-                    for (int c = 0; c < 3; ++c)
-                        d[c] = (vd_from_inv ? WSV(kPInv + cur_inv * 6 + (c == 0 ? 0 : c == 1 ? 3 : 5), k) : WSV(kPVd + c, k)) + mu;
-                    const double vb = WSV(kPVu + 0, k), vc = WSV(kPVu + 1, k), ve = WSV(kPVu + 2, k);
-                    const double c00 = d[1] * d[2] - ve * ve, c01 = vc * ve - vb * d[2], c02 = vb * ve - vc * d[1];
-                    const double det = d[0] * c00 + vb * c01 + vc * c02;
-                    if (!(isfinite(det) && det != 0)) {
-                        if (k < first_bad) first_bad = k;
-                        continue;
-                    }
-                    const double idet = 1 / det;
-                    const double inv[6] = {c00 * idet, c01 * idet, c02 * idet, (d[0] * d[2] - vc * vc) * idet, (vb * vc - d[0] * ve) * idet,
-                                           (d[0] * d[1] - vb * vb) * idet};
-                    for (int c = 0; c < 6; ++c) WSV(kPInv + (cur_inv ^ 1) * 6 + c, k) = inv[c];
+                    double inv[6];
+                    if (!damped_inverse(pw, k, vd_from_inv, cur_inv, lm.mu, inv) && k < first_bad) first_bad = k;
                 }
                 first_bad = block_min_int(first_bad, red_i);  // (its barriers also publish U's new diagonal)
                 bool accepted = false;
                 if (first_bad != INT_MAX) {
-                    // the reference walks the points in order and leaves at the first V*_i it cannot invert: earlier points hold their new
-                    // inverse's diagonal, the failing one its augmented diagonal, later ones are untouched
-                    for (int k = tid; k < n; k += kBaThreads)
-                        for (int c = 0; c < 3; ++c) {
-                            const int dslot = c == 0 ? 0 : c == 1 ? 3 : 5;
-                            const double old = vd_from_inv ? WSV(kPInv + cur_inv * 6 + dslot, k) : WSV(kPVd + c, k);
-                            WSV(kPVd + c, k) = k < first_bad ? WSV(kPInv + (cur_inv ^ 1) * 6 + dslot, k) : k == first_bad ? old + mu : old;
-                        }
+                    repair_first_bad(pw, n, first_bad, vd_from_inv, cur_inv, lm.mu);
                     vd_from_inv = false;
                 } else {
                     cur_inv ^= 1, vd_from_inv = true;
@@ -291,24 +248,24 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
                             for (int k = tid; k < n; k += kBaThreads) {
                                 if (!SEEN(j, k) || !SEEN(kc, k)) continue;
                                 double inv[6], Y[6][3], Wk[6][3];
-                                for (int c = 0; c < 6; ++c) inv[c] = WSV(kPInv + cur_inv * 6 + c, k);
+                                for (int c = 0; c < 6; ++c) inv[c] = pw(kPInv + cur_inv * 6 + c, k);
                                 const double im[3][3] = {{inv[0], inv[1], inv[2]}, {inv[1], inv[3], inv[4]}, {inv[2], inv[4], inv[5]}};
 #pragma unroll
                                 for (int ii = 0; ii < 6; ++ii) {
-                                    const double w0 = WSV(SLOT_W(j) + ii * 3, k), w1 = WSV(SLOT_W(j) + ii * 3 + 1, k), w2 = WSV(SLOT_W(j) + ii * 3 + 2, k);
+                                    const double w0 = pw(SLOT_W(j) + ii * 3, k), w1 = pw(SLOT_W(j) + ii * 3 + 1, k), w2 = pw(SLOT_W(j) + ii * 3 + 2, k);
 #pragma unroll
                                     for (int jj = 0; jj < 3; ++jj) Y[ii][jj] = w0 * im[0][jj] + w1 * im[1][jj] + w2 * im[2][jj];
                                 }
 #pragma unroll
                                 for (int ii = 0; ii < 6; ++ii)
 #pragma unroll
-                                    for (int jj = 0; jj < 3; ++jj) Wk[ii][jj] = WSV(SLOT_W(kc) + ii * 3 + jj, k);
+                                    for (int jj = 0; jj < 3; ++jj) Wk[ii][jj] = pw(SLOT_W(kc) + ii * 3 + jj, k);
 #pragma unroll
                                 for (int ii = 0; ii < 6; ++ii)
 #pragma unroll
                                     for (int jj = 0; jj < 6; ++jj) acc[ii * 6 + jj] += Y[ii][0] * Wk[jj][0] + Y[ii][1] * Wk[jj][1] + Y[ii][2] * Wk[jj][2];
                                 if (kc == j) {
-                                    const double e0 = WSV(kPEb, k), e1 = WSV(kPEb + 1, k), e2 = WSV(kPEb + 2, k);
+                                    const double e0 = pw(kPEb, k), e1 = pw(kPEb + 1, k), e2 = pw(kPEb + 2, k);
 #pragma unroll
                                     for (int ii = 0; ii < 6; ++ii) acc[36 + ii] += Y[ii][0] * e0 + Y[ii][1] * e1 + Y[ii][2] * e2;
                                 }
@@ -351,7 +308,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
                         if (kk < dim) Sm[j * dim + kk] = val;
                         __syncthreads();
                     }
-                    ++nlss;
+                    ++lm.nlss;
                     if (solved) {
                         // U^T y = E column by column (lane jj keeps its running right-hand side; y into E), then U x = y by one lane
                         double rhs = tid < dim ? E[tid] : 0.0;
@@ -380,103 +337,58 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
                         // ---- db_i, the trial point, its residuals; ||db||^2, ||e(p + dp)||^2, dL over the points
                         double s3[3] = {0.0, 0.0, 0.0};
                         for (int k = tid; k < n; k += kBaThreads) {
-                            double inv[6], ebv[3], wtda[3] = {0.0, 0.0, 0.0}, r[3], db[3], Mn[3], e[2];
-                            for (int c = 0; c < 6; ++c) inv[c] = WSV(kPInv + cur_inv * 6 + c, k);
-                            const double im[3][3] = {{inv[0], inv[1], inv[2]}, {inv[1], inv[3], inv[4]}, {inv[2], inv[4], inv[5]}};
+                            double inv[6], ebv[3], wtda[3] = {0.0, 0.0, 0.0}, r[3], Mn[3], e[2];
+                            load_inverse(pw, k, cur_inv, inv);
                             for (int j = 1; j < m; ++j) {
                                 if (!SEEN(j, k)) continue;
                                 const double *dj = da + 6 * (j - 1);
 #pragma unroll
                                 for (int ii = 0; ii < 3; ++ii) {
-                                    double wt = WSV(SLOT_W(j) + ii, k) * dj[0];
+                                    double wt = pw(SLOT_W(j) + ii, k) * dj[0];
 #pragma unroll
-                                    for (int jj = 1; jj < 6; ++jj) wt = wt + WSV(SLOT_W(j) + jj * 3 + ii, k) * dj[jj];
+                                    for (int jj = 1; jj < 6; ++jj) wt = wt + pw(SLOT_W(j) + jj * 3 + ii, k) * dj[jj];
                                     wtda[ii] = wtda[ii] + wt;
                                 }
                             }
 #pragma unroll
                             for (int ii = 0; ii < 3; ++ii) {
-                                ebv[ii] = WSV(kPEb + ii, k);
+                                ebv[ii] = pw(kPEb + ii, k);
                                 r[ii] = ebv[ii] - wtda[ii];
                             }
-#pragma unroll
-                            for (int ii = 0; ii < 3; ++ii) {
-                                db[ii] = im[ii][0] * r[0] + im[ii][1] * r[1] + im[ii][2] * r[2];
-                                Mn[ii] = WSV(kPM + cur_m * 3 + ii, k) + db[ii];
-                                WSV(kPM + (cur_m ^ 1) * 3 + ii, k) = Mn[ii];
-                                s3[0] += db[ii] * db[ii];
-                                s3[2] += db[ii] * (mu * db[ii] + ebv[ii]);
-                            }
+                            point_update(pw, k, cur_m, inv, r, ebv, lm.mu, Mn, s3);
                             for (int j = 0; j < m; ++j) {
                                 if (!SEEN(j, k)) continue;
                                 const double x[2] = {px[((size_t)j * S + k) * 2], px[((size_t)j * S + k) * 2 + 1]};
                                 const double tj[3] = {tn[3 * j], tn[3 * j + 1], tn[3 * j + 2]};
                                 residual2(lds_quat(qc + 4 * j), tj, Mn, x, th, e);
                                 for (int c = 0; c < 2; ++c) {
-                                    WSV(SLOT_E(j, cur_e ^ 1) + c, k) = e[c];
+                                    pw(SLOT_E(j, cur_e ^ 1) + c, k) = e[c];
                                     s3[1] += e[c] * e[c];
                                 }
                             }
                         }
                         block_sum(s3, red);
-                        dp_L2 = 0.0;
-                        double dL = 0.0;
+                        double dp_L2 = 0.0, dL = 0.0;  // the cameras' part
                         for (int k = 0; k < dim; ++k) {
                             dp_L2 += da[k] * da[k];
-                            dL += da[k] * (mu * da[k] + ea[k]);
+                            dL += da[k] * (lm.mu * da[k] + ea[k]);
                         }
-                        dp_L2 += s3[0];
-                        dL += s3[2];
-                        const double pdp_eL2 = s3[1];
-                        if (dp_L2 <= eps2_sq * p_L2) {
-                            stop = 2;
-                            break;
-                        }
-                        if (dp_L2 >= (p_L2 + eps2) / (1E-12 * 1E-12)) {  // "almost singular": the optimiser fails, info stays unwritten
-                            failed = true;
-                            break;
-                        }
-                        ++nfev;
-                        if (!isfinite(pdp_eL2)) {
-                            stop = 7;
-                            break;
-                        }
-                        const double dF = p_eL2 - pdp_eL2;
-                        if (dL > 0.0 && dF > 0.0) {
-                            double tmp = 2.0 * dF / dL - 1.0;
-                            tmp = 1.0 - tmp * tmp * tmp;
-                            mu = mu * ((tmp >= 0.3333333334) ? tmp : 0.3333333334);
-                            nu = 2;
-                            if (pdp_eL2 - 2.0 * sqrt(p_eL2 * pdp_eL2) < (eps4_sq - 1.0) * p_eL2) stop = 4;
+                        const LmVerdict verdict = lm.verdict(dp_L2, dL, s3, p_L2);
+                        if (verdict == kLmLeave) break;
+                        if (verdict == kLmAccepted) {
                             __syncthreads();
                             if (tid < 3 * m) v[tid] = vn[tid], t[tid] = tn[tid];
                             __syncthreads();
                             cur_m ^= 1, cur_e ^= 1;
-                            p_eL2 = pdp_eL2;
                             accepted = true;
                         }
                     }
                 }
-                if (accepted) break;
-                mu *= nu;
-                if (nu >= (1 << 30)) {  // 2 nu no longer fits an int
-                    stop = 6;
-                    break;
-                }
-                nu *= 2;
+                if (accepted || !lm.reject()) break;
             }
-            if (failed) break;
-            if (p_eL2 <= eps3_sq) stop = 5;
+            if (!lm.end_step()) break;
         }
-        if (!failed) {
-            if (itno >= kBaMaxIter) stop = 3;
-            info[0] = init_p_eL2, info[1] = p_eL2, info[2] = eab_inf, info[3] = dp_L2;
-            if (have_diag) info[4] = mu / max_diag;
-            info[5] = itno, info[6] = stop, info[7] = nfev, info[8] = njev, info[9] = nlss;
-            sba_ok = stop != 7;
-        } else {
-            mu = 0.0;
-        }
+        sba_ok = lm.finish(info);
     }
     __syncthreads();
 
@@ -505,7 +417,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
     accept = accept && red_i[0] == 0;
     if (accept) {
         for (int k = tid; k < n; k += kBaThreads)
-            for (int c = 0; c < 3; ++c) Q[(row0 + k) * 3 + c] = WSV(kPM + cur_m * 3 + c, k);
+            for (int c = 0; c < 3; ++c) Q[(row0 + k) * 3 + c] = pw(kPM + cur_m * 3 + c, k);
         if (tid < m) {
             double Rout[9];
             quat_to_matrix(qn, Rout);
@@ -515,51 +427,39 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_multicam_kernel(
     }
     if (tid == 0) {
         for (int k = 0; k < 10; ++k) po[k] = info[k];
-        po[10] = mu;
+        po[10] = lm.mu;
         po[11] = accept ? 1.0 : 0.0;
     }
-#undef WSV
 #undef SLOT_E
 #undef SLOT_W
 #undef SEEN
 }
 
-thread_local std::vector<double> g_last_mu_mc;  // mu at exit of the problems of the calling thread's last call (mlpl_debug_ba_multicam_last_mu)
+thread_local LastMu g_last_mu_mc;  // mlpl_debug_ba_multicam_last_mu
 
 // One launch for B problems.  R [B][cams_stride][9], t [B][cams_stride][3] (host, in / out), th [B], accepted [B], info [B][10] or NULL.
 int mc_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p, const uint8_t *d_vis, int cams_stride, int stride, const int32_t *n_cams,
            const int32_t *counts, double *d_Q, double *R, double *t, const double *th, double angle_thresh, double t_norm_thresh,
            int32_t *accepted, double *info, hipStream_t s) {
-    if (B < 1 || stride < 1 || cams_stride < 1 || !d_p || !d_vis || !d_Q || !n_cams || !counts || !R || !t || !th || !accepted) {
-        set_error("%s: bad arguments", who);
-        return MLPL_E_BAD_INPUT;
-    }
-    if (B > 65535) {
-        set_error("%s: at most 65535 problems per call", who);
-        return MLPL_E_BAD_INPUT;
-    }
     int max_m = 2;
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    int rc = ba_check_batch(who, cams_stride >= 1 && d_p && d_vis && d_Q && n_cams && R && t && th && accepted, B, stride, counts, [&](int b) {
         if (n_cams[b] < 0 || n_cams[b] > cams_stride) {
             set_error("%s: n_cams[%d] = %d outside [0, cams_stride = %d]", who, b, n_cams[b], cams_stride);
-            return MLPL_E_BAD_INPUT;
+            return (int)MLPL_E_BAD_INPUT;
         }
         if (n_cams[b] > kMcMaxCams) {
             set_error("%s: n_cams[%d] = %d: at most MLPL_BA_MAX_CAMS = %d cameras are built", who, b, n_cams[b], kMcMaxCams);
-            return MLPL_E_UNSUPPORTED;
+            return (int)MLPL_E_UNSUPPORTED;
         }
         max_m = std::max(max_m, (int)n_cams[b]);
-    }
+        return (int)MLPL_OK;
+    });
+    if (rc) return rc;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     const size_t n_in = (size_t)mc_in(cams_stride), n_out = (size_t)mc_out(cams_stride);
     const size_t off_in = 0, off_out = off_in + (size_t)B * n_in * 8, off_cams = off_out + (size_t)B * n_out * 8, off_counts = off_cams + (size_t)B * 4,
                  small_bytes = off_counts + (size_t)B * 4;
     void *d_small, *d_ws;
-    int rc;
     if ((rc = ws_get(ctx, WS_BA_MULTICAM_IO, small_bytes, &d_small))) return rc;
     if ((rc = ws_get(ctx, WS_BA_MULTICAM, (size_t)B * stride * mc_slots(cams_stride) * 8, &d_ws))) return rc;
     std::vector<char> h(off_out, 0);
@@ -587,7 +487,7 @@ int mc_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p, const uint8
     std::vector<double> ho((size_t)B * n_out);
     MLPL_HIP_TRY(hipMemcpyAsync(ho.data(), sm + off_out, ho.size() * 8, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
-    g_last_mu_mc.resize((size_t)B);
+    g_last_mu_mc.mu.resize((size_t)B);
     for (int b = 0; b < B; ++b) {
         const double *o = ho.data() + (size_t)b * n_out;
         accepted[b] = o[11] != 0.0;
@@ -596,7 +496,7 @@ int mc_run(mlpl_ctx *ctx, const char *who, int B, const double *d_p, const uint8
             std::memcpy(t + (size_t)b * cams_stride * 3, o + 12 + 9 * cams_stride, (size_t)n_cams[b] * 24);
         }
         if (info) std::memcpy(info + 10 * b, o, 80);
-        g_last_mu_mc[(size_t)b] = o[10];
+        g_last_mu_mc.mu[(size_t)b] = o[10];
     }
     return MLPL_OK;
 }
@@ -676,9 +576,4 @@ extern "C" int mlpl_refine_multicam_ba(mlpl_ctx *ctx, const double *p, const uin
     return acc;
 }
 
-extern "C" int mlpl_debug_ba_multicam_last_mu(double *mu, int max_items) {
-    if (!mu || max_items < 0) return MLPL_E_BAD_INPUT;
-    const int n = std::min<int>((int)g_last_mu_mc.size(), max_items);
-    for (int i = 0; i < n; ++i) mu[i] = g_last_mu_mc[(size_t)i];
-    return n;
-}
+extern "C" int mlpl_debug_ba_multicam_last_mu(double *mu, int max_items) { return g_last_mu_mc.get(mu, max_items); }

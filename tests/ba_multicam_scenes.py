@@ -187,6 +187,31 @@ def oracle_result(name):
 integers = BAS.integers
 rel_diff = BAS.rel_diff
 
+# ---- the stereo scenes of ba_scenes.BRANCH_SCENES as two-camera problems: they reach every exit of the optimiser, which SCENES above do not -------
+_two_cam, _two_cam_results = {}, {}
+
+
+def two_camera(name):
+    """Scene `name` of ba_scenes.BRANCH_SCENES as this entry's arguments: the rows outside the mask dropped, camera 0 at the identity, every
+    point seen by both cameras, the scene's own thresholds."""
+    if name not in _two_cam:
+        s = BAS.scene(name)
+        keep = slice(None) if s["mask"] is None else s["mask"] != 0
+        p = np.ascontiguousarray(np.stack([s["p1"][keep], s["p2"][keep]]))
+        _two_cam[name] = dict(p=p, vis=np.ones(p.shape[:2], np.uint8), R=np.stack([np.eye(3), s["R"]]), t=np.stack([np.zeros(3), s["t"]]),
+                              Q=np.ascontiguousarray(s["Q"][keep]), th=s["th"], angle_thresh=s["angle_thresh"], t_norm_thresh=s["t_norm_thresh"],
+                              m=2, n=p.shape[1])
+    return _two_cam[name]
+
+
+def two_camera_oracle_result(name):
+    """ba_multicam_oracle on two_camera(name).  Computed once per session and shared; callers must not modify it."""
+    if name not in _two_cam_results:
+        s = two_camera(name)
+        with np.errstate(all="ignore"):        # the stop-6 and stop-7 scenes overflow or divide by zero on purpose
+            _two_cam_results[name] = BMO.ba_multicam_oracle(s["p"], s["vis"], s["R"], s["t"], s["Q"], s["th"], s["angle_thresh"], s["t_norm_thresh"])
+    return _two_cam_results[name]
+
 
 def compacted(s):
     """The facade's arguments: ps[j] = camera j's observations in ascending point order, map3D[j] = int8 [n]."""

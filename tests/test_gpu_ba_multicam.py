@@ -86,6 +86,34 @@ def test_two_cameras_against_the_stereo_entry(ctx):
     assert np.abs(r["Q"] - st["Q"]).max() <= BAS.TOL_Q + tol["q"]
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(BAS.BRANCH_SCENES))
+def test_branch_scene_as_two_cameras(ctx, name):
+    """Every exit of the optimiser (stops 1 to 7, rejected attempts, refused solves, both first_bad repairs) and the edge sizes through THIS
+    kernel: the scenes of ba_scenes.BRANCH_SCENES at m = 2 (S.two_camera) against ba_multicam_oracle on the same arguments.
+    test_oracle_ba_multicam.py shows that this oracle gives there what ba_oracle gives on the stereo scene, so the scene's own tolerances
+    hold; they were derived for entries of R and t of size at most 1 and this entry returns t un-normalised, hence tol * max(1, |t|)."""
+    from matchinglib_poselib_amd import pose
+
+    row, s, o = BAS.BRANCH_SCENES[name], S.two_camera(name), S.two_camera_oracle_result(name)
+    tol, kind = row["tol"], row["kind"]
+    r = pose.refine_multicam_ba(s["p"], s["vis"], s["R"], s["t"], s["Q"], s["th"], s["angle_thresh"], s["t_norm_thresh"], ctx=ctx)
+    got = (bool(r["accepted"]),) + tuple(int(x) for x in r["info"][5:10])
+    d_info = [S.rel_diff(r["info"][i], o["info"][i]) for i in BAS.INFO_COMPARED[kind]]
+    d_mu = S.rel_diff(r["mu"], o["mu"])
+    print(name, "integers", got, "info", d_info, "(%.3g)" % tol["info"], "mu %.3g (%.3g)" % (d_mu, tol["mu"]))
+    assert got == S.integers(o), name
+    assert max(d_info) <= tol["info"] and d_mu <= tol["mu"], name
+    if o["accepted"]:
+        t_size = max(1.0, np.sqrt(o["t"][1] @ o["t"][1]))
+        d_R, d_t, d_q = np.abs(r["R"][1] - o["R"][1]).max(), np.abs(r["t"][1] - o["t"][1]).max(), np.abs(r["Q"] - o["Q"]).max()
+        print(name, "dR %.3g dt %.3g (%.3g, |t| %.3g) dQ %.3g (%.3g)" % (d_R, d_t, tol["pose"], t_size, d_q, tol["q"]))
+        assert d_R <= tol["pose"] and d_t <= tol["pose"] * t_size and d_q <= tol["q"], name
+        assert np.abs(r["R"][0] - np.eye(3)).max() < 1e-15 and _same_bits(r["t"][0], s["t"][0]), name
+    else:
+        assert _same_bits(r["R"], s["R"]) and _same_bits(r["t"], s["t"]) and _same_bits(r["Q"], s["Q"]), name
+
+
 BATCH = ("m2_full_n65", "m3_n15_short", "m4_n257", None, "m16_n128", "rejected", "m5_sparse_cam")
 CAMS_STRIDE, STRIDE = 16, 320
 

@@ -79,6 +79,19 @@ def test_two_camera_reduction_is_ba_oracle_bit_for_bit():
     assert np.array_equal(oa["info"], ob["info"]) and oa["mu"] == ob["mu"] and oa["trace"] == ob["trace"]
 
 
+@pytest.mark.parametrize("name", list(BAS.BRANCH_SCENES))
+def test_two_camera_reduction_over_the_branch_scenes(name):
+    """The same reduction at every exit of the optimiser, branch of the wrapper and edge size: each scene of ba_scenes.BRANCH_SCENES as a
+    two-camera problem (S.two_camera) gives info and mu bit for bit as ba_oracle does on the scene itself, and the same verdict.  So what
+    test_oracle_bundle_adjust.py finds in each scene (the stop, the rejected attempts, the refused solves, first_bad) and the scene's
+    permutation tolerances stand behind ba_multicam_oracle at m = 2, which is what test_gpu_ba_multicam.py holds the device to."""
+    a, b = BAS.oracle_result(name), S.two_camera_oracle_result(name)
+    print(name, BAS.integers(a), BAS.integers(b))
+    assert a["accepted"] == b["accepted"]
+    assert np.asarray(a["info"]).tobytes() == np.asarray(b["info"]).tobytes()
+    assert np.array([a["mu"]]).tobytes() == np.array([b["mu"]]).tobytes()
+
+
 def test_refusals():
     # fewer measurements than unknowns: the optimiser refuses, info stays zero, everything comes back
     s, o = S.scene("m3_n15_short"), S.oracle_result("m3_n15_short")

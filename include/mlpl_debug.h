@@ -40,6 +40,11 @@ int mlpl_debug_ransac_draw(mlpl_ctx *ctx, long long out[2]);
  * thread.  Returns n * rounds, or a negative value on bad arguments / a fiber that was not released exactly once per round. */
 long long mlpl_debug_fiber_selftest(int n, int workers, int rounds);
 
+/* The guard every entry carries against C++ exceptions by itself, no GPU and no context needed: a guarded body that returns 7 (kind 0),
+ * throws std::bad_alloc (kind 1: MLPL_E_NOMEM comes back), a std::runtime_error (kind 2: MLPL_E_INTERNAL, mlpl_last_error() carries its
+ * what()) or an int (kind 3: MLPL_E_INTERNAL). */
+int mlpl_debug_entry_guard(int kind);
+
 /* The two eigen-solvers of the re-weighted 9 x 9 fits on `count` symmetric matrices G[count][81] (tests): out12[count][12] = {steps of the
  * inverse iteration (0: it did not settle and the caller would take the Jacobi path), x^T G x, 0, x[9]}; jacobi10[count][10] = {smallest
  * eigenvalue, its eigenvector} of the full Jacobi decomposition; start[count][9] (may be NULL) = start vectors of the inverse iteration. */

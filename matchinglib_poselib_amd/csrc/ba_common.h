@@ -389,13 +389,9 @@ int ba_check_batch(const char *who, bool have_args, int B, int stride, const int
         set_error("%s: at most 65535 problems per call", who);
         return MLPL_E_BAD_INPUT;
     }
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    if (!counts_in_range(who, B, counts, 0, stride)) return MLPL_E_BAD_INPUT;
+    for (int b = 0; b < B; ++b)
         if (int rc = per_problem(b)) return rc;
-    }
     return MLPL_OK;
 }
 

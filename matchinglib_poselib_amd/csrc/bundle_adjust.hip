@@ -410,18 +410,18 @@ using namespace mlpl;
 extern "C" int mlpl_refine_stereo_ba_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride,
                                                const int32_t *counts, const uint8_t *d_masks, double *d_Q, double *R, double *t,
                                                const double *th, double angle_thresh, double t_norm_thresh, int32_t *accepted, double *info,
-                                               void *stream) {
+                                               void *stream) try {
     if (!ctx) {
         set_error("mlpl_refine_stereo_ba_batch_dev: ctx is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return ba_run(ctx, "mlpl_refine_stereo_ba_batch_dev", n_problems, d_p1, d_p2, stride, counts, d_masks, d_Q, R, t, th, angle_thresh,
                   t_norm_thresh, accepted, info, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_refine_stereo_ba_batch_dev")
 
 extern "C" int mlpl_refine_stereo_ba_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const uint8_t *d_mask, double R[9],
                                          double t[3], double *d_Q, double th, double angle_thresh, double t_norm_thresh, double info[10],
-                                         void *stream) {
+                                         void *stream) try {
     if (!ctx || n < 0) {
         set_error("mlpl_refine_stereo_ba_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -433,10 +433,10 @@ extern "C" int mlpl_refine_stereo_ba_dev(mlpl_ctx *ctx, const double *d_p1, cons
     const int rc = ba_run(ctx, "mlpl_refine_stereo_ba_dev", 1, d_p1, d_p2, n, &count, d_mask, d_Q, R, t, &th, angle_thresh, t_norm_thresh, &acc,
                           info, pick_stream(ctx, stream));
     return rc ? rc : acc;
-}
+} MLPL_ENTRY_END("mlpl_refine_stereo_ba_dev")
 
 extern "C" int mlpl_refine_stereo_ba(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask, double R[9], double t[3],
-                                     double *Q, double th, double angle_thresh, double t_norm_thresh, double info[10]) {
+                                     double *Q, double th, double angle_thresh, double t_norm_thresh, double info[10]) try {
     if (!ctx || n < 0 || (n > 0 && (!p1 || !p2 || !Q)) || !R || !t) {
         set_error("mlpl_refine_stereo_ba: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -445,23 +445,21 @@ extern "C" int mlpl_refine_stereo_ba(mlpl_ctx *ctx, const double *p1, const doub
     if (n == 0) return 0;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2, *dQ, *dmask = nullptr;
+    const double *dp1, *dp2;
+    void *dQ, *dmask = nullptr;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     if ((rc = ws_get(ctx, WS_AUX5, (size_t)n * 24, &dQ))) return rc;
     if (mask && (rc = ws_get(ctx, WS_AUX6, (size_t)n, &dmask))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dQ, Q, (size_t)n * 24, hipMemcpyHostToDevice, s));
     if (mask) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
     const int32_t count = n;
     int32_t acc = 0;
-    if ((rc = ba_run(ctx, "mlpl_refine_stereo_ba", 1, (const double *)dp1, (const double *)dp2, n, &count, (const uint8_t *)dmask, (double *)dQ,
-                     R, t, &th, angle_thresh, t_norm_thresh, &acc, info, s)))
+    if ((rc = ba_run(ctx, "mlpl_refine_stereo_ba", 1, dp1, dp2, n, &count, (const uint8_t *)dmask, (double *)dQ, R, t, &th, angle_thresh,
+                     t_norm_thresh, &acc, info, s)))
         return rc;
     if (acc) MLPL_HIP_TRY(hipMemcpy(Q, dQ, (size_t)n * 24, hipMemcpyDeviceToHost));
     return acc;
-}
+} MLPL_ENTRY_END("mlpl_refine_stereo_ba")
 
 extern "C" int mlpl_debug_ba_last_mu(double *mu, int max_items) { return g_last_mu.get(mu, max_items); }

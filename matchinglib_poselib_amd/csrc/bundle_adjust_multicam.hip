@@ -522,17 +522,17 @@ using namespace mlpl;
 extern "C" int mlpl_refine_multicam_ba_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p, const uint8_t *d_vis, int cams_stride,
                                                  int stride, const int32_t *n_cams, const int32_t *counts, double *d_Q, double *R, double *t,
                                                  const double *th, double angle_thresh, double t_norm_thresh, int32_t *accepted, double *info,
-                                                 void *stream) {
+                                                 void *stream) try {
     if (!ctx) {
         set_error("mlpl_refine_multicam_ba_batch_dev: ctx is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return mc_run(ctx, "mlpl_refine_multicam_ba_batch_dev", n_problems, d_p, d_vis, cams_stride, stride, n_cams, counts, d_Q, R, t, th,
                   angle_thresh, t_norm_thresh, accepted, info, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_refine_multicam_ba_batch_dev")
 
 extern "C" int mlpl_refine_multicam_ba_dev(mlpl_ctx *ctx, const double *d_p, const uint8_t *d_vis, int m, int n, double *R, double *t,
-                                           double *d_Q, double th, double angle_thresh, double t_norm_thresh, double info[10], void *stream) {
+                                           double *d_Q, double th, double angle_thresh, double t_norm_thresh, double info[10], void *stream) try {
     if (!ctx || n < 0) {
         set_error("mlpl_refine_multicam_ba_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -545,10 +545,10 @@ extern "C" int mlpl_refine_multicam_ba_dev(mlpl_ctx *ctx, const double *d_p, con
     const int rc = mc_run(ctx, "mlpl_refine_multicam_ba_dev", 1, d_p, d_vis, m, n, &cams, &count, d_Q, R, t, &th, angle_thresh, t_norm_thresh,
                           &acc, info, pick_stream(ctx, stream));
     return rc ? rc : acc;
-}
+} MLPL_ENTRY_END("mlpl_refine_multicam_ba_dev")
 
 extern "C" int mlpl_refine_multicam_ba(mlpl_ctx *ctx, const double *p, const uint8_t *vis, int m, int n, double *R, double *t, double *Q,
-                                       double th, double angle_thresh, double t_norm_thresh, double info[10]) {
+                                       double th, double angle_thresh, double t_norm_thresh, double info[10]) try {
     if (!ctx || n < 0 || (n > 0 && (!p || !vis || !Q)) || !R || !t) {
         set_error("mlpl_refine_multicam_ba: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -574,6 +574,6 @@ extern "C" int mlpl_refine_multicam_ba(mlpl_ctx *ctx, const double *p, const uin
         return rc;
     if (acc) MLPL_HIP_TRY(hipMemcpy(Q, dQ, (size_t)n * 24, hipMemcpyDeviceToHost));
     return acc;
-}
+} MLPL_ENTRY_END("mlpl_refine_multicam_ba")
 
 extern "C" int mlpl_debug_ba_multicam_last_mu(double *mu, int max_items) { return g_last_mu_mc.get(mu, max_items); }

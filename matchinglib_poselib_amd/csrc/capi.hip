@@ -5,6 +5,7 @@
 #include <cfloat>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <new>
 
 #include "mlpl_internal.h"
@@ -18,6 +19,50 @@ void set_error(const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+int entry_failed(const char *who) noexcept {
+    try {
+        throw;
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", who);
+        return MLPL_E_NOMEM;
+    } catch (const std::exception &e) {
+        set_error("%s: C++ exception: %s", who, e.what());
+    } catch (...) {
+        set_error("%s: C++ exception of an unknown type", who);
+    }
+    return MLPL_E_INTERNAL;
+}
+
+bool counts_in_range(const char *who, int n_problems, const int32_t *counts, int lo, int stride) {
+    for (int b = 0; b < n_problems; ++b)
+        if (counts[b] < lo || counts[b] > stride) {
+            set_error("%s: counts[%d] = %d outside [%d, stride = %d]", who, b, counts[b], lo, stride);
+            return false;
+        }
+    return true;
+}
+
+int upload_points(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double **d_p1, const double **d_p2, size_t match_bytes,
+                  void **d_match) {
+    const size_t bytes = (size_t)std::max(n, 1) * 16;
+    void *a, *b;
+    int rc;
+    if ((rc = ws_get(ctx, WS_AUX0, bytes, &a))) return rc;
+    if ((rc = ws_get(ctx, WS_AUX1, bytes, &b))) return rc;
+    if (match_bytes && (rc = ws_get(ctx, WS_MATCH, match_bytes, d_match))) return rc;
+    if (n > 0) {
+        MLPL_HIP_TRY(hipMemcpyAsync(a, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+        MLPL_HIP_TRY(hipMemcpyAsync(b, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *d_p1 = (const double *)a, *d_p2 = (const double *)b;
+    return MLPL_OK;
+}
+
+int download_mask(uint8_t *mask, const void *d_mask, int n) {
+    if (n > 0) MLPL_HIP_TRY(hipMemcpy(mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+    return MLPL_OK;
 }
 
 int ws_get(mlpl_ctx *ctx, WsSlot slot, size_t bytes, void **out) {
@@ -186,7 +231,7 @@ int mlpl_device_count(void) {
     return n;
 }
 
-int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
+int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) try {
     if (!out) return MLPL_E_BAD_INPUT;
     *out = nullptr;
     int n = 0;
@@ -231,7 +276,7 @@ int mlpl_ctx_create(int device_ordinal, mlpl_ctx **out) {
     }
     *out = ctx;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_ctx_create")
 
 void mlpl_ctx_destroy(mlpl_ctx *ctx) {
     if (!ctx) return;
@@ -320,7 +365,7 @@ int mlpl_debug_last_l2_match(mlpl_ctx *ctx, int out[4]) {
     return 4;
 }
 
-int mlpl_debug_hamming_stamps(mlpl_ctx *ctx, unsigned long long *out, int max_items) {
+int mlpl_debug_hamming_stamps(mlpl_ctx *ctx, unsigned long long *out, int max_items) try {
     if (!ctx || !out) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     MLPL_HIP_TRY(hipDeviceSynchronize());
@@ -334,7 +379,7 @@ int mlpl_debug_hamming_stamps(mlpl_ctx *ctx, unsigned long long *out, int max_it
     const int n = ctx->dbg_stamp_items < max_items ? ctx->dbg_stamp_items : max_items;
     if (n > 0 && ctx->ws[WS_DEBUG]) MLPL_HIP_TRY(hipMemcpy(out, ctx->ws[WS_DEBUG], (size_t)n * 32, hipMemcpyDeviceToHost));
     return n;
-}
+} MLPL_ENTRY_END("mlpl_debug_hamming_stamps")
 
 int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, long long *ws_grows) {
     if (!ctx) return MLPL_E_BAD_INPUT;
@@ -347,7 +392,7 @@ int mlpl_debug_hop_trace(mlpl_ctx *ctx, float *us, int *codes, int max_items, lo
     return n;
 }
 
-int mlpl_debug_hamming_clock(mlpl_ctx *ctx, unsigned long long *out, int max_items) {
+int mlpl_debug_hamming_clock(mlpl_ctx *ctx, unsigned long long *out, int max_items) try {
     if (!ctx || !out || max_items < 0) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     MLPL_HIP_TRY(hipDeviceSynchronize());
@@ -361,9 +406,9 @@ int mlpl_debug_hamming_clock(mlpl_ctx *ctx, unsigned long long *out, int max_ite
         std::memcpy(out + (size_t)i * 4, ring + (size_t)(launch % kClockRing) * 4, 32);
     }
     return n;
-}
+} MLPL_ENTRY_END("mlpl_debug_hamming_clock")
 
-int mlpl_profile_enable(mlpl_ctx *ctx, int on) {
+int mlpl_profile_enable(mlpl_ctx *ctx, int on) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     ctx->prof_on = on > 0 ? on : 0;  // N > 1: every Nth launch of a kernel is bracketed
     if (ctx->prof_on) {
@@ -375,16 +420,16 @@ int mlpl_profile_enable(mlpl_ctx *ctx, int on) {
         }
     }
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_profile_enable")
 
-int mlpl_profile_reset(mlpl_ctx *ctx) {
+int mlpl_profile_reset(mlpl_ctx *ctx) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipDeviceSynchronize());
     for (int k = 0; k < MLPL_PROF_NUM; ++k) ctx->prof_n[k] = ctx->prof_calls[k] = 0;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_profile_reset")
 
-int mlpl_profile_read(mlpl_ctx *ctx, int kernel_id, double *total_ms, int *launches) {
+int mlpl_profile_read(mlpl_ctx *ctx, int kernel_id, double *total_ms, int *launches) try {
     if (!ctx || kernel_id < 0 || kernel_id >= MLPL_PROF_NUM || !total_ms || !launches) return MLPL_E_BAD_INPUT;
     double tot = 0.0;
     const int n = ctx->prof_n[kernel_id];
@@ -397,16 +442,16 @@ int mlpl_profile_read(mlpl_ctx *ctx, int kernel_id, double *total_ms, int *launc
     *total_ms = tot;
     *launches = n;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_profile_read")
 
-int mlpl_debug_l2_flags(mlpl_ctx *ctx, int flags[4]) {
+int mlpl_debug_l2_flags(mlpl_ctx *ctx, int flags[4]) try {
     if (!ctx || !flags) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     MLPL_HIP_TRY(hipDeviceSynchronize());
     flags[0] = flags[1] = flags[2] = flags[3] = 0;
     if (ctx->l2_flag_ptr) MLPL_HIP_TRY(hipMemcpy(flags, ctx->l2_flag_ptr, 16, hipMemcpyDeviceToHost));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_debug_l2_flags")
 
 int mlpl_set_l2_path(mlpl_ctx *ctx, int mode) {
     if (!ctx || mode < 0 || mode > 3) return MLPL_E_BAD_INPUT;
@@ -420,47 +465,47 @@ int mlpl_set_l2_path(mlpl_ctx *ctx, int mode) {
 
 int mlpl_knn2_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_stride, size_t q_batch_stride,
                           const uint8_t *d_t, int nt, size_t t_stride, size_t t_batch_stride, int nbytes, int k,
-                          int batch, int32_t *d_idx, int32_t *d_dist, void *stream) {
+                          int batch, int32_t *d_idx, int32_t *d_dist, void *stream) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_knn_hamming(ctx, d_q, nq, q_stride, q_batch_stride, d_t, nt, t_stride, t_batch_stride, nbytes, k,
                               batch, d_idx, d_dist, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_knn2_hamming_dev")
 
 int mlpl_knn2_l2sq_f32_dev(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride,
                            const float *d_t, int nt, size_t t_stride, size_t t_batch_stride, int dim, int k, int batch,
-                           int32_t *d_idx, float *d_dist, void *stream) {
+                           int32_t *d_idx, float *d_dist, void *stream) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_knn_l2(ctx, d_q, nq, q_stride, q_batch_stride, d_t, nt, t_stride, t_batch_stride, dim, k, batch,
                          d_idx, d_dist, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_knn2_l2sq_f32_dev")
 
 int mlpl_ratio_compact_i32_dev(mlpl_ctx *ctx, const int32_t *d_idx, const int32_t *d_dist, int nq, int k, int batch,
-                               float ratio, mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) {
+                               float ratio, mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_ratio_compact(ctx, d_idx, d_dist, 0, nq, k, batch, ratio, d_out, d_n_out, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_ratio_compact_i32_dev")
 
 int mlpl_ratio_compact_f32_dev(mlpl_ctx *ctx, const int32_t *d_idx, const float *d_dist, int nq, int k, int batch,
-                               float ratio, mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) {
+                               float ratio, mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_ratio_compact(ctx, d_idx, d_dist, 1, nq, k, batch, ratio, d_out, d_n_out, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_ratio_compact_f32_dev")
 
 int mlpl_gather_match_points_dev(mlpl_ctx *ctx, const mlpl_dmatch *d_matches, int n, const float *d_kp1, const float *d_kp2,
-                                 const double K0[4], const double K1[4], double *d_p1, double *d_p2, void *stream) {
+                                 const double K0[4], const double K1[4], double *d_p1, double *d_p2, void *stream) try {
     if (!ctx || !d_matches || !d_kp1 || !d_kp2 || !K0 || !K1 || !d_p1 || !d_p2 || n < 0) {
         set_error("mlpl_gather_match_points_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_gather_match_points(d_matches, n, d_kp1, d_kp2, K0, K1, d_p1, d_p2, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_gather_match_points_dev")
 
-int mlpl_vfc_filter(mlpl_ctx *ctx, const float *x1, const float *x2, int n, uint32_t seed, uint8_t *keep, int *n_keep, double *P, int info[4]) {
+int mlpl_vfc_filter(mlpl_ctx *ctx, const float *x1, const float *x2, int n, uint32_t seed, uint8_t *keep, int *n_keep, double *P, int info[4]) try {
     if (!ctx || n < 0 || n > 65535 || (n > 0 && (!x1 || !x2 || !keep))) {
         set_error("mlpl_vfc_filter: bad arguments (n in [0, 65535])");
         return MLPL_E_INTERNAL;
@@ -488,11 +533,11 @@ int mlpl_vfc_filter(mlpl_ctx *ctx, const float *x1, const float *x2, int n, uint
     if (n_keep) *n_keep = res[1];
     if (info) info[0] = res[2], info[1] = res[3], info[2] = res[4], info[3] = res[5];
     return res[0];
-}
+} MLPL_ENTRY_END("mlpl_vfc_filter")
 
 int mlpl_vfc_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
                                 const float *d_kp1, int nq, const float *d_kp2, int nt, const uint32_t *seeds, int getmatches_rule,
-                                mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, void *stream) {
+                                mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, void *stream) try {
     if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
         nq < 1 || nt < 1 || !d_out || d_out == d_matches || !d_n_out || !d_status) {
         set_error("mlpl_vfc_filter_matches_dev: bad arguments (batch, match_stride in [1, 65535]; d_out apart from d_matches)");
@@ -501,10 +546,10 @@ int mlpl_vfc_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_m
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_vfc(ctx, batch, d_matches, match_stride, d_n_matches, d_kp1, nq, d_kp2, nt, nullptr, nullptr, 0, seeds, getmatches_rule, d_out,
                       d_n_out, d_status, nullptr, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_vfc_filter_matches_dev")
 
 int mlpl_gms_filter(mlpl_ctx *ctx, const float *kp1, int n1, int width1, int height1, const float *kp2, int n2, int width2, int height2,
-                    const mlpl_dmatch *matches, int n, int use_scale, int use_rotation, uint8_t *keep, int *n_keep, int info[4]) {
+                    const mlpl_dmatch *matches, int n, int use_scale, int use_rotation, uint8_t *keep, int *n_keep, int info[4]) try {
     if (!ctx || n < 0 || n > 65535 || n1 < 0 || n2 < 0 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 ||
         (n > 0 && (!kp1 || !kp2 || !matches || !keep))) {
         set_error("mlpl_gms_filter: bad arguments (n in [0, 65535], positive image sizes)");
@@ -539,12 +584,12 @@ int mlpl_gms_filter(mlpl_ctx *ctx, const float *kp1, int n1, int width1, int hei
     if (n_keep) *n_keep = res[0];
     if (info) info[0] = res[1], info[1] = res[2], info[2] = res[3], info[3] = 0;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_gms_filter")
 
 int mlpl_gms_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
                                 const float *d_kp1, int nq, const float *d_kp2, int nt, int width1, int height1, int width2, int height2,
                                 int use_scale, int use_rotation, int min_final_rule, mlpl_dmatch *d_out, int32_t *d_n_out,
-                                int32_t *d_n_inliers, void *stream) {
+                                int32_t *d_n_inliers, void *stream) try {
     if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
         nq < 1 || nt < 1 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 || !d_out || d_out == d_matches || !d_n_out ||
         !d_n_inliers) {
@@ -554,11 +599,11 @@ int mlpl_gms_filter_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_m
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_gms(ctx, batch, d_matches, match_stride, d_n_matches, 0, d_kp1, nq, d_kp2, nt, width1, height1, width2, height2, use_scale,
                       use_rotation, min_final_rule, d_out, d_n_out, d_n_inliers, nullptr, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_gms_filter_matches_dev")
 
 int mlpl_subpix_matches(mlpl_ctx *ctx, const uint8_t *img1, int width1, int height1, size_t step1, const uint8_t *img2, int width2, int height2,
                         size_t step2, const float *kp1, float *kp2, const float *size1, const float *size2, int n, uint8_t *inlier,
-                        int *n_refined, int *status, int info[4]) {
+                        int *n_refined, int *status, int info[4]) try {
     if (!ctx || n < 0 || n > 65535 || !img1 || !img2 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 || step1 < (size_t)width1 ||
         step2 < (size_t)width2 || (n > 0 && (!kp1 || !kp2 || !inlier))) {
         set_error("mlpl_subpix_matches: bad arguments (n in [0, 65535], 8-bit images of positive size, row step >= width)");
@@ -603,13 +648,13 @@ int mlpl_subpix_matches(mlpl_ctx *ctx, const uint8_t *img1, int width1, int heig
     if (status) *status = res[1];
     if (info) info[0] = res[2], info[1] = res[3], info[2] = res[4], info[3] = res[5];
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_subpix_matches")
 
 int mlpl_subpix_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
                             const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2,
                             const uint8_t *d_img1, int width1, int height1, size_t step1, size_t batch_stride1, const uint8_t *d_img2,
                             int width2, int height2, size_t step2, size_t batch_stride2, int max_side, int correspondences_rule,
-                            mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, float *d_kp2_out, uint8_t *d_inlier, void *stream) {
+                            mlpl_dmatch *d_out, int32_t *d_n_out, int32_t *d_status, float *d_kp2_out, uint8_t *d_inlier, void *stream) try {
     if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
         nq < 1 || nt < 1 || !d_img1 || !d_img2 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 || step1 < (size_t)width1 ||
         step2 < (size_t)width2 || max_side < 0 || max_side > 255 || !d_out || d_out == d_matches || !d_n_out || !d_status || !d_kp2_out) {
@@ -621,11 +666,11 @@ int mlpl_subpix_matches_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_match
     return launch_subpix(ctx, batch, d_matches, match_stride, d_n_matches, 0, d_kp1, nq, d_kp2, nt, d_size1, d_size2, d_img1, width1, height1,
                          step1, batch_stride1, d_img2, width2, height2, step2, batch_stride2, max_side, correspondences_rule, d_out, d_n_out,
                          d_status, d_kp2_out, d_inlier, nullptr, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_subpix_matches_dev")
 
 int mlpl_subpix_separate(mlpl_ctx *ctx, const uint8_t *img1, int width1, int height1, size_t step1, const uint8_t *img2, int width2, int height2,
                          size_t step2, float *kp1, float *kp2, const float *size1, const float *size2, int n, uint8_t *inlier, int32_t *iters,
-                         int *n_refined, int *status, int info[4]) {
+                         int *n_refined, int *status, int info[4]) try {
     if (!ctx || n < 0 || n > 65535 || !img1 || !img2 || width1 <= 0 || height1 <= 0 || width2 <= 0 || height2 <= 0 || step1 < (size_t)width1 ||
         step2 < (size_t)width2 || (n > 0 && (!kp1 || !kp2 || !inlier))) {
         set_error("mlpl_subpix_separate: bad arguments (n in [0, 65535], 8-bit images of positive size, row step >= width)");
@@ -680,13 +725,13 @@ int mlpl_subpix_separate(mlpl_ctx *ctx, const uint8_t *img1, int width1, int hei
     if (status) *status = res[1];
     if (info) info[0] = res[2], info[1] = res[3], info[2] = res[4], info[3] = res[5];
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_subpix_separate")
 
 int mlpl_subpix_separate_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matches, int match_stride, const int32_t *d_n_matches,
                              const float *d_kp1, int nq, const float *d_kp2, int nt, const float *d_size1, const float *d_size2,
                              const uint8_t *d_img1, int width1, int height1, size_t step1, size_t batch_stride1, const uint8_t *d_img2,
                              int width2, int height2, size_t step2, size_t batch_stride2, int correspondences_rule, mlpl_dmatch *d_out,
-                             int32_t *d_n_out, int32_t *d_status, float *d_kp1_out, float *d_kp2_out, uint8_t *d_inlier, void *stream) {
+                             int32_t *d_n_out, int32_t *d_status, float *d_kp1_out, float *d_kp2_out, uint8_t *d_inlier, void *stream) try {
     // the windows are taken on the device, so the image size rule is applied for the largest one: 2 * 10 + 5
     if (!ctx || batch < 1 || batch > 65535 || !d_matches || match_stride < 1 || match_stride > 65535 || !d_n_matches || !d_kp1 || !d_kp2 ||
         nq < 1 || nt < 1 || !d_img1 || !d_img2 || width1 < 25 || height1 < 25 || width2 < 25 || height2 < 25 || step1 < (size_t)width1 ||
@@ -699,12 +744,12 @@ int mlpl_subpix_separate_dev(mlpl_ctx *ctx, int batch, const mlpl_dmatch *d_matc
     return launch_subpix_separate(ctx, batch, d_matches, match_stride, d_n_matches, 0, d_kp1, nq, d_kp2, nt, d_size1, d_size2, d_img1, width1,
                                   height1, step1, batch_stride1, d_img2, width2, height2, step2, batch_stride2, correspondences_rule, d_out,
                                   d_n_out, d_status, d_kp1_out, d_kp2_out, d_inlier, nullptr, nullptr, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_subpix_separate_dev")
 
 int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_stride, size_t q_batch_stride,
                            const uint8_t *d_t, int nt, size_t t_stride, size_t t_batch_stride, int nbytes,
                            int ratio_test, float ratio, int batch, int32_t *d_idx, int32_t *d_dist, mlpl_dmatch *d_out,
-                           int32_t *d_n_out, void *stream) {
+                           int32_t *d_n_out, void *stream) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
@@ -719,11 +764,11 @@ int mlpl_match_hamming_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, size_t q_s
     if (rc) return rc;
     if (emit.emitted) return MLPL_OK;  // (the latency shape: the merge kernel wrote the matches and their number)
     return launch_ratio_compact(ctx, d_idx, d_dist, 0, nq, k, batch, ratio, d_out, d_n_out, s, (int32_t *)gc);
-}
+} MLPL_ENTRY_END("mlpl_match_hamming_dev")
 
 int mlpl_match_l2_dev(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride, const float *d_t, int nt,
                       size_t t_stride, size_t t_batch_stride, int dim, int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
-                      mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) {
+                      mlpl_dmatch *d_out, int32_t *d_n_out, void *stream) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
@@ -743,12 +788,12 @@ int mlpl_match_l2_dev(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, 
     rc = launch_ratio_compact(ctx, d_idx, d_dist, 1, nq, k, batch, ratio, d_out, d_n_out, s, counted ? (int32_t *)gc : nullptr);
     if (rc == MLPL_OK && nq > 0) ctx->dbg_l2_match[3] += counted ? 1 : 2;  // ratio_write_kernel [+ ratio_count_kernel]
     return rc;
-}
+} MLPL_ENTRY_END("mlpl_match_l2_dev")
 
 // (tests) the float knn with the fused fold alone: the counts the fold stored, read back
 int mlpl_debug_l2_fold_counts(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_stride, size_t q_batch_stride, const float *d_t, int nt,
                                size_t t_stride, size_t t_batch_stride, int dim, int ratio_test, float ratio, int batch, int32_t *d_idx, float *d_dist,
-                               int32_t *counts) {
+                               int32_t *counts) try {
     if (!ctx || !counts || nq < 1 || batch < 1 || batch > 65535) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     const int ncnt = (nq + kCountGroup - 1) / kCountGroup;
@@ -763,7 +808,7 @@ int mlpl_debug_l2_fold_counts(mlpl_ctx *ctx, const float *d_q, int nq, size_t q_
     MLPL_HIP_TRY(hipMemcpyAsync(counts, gc, (size_t)batch * ncnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     MLPL_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return counted ? batch * ncnt : 0;
-}
+} MLPL_ENTRY_END("mlpl_debug_l2_fold_counts")
 
 // ---------------------------------------------------------------------------------------------------------
 // host-pointer entry points: stage through the context workspace, run the device path, copy back
@@ -786,7 +831,7 @@ int upload_rows(mlpl_ctx *ctx, WsSlot slot, const void *host, int rows, size_t r
 }  // namespace
 
 int mlpl_knn2_hamming(mlpl_ctx *ctx, const uint8_t *q, int nq, size_t q_stride, const uint8_t *t, int nt, size_t t_stride,
-                      int nbytes, int k, int32_t *idx, int32_t *dist) {
+                      int nbytes, int k, int32_t *idx, int32_t *dist) try {
     if (!ctx || !q || !t || !idx || !dist || nq < 0 || nt < 0 || nbytes < 1 || q_stride < (size_t)nbytes ||
         t_stride < (size_t)nbytes || (k != 1 && k != 2) || nt < k) {
         set_error("mlpl_knn2_hamming: bad arguments");
@@ -807,10 +852,10 @@ int mlpl_knn2_hamming(mlpl_ctx *ctx, const uint8_t *q, int nq, size_t q_stride, 
     MLPL_HIP_TRY(hipMemcpyAsync(dist, ddist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     MLPL_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_knn2_hamming")
 
 int mlpl_knn2_l2sq_f32(mlpl_ctx *ctx, const float *q, int nq, size_t q_stride, const float *t, int nt, size_t t_stride,
-                       int dim, int k, int32_t *idx, float *dist) {
+                       int dim, int k, int32_t *idx, float *dist) try {
     if (!ctx || !q || !t || !idx || !dist || nq < 0 || nt < 0 || dim < 1 || q_stride < (size_t)dim ||
         t_stride < (size_t)dim || (k != 1 && k != 2) || nt < k) {
         set_error("mlpl_knn2_l2sq_f32: bad arguments");
@@ -831,7 +876,7 @@ int mlpl_knn2_l2sq_f32(mlpl_ctx *ctx, const float *q, int nq, size_t q_stride, c
     MLPL_HIP_TRY(hipMemcpyAsync(dist, ddist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     MLPL_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_knn2_l2sq_f32")
 
 static int ratio_compact_host(mlpl_ctx *ctx, const int32_t *idx, const void *dist, int is_float, int nq, int k,
                               float ratio, mlpl_dmatch *out, int *n_out) {
@@ -862,18 +907,18 @@ static int ratio_compact_host(mlpl_ctx *ctx, const int32_t *idx, const void *dis
 }
 
 int mlpl_ratio_compact_i32(mlpl_ctx *ctx, const int32_t *idx, const int32_t *dist, int nq, int k, float ratio,
-                           mlpl_dmatch *out, int *n_out) {
+                           mlpl_dmatch *out, int *n_out) try {
     return ratio_compact_host(ctx, idx, dist, 0, nq, k, ratio, out, n_out);
-}
+} MLPL_ENTRY_END("mlpl_ratio_compact_i32")
 
 int mlpl_ratio_compact_f32(mlpl_ctx *ctx, const int32_t *idx, const float *dist, int nq, int k, float ratio,
-                           mlpl_dmatch *out, int *n_out) {
+                           mlpl_dmatch *out, int *n_out) try {
     return ratio_compact_host(ctx, idx, dist, 1, nq, k, ratio, out, n_out);
-}
+} MLPL_ENTRY_END("mlpl_ratio_compact_f32")
 
 int mlpl_get_matches_linear(mlpl_ctx *ctx, int n_keypoints1, int n_keypoints2, const void *desc1, int rows1, size_t step1,
                             const void *desc2, int rows2, size_t step2, int cols, int desc_type, int ratio_test,
-                            mlpl_dmatch *out, int *n_out) {
+                            mlpl_dmatch *out, int *n_out) try {
     if (!ctx || !n_out) return MLPL_E_BAD_INPUT;
     *n_out = 0;
     // reference matchers.cpp:123-133
@@ -912,11 +957,11 @@ int mlpl_get_matches_linear(mlpl_ctx *ctx, int n_keypoints1, int n_keypoints2, c
     *n_out = cnt;
     if (cnt < 2) return MLPL_E_FAILED;  // matchers.cpp:709-713 (MIN_FINAL_MATCHES = 2)
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_get_matches_linear")
 
 int mlpl_get_matches_bruteforce_nms(mlpl_ctx *ctx, int n_keypoints1, int n_keypoints2, const void *desc1, int rows1,
                                     size_t step1, const void *desc2, int rows2, size_t step2, int cols, int desc_type,
-                                    int ratio_test, mlpl_dmatch *out, int *n_out) {
+                                    int ratio_test, mlpl_dmatch *out, int *n_out) try {
     if (!ctx || !n_out) return MLPL_E_BAD_INPUT;
     *n_out = 0;
     if (n_keypoints1 < 15 || n_keypoints2 < 15) return MLPL_E_FEW_KEYPOINTS;                 // matchers.cpp:123-127
@@ -958,6 +1003,6 @@ int mlpl_get_matches_bruteforce_nms(mlpl_ctx *ctx, int n_keypoints1, int n_keypo
     if (cnt > 0) MLPL_HIP_TRY(hipMemcpy(out, dout, (size_t)cnt * sizeof(mlpl_dmatch), hipMemcpyDeviceToHost));
     *n_out = cnt;
     return MLPL_OK;  // no minimum-match check on this branch of getMatches
-}
+} MLPL_ENTRY_END("mlpl_get_matches_bruteforce_nms")
 
 }  // extern "C"

@@ -356,16 +356,12 @@ inline int linear_refine_batch(mlpl_ctx *ctx, int B, const double *d_p1, const d
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    if (!counts_in_range(who, B, counts, 0, stride)) return MLPL_E_BAD_INPUT;
+    for (int b = 0; b < B; ++b)
         if (!(th[b] > 0) || !std::isfinite(th[b])) {
             set_error("%s: th[%d] must be positive and finite", who, b);
             return MLPL_E_BAD_INPUT;
         }
-    }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     void *d_prob, *d_lists, *d_work;
     const size_t prob_bytes = (size_t)B * sizeof(LinRefineProb);
@@ -411,11 +407,7 @@ inline int recover_pose_batch(mlpl_ctx *ctx, int B, const double *d_p1, const do
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
-    for (int b = 0; b < B; ++b)
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    if (!counts_in_range(who, B, counts, 0, stride)) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     int rc;
     void *d_small, *d_cmask, *d_ones = nullptr;

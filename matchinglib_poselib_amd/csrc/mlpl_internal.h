@@ -15,6 +15,16 @@ namespace mlpl {
 
 void set_error(const char *fmt, ...);
 
+// The guard of the C boundary.  Every entry is a function-try-block,
+//     int mlpl_x(...) try { body } MLPL_ENTRY_END("mlpl_x")
+// and entry_failed, called from its handler, rethrows the exception in flight and turns it into an error: std::bad_alloc ->
+// MLPL_E_NOMEM, anything else -> MLPL_E_INTERNAL, the text names the entry.  Nothing leaves it.
+int entry_failed(const char *who) noexcept;
+#define MLPL_ENTRY_END(who) catch (...) { return ::mlpl::entry_failed(who); }
+
+// counts[b] in [lo, stride] for every problem of a batch entry; otherwise the error is set and the answer is false
+bool counts_in_range(const char *who, int n_problems, const int32_t *counts, int lo, int stride);
+
 #define MLPL_HIP_TRY(expr)                                                                                  \
     do {                                                                                                    \
         hipError_t e__ = (expr);                                                                            \
@@ -235,6 +245,13 @@ int ws_get(mlpl_ctx *ctx, WsSlot slot, size_t bytes, void **out);
 int pinned_get(mlpl_ctx *ctx, size_t bytes, void **out);
 int pinned_batch_get(mlpl_ctx *ctx, size_t bytes, void **out);
 void hub_streams_free(void *p);
+
+// The correspondences of a host-pointer entry on the device: p1 -> WS_AUX0, p2 -> WS_AUX1 (n x 2 doubles each, sized for max(n, 1)), copied
+// on ctx->stream when n > 0.  match_bytes > 0: *d_match = WS_MATCH with that many bytes (the entry's mask or labels; the entry fills it).
+int upload_points(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double **d_p1, const double **d_p2, size_t match_bytes = 0,
+                  void **d_match = nullptr);
+// ... and a mask of n bytes back to the host once the entry's work on the stream is done (a blocking copy)
+int download_mask(uint8_t *mask, const void *d_mask, int n);
 
 constexpr int kProfMaxLaunches = 2048;
 constexpr int kClockRing = 256;  // launches the Hamming clock ring keeps

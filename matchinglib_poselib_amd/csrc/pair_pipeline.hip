@@ -74,22 +74,22 @@ using namespace mlpl;
 
 extern "C" int mlpl_pair_pose_dev(mlpl_ctx *ctx, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                                   const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters,
-                                  double confidence, int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream) {
+                                  double confidence, int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream) try {
     if (!ctx || !d_q || !d_t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || nq < 1 || nt < 2 || nbytes < 1) {
         set_error("mlpl_pair_pose_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return pair_pose_one(ctx, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, max_iters, confidence, refit, seed, dist, out, stream);
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_dev")
 
 extern "C" int mlpl_pair_pose_f32_dev(mlpl_ctx *ctx, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
                                       const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters,
-                                      double confidence, int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream) {
+                                      double confidence, int refit, uint32_t seed, double dist, mlpl_pair_result *out, void *stream) try {
     if (!ctx || !d_q || !d_t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || nq < 1 || nt < 2 || dim < 1 || dim > 1024) {
         set_error("mlpl_pair_pose_f32_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return pair_pose_one(ctx, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, max_iters, confidence, refit, seed, dist, out, stream);
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_f32_dev")

@@ -126,7 +126,7 @@ using namespace mlpl;
 
 extern "C" {
 
-int mlpl_img_to_cam(mlpl_ctx *ctx, float *pts, int n, const double K[4]) {
+int mlpl_img_to_cam(mlpl_ctx *ctx, float *pts, int n, const double K[4]) try {
     if (!ctx || !pts || !K || n < 0) return MLPL_E_BAD_INPUT;
     if (n == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
@@ -139,10 +139,10 @@ int mlpl_img_to_cam(mlpl_ctx *ctx, float *pts, int n, const double K[4]) {
     MLPL_HIP_TRY(hipMemcpyAsync(pts, d, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_img_to_cam")
 
 int mlpl_remove_lens_dist(mlpl_ctx *ctx, float *points1, float *points2, int n, const double dist1[8], const double dist2[8],
-                          int *n_out) {
+                          int *n_out) try {
     if (!ctx || !points1 || !points2 || !dist1 || !dist2 || !n_out || n < 0) return MLPL_E_BAD_INPUT;
     *n_out = n;
     double s1 = 0, s2 = 0;
@@ -182,29 +182,27 @@ int mlpl_remove_lens_dist(mlpl_ctx *ctx, float *points1, float *points2, int n, 
     MLPL_HIP_TRY(hipMemcpy(points2, o2, (size_t)n1 * 8, hipMemcpyDeviceToHost));
     *n_out = n1;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_remove_lens_dist")
 
 int mlpl_get_inliers_strict(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double E[9], double th2, double *err,
-                            uint8_t *mask) {
+                            uint8_t *mask) try {
     if (!ctx || !p1 || !p2 || !E || !err || !mask || n < 0) return MLPL_E_BAD_INPUT;
     if (n == 0) return 0;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *d1, *d2, *de, *dm, *dsmall;
+    const double *d1, *d2;
+    void *de, *dm, *dsmall;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &d1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &d2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &d1, &d2))) return rc;
     if ((rc = ws_get(ctx, WS_AUX5, (size_t)n * 8, &de))) return rc;
     if ((rc = ws_get(ctx, WS_AUX6, (size_t)n, &dm))) return rc;
     if ((rc = ws_get(ctx, WS_AUX2, 4096, &dsmall))) return rc;
     double *dE = (double *)dsmall;
     int32_t *dcnt = (int32_t *)(dE + 16);
-    MLPL_HIP_TRY(hipMemcpyAsync(d1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(d2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dE, E, 72, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemsetAsync(dcnt, 0, 4, s));
-    hipLaunchKernelGGL(inliers_strict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const double *)d1, (const double *)d2, n,
-                       (const double *)dE, th2, (double *)de, (uint8_t *)dm, dcnt);
+    hipLaunchKernelGGL(inliers_strict_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d1, d2, n, (const double *)dE, th2, (double *)de, (uint8_t *)dm,
+                       dcnt);
     MLPL_HIP_TRY(hipGetLastError());
     int32_t cnt = 0;
     MLPL_HIP_TRY(hipMemcpyAsync(err, de, (size_t)n * 8, hipMemcpyDeviceToHost, s));
@@ -212,6 +210,6 @@ int mlpl_get_inliers_strict(mlpl_ctx *ctx, const double *p1, const double *p2, i
     MLPL_HIP_TRY(hipMemcpyAsync(&cnt, dcnt, 4, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return cnt;
-}
+} MLPL_ENTRY_END("mlpl_get_inliers_strict")
 
 }  // extern "C"

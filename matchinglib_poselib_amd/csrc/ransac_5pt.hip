@@ -51,6 +51,7 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -3336,7 +3337,7 @@ extern "C" {
 // the hub's hand-over -- announce, block until the generation advances -- against a stand-in hub on the calling thread that releases a
 // round once every fiber has announced.  Returns the number of hand-overs completed (n * rounds when the scheduler works), -1 on bad
 // arguments.  tests/test_fiber_scheduler.py runs it without a GPU, also with far more fibers than workers and than host cores.
-long long mlpl_debug_fiber_selftest(int n, int workers, int rounds) {
+long long mlpl_debug_fiber_selftest(int n, int workers, int rounds) try {
     if (n < 1 || n > 4096 || workers < 1 || workers > 256 || rounds < 1 || rounds > 100000) return -1;
     HubThreads pool;
     std::atomic<int> pending{n};
@@ -3373,7 +3374,19 @@ long long mlpl_debug_fiber_selftest(int n, int workers, int rounds) {
     for (int k = 0; k < n; ++k)
         if (order_seen[(size_t)k] != rounds) return -2;
     return done.load();
+} catch (...) {
+    entry_failed("mlpl_debug_fiber_selftest");
+    return -1;
 }
+
+// The guard of the C boundary by itself (no GPU, no context): a guarded body that returns 7 (kind 0), throws std::bad_alloc (1), a
+// std::runtime_error (2) or an int (3).  tests/test_entry_guard.py checks the codes and texts that come back.
+int mlpl_debug_entry_guard(int kind) try {
+    if (kind == 1) throw std::bad_alloc();
+    if (kind == 2) throw std::runtime_error("entry guard self-test");
+    if (kind == 3) throw 3;
+    return 7;
+} MLPL_ENTRY_END("mlpl_debug_entry_guard")
 
 int mlpl_ransac_last_stats(mlpl_ctx *ctx, long long stats[2]) {
     if (!ctx || !stats) return MLPL_E_BAD_INPUT;
@@ -3389,7 +3402,7 @@ int mlpl_debug_ransac_draw(mlpl_ctx *ctx, long long out[2]) {
     return MLPL_OK;
 }
 
-int mlpl_debug_eig9(mlpl_ctx *ctx, const double *G, const double *start, int count, double *out12, double *jacobi10) {
+int mlpl_debug_eig9(mlpl_ctx *ctx, const double *G, const double *start, int count, double *out12, double *jacobi10) try {
     if (!ctx || !G || !out12 || !jacobi10 || count < 1 || count > (1 << 20)) {
         set_error("mlpl_debug_eig9: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -3410,9 +3423,9 @@ int mlpl_debug_eig9(mlpl_ctx *ctx, const double *G, const double *start, int cou
     MLPL_HIP_TRY(hipMemcpyAsync(jacobi10, dJ, (size_t)count * 10 * 8, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_debug_eig9")
 
-int mlpl_debug_dk_stats(mlpl_ctx *ctx, int enable, int stats[16]) {
+int mlpl_debug_dk_stats(mlpl_ctx *ctx, int enable, int stats[16]) try {
     if (!ctx) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     MLPL_HIP_TRY(hipDeviceSynchronize());
@@ -3422,10 +3435,10 @@ int mlpl_debug_dk_stats(mlpl_ctx *ctx, int enable, int stats[16]) {
     const int z[16] = {0, 0, 0, enable ? 1 : 0};
     MLPL_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dk_iters_dbg), z, sizeof(z)));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_debug_dk_stats")
 
 int mlpl_solve_5pt(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *samples, int n_samples,
-                   double *E_out, int32_t *n_models) {
+                   double *E_out, int32_t *n_models) try {
     if (!ctx || !p1 || !p2 || !samples || !E_out || !n_models || n < 5 || n_samples < 0) {
         set_error("mlpl_solve_5pt: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -3438,18 +3451,15 @@ int mlpl_solve_5pt(mlpl_ctx *ctx, const double *p1, const double *p2, int n, con
     if (n_samples == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2;
+    const double *dp1, *dp2;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     RansacBuffers B;
     if ((rc = alloc_ransac(ctx, n_samples, B))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(B.samples, samples, (size_t)n_samples * 20, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemsetAsync(B.E_tab, 0, (size_t)n_samples * 720, s));
     prof_mark(ctx, MLPL_PROF_SOLVE_5PT, 0, s);
-    launch_solve5pt(ctx, n_samples, s, (const double *)dp1, (const double *)dp2, B.samples, 0, n_samples, B.recs);
+    launch_solve5pt(ctx, n_samples, s, dp1, dp2, B.samples, 0, n_samples, B.recs);
     MLPL_LAUNCH_ROOTS(ctx->opt_solver_polish, dim3((n_samples + kHypPerWave - 1) / kHypPerWave), s, (const PolyRec *)B.recs, 0, n_samples,
                       B.E_tab, B.n_models, (double *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
     prof_mark(ctx, MLPL_PROF_SOLVE_5PT, 1, s);
@@ -3458,7 +3468,7 @@ int mlpl_solve_5pt(mlpl_ctx *ctx, const double *p1, const double *p2, int n, con
     MLPL_HIP_TRY(hipMemcpyAsync(n_models, B.n_models, (size_t)n_samples * 4, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_solve_5pt")
 
 // err_sum == NULL: count-only (division-free) kernels with the squared threshold given as is; shape 1 / 2 forces the
 // 4-lanes-per-model / block-per-model kernel (tests), 0 = automatic.
@@ -3467,18 +3477,16 @@ static int score_models_impl(mlpl_ctx *ctx, const double *p1, const double *p2, 
     if (n_models == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2, *dE, *dgood, *dsum;
+    const double *dp1, *dp2;
+    void *dE, *dgood, *dsum;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     if ((rc = ws_get(ctx, WS_AUX5, (size_t)n_models * 72, &dE))) return rc;
     if ((rc = ws_get(ctx, WS_AUX6, (size_t)n_models * 8, &dsum))) return rc;
     if ((rc = ws_get(ctx, WS_AUX7, (size_t)n_models * 4, &dgood))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dE, E, (size_t)n_models * 72, hipMemcpyHostToDevice, s));
     double4 *pts;
-    if ((rc = pack_points(ctx, (const double *)dp1, (const double *)dp2, n, &pts, s))) return rc;
+    if ((rc = pack_points(ctx, dp1, dp2, n, &pts, s))) return rc;
     prof_mark(ctx, MLPL_PROF_SCORE, 0, s);
     const double qmax = inlier_bound(thresh2);
     if (shape == 1 && !err_sum) {   // the large-pass instance the options select, one workgroup per model group (stores)
@@ -3506,27 +3514,27 @@ static int score_models_impl(mlpl_ctx *ctx, const double *p1, const double *p2, 
 }
 
 int mlpl_score_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_models, double thresh,
-                      int32_t *count, double *err_sum) {
+                      int32_t *count, double *err_sum) try {
     if (!ctx || !p1 || !p2 || !E || !count || !err_sum || n < 1 || n_models < 0) {
         set_error("mlpl_score_models: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     return score_models_impl(ctx, p1, p2, n, E, n_models, thresh * thresh, count, err_sum, 0);
-}
+} MLPL_ENTRY_END("mlpl_score_models")
 
 int mlpl_count_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_models, double thresh2, int shape,
-                      int32_t *count) {
+                      int32_t *count) try {
     if (!ctx || !p1 || !p2 || !E || !count || n < 1 || n_models < 0 || shape < 0 || shape > 2) {
         set_error("mlpl_count_models: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     return score_models_impl(ctx, p1, p2, n, E, n_models, thresh2, count, nullptr, shape);
-}
+} MLPL_ENTRY_END("mlpl_count_models")
 
 // The count-only pass exactly as a RANSAC pass runs it (tests): packed points, a dense model list of n_bound rows of which the first n_live
 // are live (the rest NaN), the live count read on the device, counts scattered through ids into the caller's table.
 int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_live, int n_bound,
-                          const int32_t *ids, int table_len, double thresh2, int point_splits, int32_t *table_inout) {
+                          const int32_t *ids, int table_len, double thresh2, int point_splits, int32_t *table_inout) try {
     if (!ctx || !p1 || !p2 || !E || !table_inout || n < 1 || n_live < 0 || n_bound < 1 || n_live > n_bound || table_len < 1 ||
         point_splits < -1 || point_splits > 1024 || (!ids && n_live > table_len)) {
         set_error("mlpl_debug_count_pass: bad arguments");
@@ -3540,10 +3548,10 @@ int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int
             }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2, *dE, *dids, *dtab;
+    const double *dp1, *dp2;
+    void *dE, *dids, *dtab;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     if ((rc = ws_get(ctx, WS_AUX5, (size_t)n_bound * 72, &dE))) return rc;
     if ((rc = ws_get(ctx, WS_AUX6, (size_t)(n_bound + 1) * 4, &dids))) return rc;   // [0] = live count, then the ids
     if ((rc = ws_get(ctx, WS_AUX7, (size_t)table_len * 4, &dtab))) return rc;
@@ -3552,13 +3560,11 @@ int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int
     std::vector<int32_t> hids((size_t)n_bound + 1, 0);
     hids[0] = n_live;
     for (int i = 0; i < n_live; ++i) hids[1 + i] = ids ? ids[i] : i;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dE, Epad.data(), (size_t)n_bound * 72, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dids, hids.data(), (size_t)(n_bound + 1) * 4, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dtab, table_inout, (size_t)table_len * 4, hipMemcpyHostToDevice, s));
     double4 *pts;
-    if ((rc = pack_points(ctx, (const double *)dp1, (const double *)dp2, n, &pts, s))) return rc;
+    if ((rc = pack_points(ctx, dp1, dp2, n, &pts, s))) return rc;
     const int splits = point_splits < 0 ? score_point_splits(n, n_bound, false, ctx->opt_ransac_count_tiles) : point_splits;
     const int32_t *d_total = (const int32_t *)dids;
     ctx->dbg_count_kernel[0] = launch_score(s, (const double4 *)pts, n, (const double *)dE, d_total + 1, d_total, 0, n_bound, thresh2,
@@ -3570,11 +3576,11 @@ int mlpl_debug_count_pass(mlpl_ctx *ctx, const double *p1, const double *p2, int
     MLPL_HIP_TRY(hipMemcpyAsync(table_inout, dtab, (size_t)table_len * 4, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_debug_count_pass")
 
 int mlpl_ransac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double thresh, double confidence,
                               int max_iters, int refit, uint32_t seed, double E[9], uint8_t *d_mask, int *n_inliers,
-                              int *iters_used, void *stream) {
+                              int *iters_used, void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !E || !d_mask || n < 6 || max_iters < 1 || !(thresh > 0)) {
         set_error("mlpl_ransac_essential: bad arguments (n=%d max_iters=%d); n must exceed the 5 model points", n, max_iters);
         return MLPL_E_BAD_INPUT;
@@ -3854,31 +3860,27 @@ int mlpl_ransac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d
     std::memcpy(E, fin.E, 72);
     if (n_inliers) *n_inliers = fin.maxGood;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_ransac_essential_dev")
 
 int mlpl_ransac_essential(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double thresh, double confidence,
                           int max_iters, int refit, uint32_t seed, double E[9], uint8_t *mask, int *n_inliers,
-                          int *iters_used) {
+                          int *iters_used) try {
     if (!ctx || !p1 || !p2 || !E || !mask || n < 6) {
         set_error("mlpl_ransac_essential: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dmask;
+    const double *dp1, *dp2;
+    void *dmask;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n, &dmask))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    rc = mlpl_ransac_essential_dev(ctx, (const double *)dp1, (const double *)dp2, n, thresh, confidence, max_iters, refit,
-                                   seed, E, (uint8_t *)dmask, n_inliers, iters_used, ctx->stream);
-    if (rc) return rc;
-    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
-    return MLPL_OK;
-}
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n, &dmask))) return rc;
+    rc = mlpl_ransac_essential_dev(ctx, dp1, dp2, n, thresh, confidence, max_iters, refit, seed, E, (uint8_t *)dmask, n_inliers, iters_used,
+                                   ctx->stream);
+    if (rc) return rc;  // no model: the caller's mask stays as it came
+    return download_mask(mask, dmask, n);
+} MLPL_ENTRY_END("mlpl_ransac_essential")
 
-int mlpl_median_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_models, double *median) {
+int mlpl_median_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double *E, int n_models, double *median) try {
     if (!ctx || !p1 || !p2 || !E || !median || n < 1 || n_models < 0) {
         set_error("mlpl_median_models: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -3886,17 +3888,15 @@ int mlpl_median_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n,
     if (n_models == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2, *dE, *dmed;
+    const double *dp1, *dp2;
+    void *dE, *dmed;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     if ((rc = ws_get(ctx, WS_AUX5, (size_t)n_models * 72, &dE))) return rc;
     if ((rc = ws_get(ctx, WS_AUX6, (size_t)n_models * 8, &dmed))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dE, E, (size_t)n_models * 72, hipMemcpyHostToDevice, s));
     double4 *pts;
-    if ((rc = pack_points(ctx, (const double *)dp1, (const double *)dp2, n, &pts, s))) return rc;
+    if ((rc = pack_points(ctx, dp1, dp2, n, &pts, s))) return rc;
     if (n <= kScoreBlockMaxN)
         hipLaunchKernelGGL(median_kernel<true>, dim3(n_models), dim3(256), (size_t)n * 4, s, (const double4 *)pts, n, (const double *)dE,
                            (const int32_t *)nullptr, (const int32_t *)nullptr, n_models, (double *)dmed);
@@ -3907,10 +3907,10 @@ int mlpl_median_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n,
     MLPL_HIP_TRY(hipMemcpyAsync(median, dmed, (size_t)n_models * 8, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_median_models")
 
 int mlpl_lmeds_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double confidence, int max_iters,
-                             uint32_t seed, double E[9], uint8_t *d_mask, int *n_inliers, double *min_median, void *stream) {
+                             uint32_t seed, double E[9], uint8_t *d_mask, int *n_inliers, double *min_median, void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !E || !d_mask || n < 6 || max_iters < 1 || !(confidence > 0 && confidence < 1)) {
         set_error("mlpl_lmeds_essential: bad arguments (n=%d max_iters=%d); n must exceed the 5 model points", n, max_iters);
         return MLPL_E_BAD_INPUT;
@@ -3985,85 +3985,68 @@ int mlpl_lmeds_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_
         return MLPL_E_FAILED;
     }
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_lmeds_essential_dev")
 
 int mlpl_lmeds_essential(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double confidence, int max_iters,
-                         uint32_t seed, double E[9], uint8_t *mask, int *n_inliers, double *min_median) {
+                         uint32_t seed, double E[9], uint8_t *mask, int *n_inliers, double *min_median) try {
     if (!ctx || !p1 || !p2 || !E || !mask || n < 6) {
         set_error("mlpl_lmeds_essential: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dmask;
+    const double *dp1, *dp2;
+    void *dmask;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n, &dmask))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    rc = mlpl_lmeds_essential_dev(ctx, (const double *)dp1, (const double *)dp2, n, confidence, max_iters, seed, E,
-                                  (uint8_t *)dmask, n_inliers, min_median, ctx->stream);
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n, &dmask))) return rc;
+    rc = mlpl_lmeds_essential_dev(ctx, dp1, dp2, n, confidence, max_iters, seed, E, (uint8_t *)dmask, n_inliers, min_median, ctx->stream);
     // the mask is meaningful whenever a model was found, also when the inlier count fails the final test
     if (rc && rc != MLPL_E_FAILED) return rc;
-    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
-    return rc;
-}
+    const int rc_mask = download_mask(mask, dmask, n);
+    return rc_mask ? rc_mask : rc;
+} MLPL_ENTRY_END("mlpl_lmeds_essential")
 
 int mlpl_arrsac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double thresh, int refine,
-                              uint64_t rng_state[2], double E[9], uint8_t *d_mask, int *n_inliers, void *stream) {
+                              uint64_t rng_state[2], double E[9], uint8_t *d_mask, int *n_inliers, void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !E || !d_mask || !rng_state || n < 6 || !(thresh > 0)) {
         set_error("mlpl_arrsac_essential_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return arrsac_essential_dev(ctx, d_p1, d_p2, n, thresh, refine, rng_state, E, d_mask, n_inliers, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_arrsac_essential_dev")
 
 int mlpl_arrsac_essential(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double thresh, int refine, uint64_t rng_state[2],
-                          double E[9], uint8_t *mask, int *n_inliers) {
+                          double E[9], uint8_t *mask, int *n_inliers) try {
     if (!ctx || !p1 || !p2 || !E || !mask || !rng_state || n < 6 || !(thresh > 0)) {
         set_error("mlpl_arrsac_essential: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dmask;
+    const double *dp1, *dp2;
+    void *dmask;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n, &dmask))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    rc = arrsac_essential_dev(ctx, (const double *)dp1, (const double *)dp2, n, thresh, refine, rng_state, E, (uint8_t *)dmask, n_inliers,
-                              ctx->stream);
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n, &dmask))) return rc;
+    rc = arrsac_essential_dev(ctx, dp1, dp2, n, thresh, refine, rng_state, E, (uint8_t *)dmask, n_inliers, ctx->stream);
     // the mask is meaningful whenever a hypothesis was found, also when its inlier count fails the final test
     if (rc && !(rc == MLPL_E_FAILED && n_inliers && *n_inliers > 0)) return rc;
-    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
-    return rc;
-}
+    const int rc_mask = download_mask(mask, dmask, n);
+    return rc_mask ? rc_mask : rc;
+} MLPL_ENTRY_END("mlpl_arrsac_essential")
 
 int mlpl_arrsac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double thresh,
-                                    int refine, uint64_t *rng_states, double *E, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, void *stream) {
+                                    int refine, uint64_t *rng_states, double *E, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, void *stream) try {
     if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || !E || !d_masks || !status || !(thresh > 0)) {
         set_error("mlpl_arrsac_essential_batch_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
-    for (int b = 0; b < n_problems; ++b)
-        if (counts[b] < 6 || counts[b] > stride) {
-            set_error("mlpl_arrsac_essential_batch_dev: problem %d has %d correspondences (6 ... stride %d)", b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    if (!counts_in_range("mlpl_arrsac_essential_batch_dev", n_problems, counts, 6, stride)) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return arrsac_essential_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, thresh, refine, rng_states, E, d_masks, n_inliers, status,
-                                          pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_arrsac_essential_batch_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return arrsac_essential_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, thresh, refine, rng_states, E, d_masks, n_inliers, status,
+                                      pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_arrsac_essential_batch_dev")
 
 int mlpl_arrsac_sample_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *idx, int m, int kind, double thresh,
-                              double *E_out, int32_t *n_models, uint8_t *valid) {
+                              double *E_out, int32_t *n_models, uint8_t *valid) try {
     if (!ctx || !p1 || !p2 || !idx || !E_out || !n_models || !valid || n < 5 || m < 5 || m > kArrMaxSample || (kind != 0 && kind != 1) ||
         (kind == 0 && m > 7) || (kind == 1 && m < 8) || !(thresh > 0)) {
         set_error("mlpl_arrsac_sample_models: bad arguments");
@@ -4075,85 +4058,61 @@ int mlpl_arrsac_sample_models(mlpl_ctx *ctx, const double *p1, const double *p2,
             return MLPL_E_BAD_INPUT;
         }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2;
+    const double *dp1, *dp2;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    return arrsac_sample_models(ctx, (const double *)dp1, (const double *)dp2, n, idx, m, kind, thresh, E_out, n_models, valid, ctx->stream);
-}
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
+    return arrsac_sample_models(ctx, dp1, dp2, n, idx, m, kind, thresh, E_out, n_models, valid, ctx->stream);
+} MLPL_ENTRY_END("mlpl_arrsac_sample_models")
 
 // ---- plane-induced homographies (homography_impl.h) ----
-static int homography_upload(mlpl_ctx *ctx, const double *p1, const double *p2, int n, void **dp1, void **dp2, void **dmask) {
-    int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, dp2))) return rc;
-    if (dmask && (rc = ws_get(ctx, WS_MATCH, (size_t)n, dmask))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(*dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    MLPL_HIP_TRY(hipMemcpyAsync(*dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    return MLPL_OK;
-}
-
 int mlpl_homography_arrsac_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, uint64_t rng_state[2], double H[9],
-                               uint8_t *d_mask, int *n_inliers, long long stats[12], void *stream) {
+                               uint8_t *d_mask, int *n_inliers, long long stats[12], void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !H || !d_mask || !rng_state || n < 1 || !(th > 0) || !std::isfinite(th)) {
         set_error("mlpl_homography_arrsac_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return homography_arrsac_dev(ctx, d_p1, d_p2, n, th, rng_state, H, d_mask, n_inliers, stats, pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_homography_arrsac_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return homography_arrsac_dev(ctx, d_p1, d_p2, n, th, rng_state, H, d_mask, n_inliers, stats, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_homography_arrsac_dev")
 
 int mlpl_homography_arrsac(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, uint64_t rng_state[2], double H[9], uint8_t *mask,
-                           int *n_inliers, long long stats[12]) {
+                           int *n_inliers, long long stats[12]) try {
     if (!ctx || !p1 || !p2 || !H || !mask || !rng_state || n < 1 || !(th > 0) || !std::isfinite(th)) {
         set_error("mlpl_homography_arrsac: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dmask;
+    const double *dp1, *dp2;
+    void *dmask;
     int rc;
-    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, &dmask))) return rc;
-    try {
-        rc = homography_arrsac_dev(ctx, (const double *)dp1, (const double *)dp2, n, th, rng_state, H, (uint8_t *)dmask, n_inliers, stats, ctx->stream);
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_homography_arrsac: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-    if (rc) return rc;
-    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
-    return rc;
-}
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n, &dmask))) return rc;
+    if ((rc = homography_arrsac_dev(ctx, dp1, dp2, n, th, rng_state, H, (uint8_t *)dmask, n_inliers, stats, ctx->stream))) return rc;
+    return download_mask(mask, dmask, n);
+} MLPL_ENTRY_END("mlpl_homography_arrsac")
 
 int mlpl_homography_inliers_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const double H[9], double th, uint8_t *d_mask,
-                                int *n_inliers, void *stream) {
+                                int *n_inliers, void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !H || !d_mask || n < 1 || !(th > 0)) {
         set_error("mlpl_homography_inliers_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return homography_inliers_dev(ctx, d_p1, d_p2, n, H, th, d_mask, n_inliers, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_homography_inliers_dev")
 
-int mlpl_homography_inliers(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double H[9], double th, uint8_t *mask, int *n_inliers) {
+int mlpl_homography_inliers(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const double H[9], double th, uint8_t *mask, int *n_inliers) try {
     if (!ctx || !p1 || !p2 || !H || !mask || n < 1 || !(th > 0)) {
         set_error("mlpl_homography_inliers: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dmask;
+    const double *dp1, *dp2;
+    void *dmask;
     int rc;
-    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, &dmask))) return rc;
-    if ((rc = homography_inliers_dev(ctx, (const double *)dp1, (const double *)dp2, n, H, th, (uint8_t *)dmask, n_inliers, ctx->stream))) return rc;
-    MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
-    return MLPL_OK;
-}
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n, &dmask))) return rc;
+    if ((rc = homography_inliers_dev(ctx, dp1, dp2, n, H, th, (uint8_t *)dmask, n_inliers, ctx->stream))) return rc;
+    return download_mask(mask, dmask, n);
+} MLPL_ENTRY_END("mlpl_homography_inliers")
 
 static bool mult_homographies_args_ok(mlpl_ctx *ctx, const void *p1, const void *p2, int n, double th, const uint64_t *rng_state, int cap,
                                       const int *n_planes, const double *H, const int32_t *num_inl, const double *strength, const double *th_used) {
@@ -4162,20 +4121,15 @@ static bool mult_homographies_args_ok(mlpl_ctx *ctx, const void *p1, const void 
 
 int mlpl_mult_homographies_labels_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
                                       unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl,
-                                      double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, uint8_t *d_masks, void *stream) {
+                                      double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, uint8_t *d_masks, void *stream) try {
     if (!mult_homographies_args_ok(ctx, d_p1, d_p2, n, th, rng_state, cap, n_planes, H, num_inl, strength, th_used)) {
         set_error("mlpl_mult_homographies_dev: bad arguments (n must exceed 3, cap 0)");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return mult_homographies_dev(ctx, d_p1, d_p2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H, num_inl, strength, th_used,
-                                     d_masks, d_labels, found_at, pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_mult_homographies_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return mult_homographies_dev(ctx, d_p1, d_p2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H, num_inl, strength, th_used,
+                                 d_masks, d_labels, found_at, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_mult_homographies_dev")
 
 int mlpl_mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, double th, int var_th, unsigned max_planes,
                                unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength,
@@ -4187,36 +4141,31 @@ int mlpl_mult_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *
 // host pointers: the labels come back (n int32) and the masks of the planes FOUND are written from them -- no cap x n block anywhere
 int mlpl_mult_homographies_labels(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, int var_th, unsigned max_planes,
                                   unsigned min_pts_per_plane, uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength,
-                                  double *th_used, int32_t *found_at, int32_t *labels, uint8_t *masks) {
+                                  double *th_used, int32_t *found_at, int32_t *labels, uint8_t *masks) try {
     if (!mult_homographies_args_ok(ctx, p1, p2, n, th, rng_state, cap, n_planes, H, num_inl, strength, th_used)) {
         set_error("mlpl_mult_homographies: bad arguments (n must exceed 3, cap 0)");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dlabels = nullptr;
+    const double *dp1, *dp2;
+    void *dlabels = nullptr;
     int rc;
-    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
     const bool want = labels || masks;
-    if (want && (rc = ws_get(ctx, WS_MATCH, (size_t)n * 4, &dlabels))) return rc;
-    try {
-        rc = mult_homographies_dev(ctx, (const double *)dp1, (const double *)dp2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H,
-                                   num_inl, strength, th_used, nullptr, (int32_t *)dlabels, found_at, ctx->stream);
-        if (rc || !want || *n_planes <= 0) return rc;
-        std::vector<int32_t> tmp;
-        int32_t *lab = labels;
-        if (!lab) tmp.resize((size_t)n), lab = tmp.data();
-        MLPL_HIP_TRY(hipMemcpy(lab, dlabels, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (masks) {
-            std::memset(masks, 0, (size_t)*n_planes * n);
-            for (int j = 0; j < n; ++j)
-                if (lab[j] >= 0 && lab[j] < *n_planes) masks[(size_t)lab[j] * n + j] = 1;
-        }
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_mult_homographies: out of host memory");
-        return MLPL_E_NOMEM;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, want ? (size_t)n * 4 : 0, &dlabels))) return rc;
+    rc = mult_homographies_dev(ctx, dp1, dp2, n, th, var_th, max_planes, min_pts_per_plane, rng_state, cap, n_planes, H, num_inl, strength, th_used,
+                               nullptr, (int32_t *)dlabels, found_at, ctx->stream);
+    if (rc || !want || *n_planes <= 0) return rc;
+    std::vector<int32_t> tmp;
+    int32_t *lab = labels;
+    if (!lab) tmp.resize((size_t)n), lab = tmp.data();
+    MLPL_HIP_TRY(hipMemcpy(lab, dlabels, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (masks) {
+        std::memset(masks, 0, (size_t)*n_planes * n);
+        for (int j = 0; j < n; ++j)
+            if (lab[j] >= 0 && lab[j] < *n_planes) masks[(size_t)lab[j] * n + j] = 1;
     }
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_mult_homographies")
 
 int mlpl_mult_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, int n, double th, int var_th, unsigned max_planes, unsigned min_pts_per_plane,
                            uint64_t rng_state[2], int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, double *th_used, uint8_t *masks) {
@@ -4224,56 +4173,37 @@ int mlpl_mult_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, in
                                          nullptr, nullptr, masks);
 }
 
-static bool homography_batch_counts_ok(const char *name, int n_problems, const int32_t *counts, int stride) {
-    for (int b = 0; b < n_problems; ++b)
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: problem %d has %d correspondences (0 ... stride %d)", name, b, counts[b], stride);
-            return false;
-        }
-    return true;
-}
-
 int mlpl_homography_arrsac_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
-                                     uint64_t *rng_states, double *H, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, long long *stats, void *stream) {
+                                     uint64_t *rng_states, double *H, uint8_t *d_masks, int32_t *n_inliers, int32_t *status, long long *stats, void *stream) try {
     if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || !H || !d_masks || !n_inliers || !status || !(th > 0) ||
         !std::isfinite(th)) {
         set_error("mlpl_homography_arrsac_batch_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
-    if (!homography_batch_counts_ok("mlpl_homography_arrsac_batch_dev", n_problems, counts, stride)) return MLPL_E_BAD_INPUT;
+    if (!counts_in_range("mlpl_homography_arrsac_batch_dev", n_problems, counts, 0, stride)) return MLPL_E_BAD_INPUT;
     if (n_problems == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return homography_arrsac_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, rng_states, H, d_masks, n_inliers, status, stats,
-                                           pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_homography_arrsac_batch_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return homography_arrsac_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, rng_states, H, d_masks, n_inliers, status, stats,
+                                       pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_homography_arrsac_batch_dev")
 
 int mlpl_mult_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
                                      int var_th, unsigned max_planes, unsigned min_pts_per_plane, uint64_t *rng_states, int cap, int32_t *n_planes,
                                      double *H, int32_t *num_inl, double *strength, double *th_used, int32_t *found_at, int32_t *d_labels, int32_t *status,
-                                     void *stream) {
+                                     void *stream) try {
     if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || cap < 1 || !n_planes || !H || !num_inl || !strength ||
         !th_used || !status || !(th > 0) || !std::isfinite(th)) {
         set_error("mlpl_mult_homographies_batch_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
-    if (!homography_batch_counts_ok("mlpl_mult_homographies_batch_dev", n_problems, counts, stride)) return MLPL_E_BAD_INPUT;
+    if (!counts_in_range("mlpl_mult_homographies_batch_dev", n_problems, counts, 0, stride)) return MLPL_E_BAD_INPUT;
     if (n_problems == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return mult_homographies_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, var_th, max_planes, min_pts_per_plane, rng_states, cap, n_planes,
-                                           H, num_inl, strength, th_used, found_at, d_labels, status, pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_mult_homographies_batch_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return mult_homographies_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, var_th, max_planes, min_pts_per_plane, rng_states, cap, n_planes, H,
+                                       num_inl, strength, th_used, found_at, d_labels, status, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_mult_homographies_batch_dev")
 
-int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *idx, int m, int count, double *H, int32_t *ok) {
+int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const int32_t *idx, int m, int count, double *H, int32_t *ok) try {
     if (!ctx || !p1 || !p2 || !idx || !H || !ok || n < 4 || m < 4 || m > 12 || count < 1 || count > 512) {
         set_error("mlpl_debug_homography_models: bad arguments (4 <= m <= 12, 1 <= count <= 512)");
         return MLPL_E_BAD_INPUT;
@@ -4284,11 +4214,11 @@ int mlpl_debug_homography_models(mlpl_ctx *ctx, const double *p1, const double *
             return MLPL_E_BAD_INPUT;
         }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2;
+    const double *dp1, *dp2;
     int rc;
-    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
-    return homography_sample_models(ctx, (const double *)dp1, (const double *)dp2, n, idx, m, count, H, ok, ctx->stream);
-}
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
+    return homography_sample_models(ctx, dp1, dp2, n, idx, m, count, H, ok, ctx->stream);
+} MLPL_ENTRY_END("mlpl_debug_homography_models")
 
 // ---- pose from planes (homography_align_impl.h) ----
 // labels against P and num_inl: every label below P, exactly num_inl[k] labels k
@@ -4336,47 +4266,31 @@ static int alignment_checked(mlpl_ctx *ctx, const double *d_p1, const double *d_
 
 int mlpl_homography_alignment_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, const int32_t *d_labels, int n, int n_planes, const int32_t *num_inl,
                                   const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms, double *Hs_out, double info[24],
-                                  void *stream) {
+                                  void *stream) try {
     static const char *who = "mlpl_homography_alignment_dev";
     if (!alignment_args_ok(who, ctx, d_p1, d_p2, d_labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info)) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
-    try {
-        std::vector<int32_t> lab((size_t)n);
-        MLPL_HIP_TRY(hipMemcpyAsync(lab.data(), d_labels, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        MLPL_HIP_TRY(hipStreamSynchronize(s));
-        if (!alignment_labels_ok(who, lab.data(), n, n_planes, num_inl)) return MLPL_E_BAD_INPUT;
-        return alignment_checked(ctx, d_p1, d_p2, d_labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info, s);
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
-    }
-}
+    std::vector<int32_t> lab((size_t)n);
+    MLPL_HIP_TRY(hipMemcpyAsync(lab.data(), d_labels, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    MLPL_HIP_TRY(hipStreamSynchronize(s));
+    if (!alignment_labels_ok(who, lab.data(), n, n_planes, num_inl)) return MLPL_E_BAD_INPUT;
+    return alignment_checked(ctx, d_p1, d_p2, d_labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info, s);
+} MLPL_ENTRY_END("mlpl_homography_alignment_dev")
 
 int mlpl_homography_alignment(mlpl_ctx *ctx, const double *p1, const double *p2, const int32_t *labels, int n, int n_planes, const int32_t *num_inl,
-                              const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms, double *Hs_out, double info[24]) {
+                              const double H0[9], double tol, double R[9], double t[3], double E[9], double *norms, double *Hs_out, double info[24]) try {
     static const char *who = "mlpl_homography_alignment";
     if (!alignment_args_ok(who, ctx, p1, p2, labels, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info)) return MLPL_E_BAD_INPUT;
-    try {
-        if (!alignment_labels_ok(who, labels, n, n_planes, num_inl)) return MLPL_E_BAD_INPUT;
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
-    }
+    if (!alignment_labels_ok(who, labels, n, n_planes, num_inl)) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2, *dlab;
+    const double *dp1, *dp2;
+    void *dlab;
     int rc;
-    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n * 4, &dlab))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n * 4, &dlab))) return rc;
     MLPL_HIP_TRY(hipMemcpyAsync(dlab, labels, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    try {
-        return alignment_checked(ctx, (const double *)dp1, (const double *)dp2, (const int32_t *)dlab, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out,
-                                 info, ctx->stream);
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
-    }
-}
+    return alignment_checked(ctx, dp1, dp2, (const int32_t *)dlab, n, n_planes, num_inl, H0, tol, R, t, E, norms, Hs_out, info, ctx->stream);
+} MLPL_ENTRY_END("mlpl_homography_alignment")
 
 static bool pose_homographies_args_ok(const char *who, mlpl_ctx *ctx, const void *p1, const void *p2, int n, double th, const uint64_t *rng_state,
                                       const int *result, const double *R, const double *t, const double *E, const int *n_inliers, const void *mask_out, int cap,
@@ -4392,92 +4306,74 @@ static bool pose_homographies_args_ok(const char *who, mlpl_ctx *ctx, const void
 
 int mlpl_pose_homographies_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const uint8_t *d_mask_in, double th, int check_plane_strength,
                                int var_th, uint64_t rng_state[2], int *result, double R[9], double t[3], double E[9], int *n_inliers, uint8_t *d_mask_out,
-                               int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *d_labels, double *info, void *stream) {
+                               int cap, int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *d_labels, double *info, void *stream) try {
     static const char *who = "mlpl_pose_homographies_dev";
     if (!pose_homographies_args_ok(who, ctx, d_p1, d_p2, n, th, rng_state, result, R, t, E, n_inliers, d_mask_out, cap, n_planes, H, num_inl, strength))
         return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return pose_homographies_dev(ctx, d_p1, d_p2, n, d_mask_in, th, check_plane_strength, var_th, rng_state, result, R, t, E, n_inliers, d_mask_out, cap,
-                                     n_planes, H, num_inl, strength, d_labels, info, pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
-    }
-}
+    return pose_homographies_dev(ctx, d_p1, d_p2, n, d_mask_in, th, check_plane_strength, var_th, rng_state, result, R, t, E, n_inliers, d_mask_out, cap,
+                                 n_planes, H, num_inl, strength, d_labels, info, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_pose_homographies_dev")
 
 int mlpl_pose_homographies_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double th,
                                      int check_plane_strength, int var_th, uint64_t *rng_states, int32_t *results, double *R, double *t, double *E,
                                      int32_t *n_inliers, uint8_t *d_masks, int cap, int32_t *n_planes, double *H, int32_t *num_inl, double *strength,
-                                     int32_t *d_labels, double *info, int32_t *status, void *stream) {
+                                     int32_t *d_labels, double *info, int32_t *status, void *stream) try {
     static const char *who = "mlpl_pose_homographies_batch_dev";
     if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !rng_states || !results || !R || !t || !E || !n_inliers || !d_masks || cap < 1 ||
         !n_planes || !H || !num_inl || !strength || !status || !(th > 0) || !std::isfinite(th)) {
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
-    if (!homography_batch_counts_ok(who, n_problems, counts, stride)) return MLPL_E_BAD_INPUT;
+    if (!counts_in_range(who, n_problems, counts, 0, stride)) return MLPL_E_BAD_INPUT;
     if (n_problems == 0) return MLPL_OK;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {
-        return pose_homographies_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, check_plane_strength, var_th, rng_states, results, R, t, E,
-                                           n_inliers, d_masks, cap, n_planes, H, num_inl, strength, d_labels, info, status, pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
-    }
-}
+    return pose_homographies_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, th, check_plane_strength, var_th, rng_states, results, R, t, E, n_inliers,
+                                       d_masks, cap, n_planes, H, num_inl, strength, d_labels, info, status, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_pose_homographies_batch_dev")
 
 int mlpl_pose_homographies(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask_in, double th, int check_plane_strength, int var_th,
                            uint64_t rng_state[2], int *result, double R[9], double t[3], double E[9], int *n_inliers, uint8_t *mask_out, int cap,
-                           int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *labels, double *info) {
+                           int *n_planes, double *H, int32_t *num_inl, double *strength, int32_t *labels, double *info) try {
     static const char *who = "mlpl_pose_homographies";
     if (!pose_homographies_args_ok(who, ctx, p1, p2, n, th, rng_state, result, R, t, E, n_inliers, mask_out, cap, n_planes, H, num_inl, strength))
         return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2, *dmasks, *dlab;
+    const double *dp1, *dp2;
+    void *dmasks, *dlab;
     int rc;
-    if ((rc = homography_upload(ctx, p1, p2, n, &dp1, &dp2, nullptr))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n * 4, &dlab))) return rc;
     const size_t mask_b = (((size_t)n + 255) / 256) * 256;
     if ((rc = ws_get(ctx, WS_AUX6, 2 * mask_b, &dmasks))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n * 4, &dlab))) return rc;
     uint8_t *d_in = (uint8_t *)dmasks, *d_out = d_in + mask_b;
     if (mask_in) MLPL_HIP_TRY(hipMemcpyAsync(d_in, mask_in, (size_t)n, hipMemcpyHostToDevice, s));
-    try {
-        rc = pose_homographies_dev(ctx, (const double *)dp1, (const double *)dp2, n, mask_in ? d_in : nullptr, th, check_plane_strength, var_th, rng_state,
-                                   result, R, t, E, n_inliers, d_out, cap, n_planes, H, num_inl, strength, (int32_t *)dlab, info, s);
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
-    }
-    if (rc) return rc;
-    if (*result == 0) MLPL_HIP_TRY(hipMemcpy(mask_out, d_out, (size_t)n, hipMemcpyDeviceToHost));
+    if ((rc = pose_homographies_dev(ctx, dp1, dp2, n, mask_in ? d_in : nullptr, th, check_plane_strength, var_th, rng_state, result, R, t, E, n_inliers, d_out,
+                                    cap, n_planes, H, num_inl, strength, (int32_t *)dlab, info, s)))
+        return rc;
+    if (*result == 0 && (rc = download_mask(mask_out, d_out, n))) return rc;
     if (labels && n_planes && *n_planes > 0) MLPL_HIP_TRY(hipMemcpy(labels, dlab, (size_t)n * 4, hipMemcpyDeviceToHost));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_pose_homographies")
 
 int mlpl_robust_essential_refine(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const uint8_t *mask, const double E_init[9],
-                                 double th, double E_refined[9], int info[2]) {
+                                 double th, double E_refined[9], int info[2]) try {
     if (!ctx || !p1 || !p2 || !E_init || !E_refined || n < 1 || !(th > 0)) {
         set_error("mlpl_robust_essential_refine: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    void *dp1, *dp2, *dmask, *dE;
+    const double *dp1, *dp2;
+    void *dmask, *dE;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, (size_t)n * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, (size_t)n * 16, &dp2))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, (size_t)n, &dmask))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, (size_t)n, &dmask))) return rc;
     if ((rc = ws_get(ctx, WS_AUX7, 256, &dE))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
     if (mask) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
     else MLPL_HIP_TRY(hipMemsetAsync(dmask, 1, (size_t)n, s));
     MLPL_HIP_TRY(hipMemcpyAsync(dE, E_init, 72, hipMemcpyHostToDevice, s));
     double4 *pts = nullptr;
-    if ((rc = pack_points(ctx, (const double *)dp1, (const double *)dp2, n, &pts, s))) return rc;
+    if ((rc = pack_points(ctx, dp1, dp2, n, &pts, s))) return rc;
     double *d_E = (double *)dE;
     int32_t *d_info = (int32_t *)(d_E + 18);
     {
@@ -4494,10 +4390,10 @@ int mlpl_robust_essential_refine(mlpl_ctx *ctx, const double *p1, const double *
     std::memcpy(E_refined, h, 72);
     if (info) std::memcpy(info, h + 9, 8);
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_robust_essential_refine")
 
 int mlpl_refine_essential_linear(mlpl_ctx *ctx, const double *p1, const double *p2, int n, int method, double th, int steps, double th_mult,
-                                 double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done) {
+                                 double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done) try {
     static const char *who = "mlpl_refine_essential_linear";
     LinRefineArgs probe{};
     int rc;
@@ -4509,37 +4405,32 @@ int mlpl_refine_essential_linear(mlpl_ctx *ctx, const double *p1, const double *
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t nn = (size_t)std::max(n, 1);
-    void *dp1, *dp2, *dmask;
-    if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, nn, &dmask))) return rc;
-    if (n > 0) {
-        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
-    }
+    const double *dp1, *dp2;
+    void *dmask;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, nn, &dmask))) return rc;
+    if (n > 0) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
     const int32_t count = n;
     int32_t st = 0, ninl = 0, done = 0;
-    if ((rc = linear_refine_batch(ctx, 1, (const double *)dp1, (const double *)dp2, (int)nn, &count, &th, method, steps, th_mult, ph_mult, max_loss,
-                                  E, (uint8_t *)dmask, &ninl, &st, &done, s, who)))
+    if ((rc = linear_refine_batch(ctx, 1, dp1, dp2, (int)nn, &count, &th, method, steps, th_mult, ph_mult, max_loss, E, (uint8_t *)dmask, &ninl, &st, &done,
+                                  s, who)))
         return rc;
     if (st != 0) return st;
-    if (n > 0) MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    if ((rc = download_mask(mask, dmask, n))) return rc;
     if (n_inliers) *n_inliers = ninl;
     if (steps_done) *steps_done = done;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_refine_essential_linear")
 
 int mlpl_refine_essential_linear_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                                            const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
-                                           uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, void *stream) {
+                                           uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, void *stream) try {
     if (!ctx) {
         set_error("mlpl_refine_essential_linear_batch_dev: ctx is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return linear_refine_batch(ctx, n_problems, d_p1, d_p2, stride, counts, th, method, steps, th_mult, ph_mult, max_loss, E, d_masks, n_inliers,
                                status, steps_done, pick_stream(ctx, stream), "mlpl_refine_essential_linear_batch_dev");
-}
+} MLPL_ENTRY_END("mlpl_refine_essential_linear_batch_dev")
 
 static int kneip_refine_entry(mlpl_ctx *ctx, int B, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, const double *th, int method,
                               int steps, double th_mult, double ph_mult, double max_loss, double *E, uint8_t *d_masks, int32_t *n_inliers, int32_t *status,
@@ -4554,7 +4445,7 @@ static int kneip_refine_entry(mlpl_ctx *ctx, int B, const double *d_p1, const do
 
 int mlpl_refine_essential_linear_rt(mlpl_ctx *ctx, const double *p1, const double *p2, int n, int method, double th, int steps, double th_mult,
                                     double ph_mult, double max_loss, double E[9], uint8_t *mask, int *n_inliers, int *steps_done, double R[9], double t[3],
-                                    int *rt_valid, uint32_t seed, int *attempts_used) {
+                                    int *rt_valid, uint32_t seed, int *attempts_used) try {
     static const char *who = "mlpl_refine_essential_linear_rt";
     int rc;
     if ((method & 0xF) != 4 || method < 0 || method > 0xFF) {
@@ -4568,26 +4459,21 @@ int mlpl_refine_essential_linear_rt(mlpl_ctx *ctx, const double *p1, const doubl
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t nn = (size_t)std::max(n, 1);
-    void *dp1, *dp2, *dmask;
-    if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
-    if ((rc = ws_get(ctx, WS_MATCH, nn, &dmask))) return rc;
-    if (n > 0) {
-        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
-    }
+    const double *dp1, *dp2;
+    void *dmask;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2, nn, &dmask))) return rc;
+    if (n > 0) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask, (size_t)n, hipMemcpyHostToDevice, s));
     const int32_t count = n;
     int32_t st = 0, ninl = 0, done = 0, valid = *rt_valid ? 1 : 0, attempts = 0;
     double E_io[9], R_io[9], t_io[3] = {t[0], t[1], t[2]};
     std::memcpy(E_io, E, 72);
     std::memcpy(R_io, R, 72);
-    if ((rc = kneip_refine_entry(ctx, 1, (const double *)dp1, (const double *)dp2, (int)nn, &count, &th, method, steps, th_mult, ph_mult, max_loss, E_io,
-                                 (uint8_t *)dmask, &ninl, &st, &done, R_io, t_io, &valid, &seed, &attempts, s, who)))
+    if ((rc = kneip_refine_entry(ctx, 1, dp1, dp2, (int)nn, &count, &th, method, steps, th_mult, ph_mult, max_loss, E_io, (uint8_t *)dmask, &ninl, &st, &done,
+                                 R_io, t_io, &valid, &seed, &attempts, s, who)))
         return rc;
     if (attempts_used) *attempts_used = attempts;
     if (st != 0) return st;
-    if (n > 0) MLPL_HIP_TRY(hipMemcpy(mask, dmask, (size_t)n, hipMemcpyDeviceToHost));
+    if ((rc = download_mask(mask, dmask, n))) return rc;
     std::memcpy(E, E_io, 72);
     if (valid) {
         std::memcpy(R, R_io, 72);
@@ -4597,19 +4483,19 @@ int mlpl_refine_essential_linear_rt(mlpl_ctx *ctx, const double *p1, const doubl
     if (n_inliers) *n_inliers = ninl;
     if (steps_done) *steps_done = done;
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_refine_essential_linear_rt")
 
 int mlpl_refine_essential_linear_rt_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                                               const double *th, int method, int steps, double th_mult, double ph_mult, double max_loss, double *E,
                                               uint8_t *d_masks, int32_t *n_inliers, int32_t *status, int32_t *steps_done, double *R, double *t,
-                                              int32_t *rt_valid, const uint32_t *seeds, int32_t *attempts_used, void *stream) {
+                                              int32_t *rt_valid, const uint32_t *seeds, int32_t *attempts_used, void *stream) try {
     if (!ctx) {
         set_error("mlpl_refine_essential_linear_rt_batch_dev: ctx is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return kneip_refine_entry(ctx, n_problems, d_p1, d_p2, stride, counts, th, method, steps, th_mult, ph_mult, max_loss, E, d_masks, n_inliers, status,
                               steps_done, R, t, rt_valid, seeds, attempts_used, pick_stream(ctx, stream), "mlpl_refine_essential_linear_rt_batch_dev");
-}
+} MLPL_ENTRY_END("mlpl_refine_essential_linear_rt_batch_dev")
 
 int mlpl_kneip_refine_times(mlpl_ctx *ctx, int enable, double out[4]) {
     if (!ctx) {
@@ -4623,20 +4509,25 @@ int mlpl_kneip_refine_times(mlpl_ctx *ctx, int enable, double out[4]) {
 }
 
 int mlpl_recover_pose_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
-                                const double *E, double dist, uint8_t *d_masks, int32_t *n_good, double *R, double *t, void *stream) {
+                                const double *E, double dist, uint8_t *d_masks, int32_t *n_good, double *R, double *t, void *stream) try {
     if (!ctx) {
         set_error("mlpl_recover_pose_batch_dev: ctx is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return recover_pose_batch(ctx, n_problems, d_p1, d_p2, stride, counts, E, dist, d_masks, n_good, R, t, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_recover_pose_batch_dev")
+
+// what the three pair-batch entries ask of the arguments they share
+static bool pair_batch_args_ok(const mlpl_ctx *ctx, const DescView &dv, const float *d_kp1, const float *d_kp2, const double *K0, const double *K1,
+                               const mlpl_pair_result *out, int n_pairs, int nq, int nt) {
+    return ctx && dv.q && dv.t && d_kp1 && d_kp2 && K0 && K1 && out && n_pairs >= 1 && nq >= 1 && nt >= 2 && dv.cols >= 1 && !(dv.type == 5 && dv.cols > 1024);
 }
 
 // the body of mlpl_pair_pose_batch_dev / mlpl_pair_pose_batch_f32_dev
 static int pair_pose_batch_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv, int nq, int nt, const float *d_kp1, const float *d_kp2, const double K0[4],
                                  const double K1[4], double thresh, int max_iters, double confidence, int refit, const uint32_t *seeds, double dist,
                                  mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream, const char *who) {
-    if (!ctx || !dv.q || !dv.t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !seeds || n_pairs < 1 || nq < 1 || nt < 2 || dv.cols < 1 || max_iters < 1 ||
-        !(thresh > 0) || (dv.type == 5 && dv.cols > 1024)) {
+    if (!pair_batch_args_ok(ctx, dv, d_kp1, d_kp2, K0, K1, out, n_pairs, nq, nt) || !seeds || max_iters < 1 || !(thresh > 0)) {
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
@@ -4673,17 +4564,17 @@ static int pair_pose_batch_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv,
 
 int mlpl_pair_pose_batch_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                              const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
-                             int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+                             int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) try {
     return pair_pose_batch_entry(ctx, n_pairs, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, max_iters, confidence, refit, seeds, dist,
                                  out, d_matches_out, stream, "mlpl_pair_pose_batch_dev");
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_dev")
 
 int mlpl_pair_pose_batch_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
                                  const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters, double confidence,
-                                 int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+                                 int refit, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) try {
     return pair_pose_batch_entry(ctx, n_pairs, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, max_iters, confidence, refit, seeds, dist,
                                  out, d_matches_out, stream, "mlpl_pair_pose_batch_f32_dev");
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_f32_dev")
 
 // Two (or more) batched calls in flight on one GPU, inside the library: lane l = (ctxs[l], streams[l]) takes the l-th contiguous share of
 // the batch on a thread of its own (lane 0: the calling thread), so that one lane's host hops fall into the other's kernels.  The Python
@@ -4693,7 +4584,7 @@ int mlpl_pair_pose_batch_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, i
 int mlpl_pair_pose_batch_lanes_dev(mlpl_ctx *const *ctxs, void *const *streams, int lanes, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt,
                                    int nbytes, const float *d_kp1, const float *d_kp2, const double K0[4], const double K1[4], double thresh, int max_iters,
                                    double confidence, const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out,
-                                   double *lane_span_ms) {
+                                   double *lane_span_ms) try {
     if (!ctxs || !streams || lanes < 1 || lanes > 8 || n_pairs < 1 || !seeds || !out) {
         set_error("mlpl_pair_pose_batch_lanes_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -4740,25 +4631,20 @@ int mlpl_pair_pose_batch_lanes_dev(mlpl_ctx *const *ctxs, void *const *streams, 
             return rcs[l];
         }
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_lanes_dev")
 
-int mlpl_sorted_match_idx(const mlpl_dmatch *matches, int n, uint32_t *sorted_idx) {
+int mlpl_sorted_match_idx(const mlpl_dmatch *matches, int n, uint32_t *sorted_idx) try {
     if ((!matches || !sorted_idx) && n > 0) return MLPL_E_BAD_INPUT;
     if (n < 0) return MLPL_E_BAD_INPUT;
-    try {
-        sorted_match_idx(matches, n, sorted_idx);
-    } catch (const std::bad_alloc &) {
-        return MLPL_E_NOMEM;
-    }
+    sorted_match_idx(matches, n, sorted_idx);
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_sorted_match_idx")
 
 static int usac_check_params(const mlpl_usac_params *P, int n, const char *who);
 static int pair_pose_batch_usac_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv, int nq, int nt, const float *d_kp1, const float *d_kp2,
                                       const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac, const uint32_t *seeds, double dist,
                                       mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream, const char *who) {
-    if (!ctx || !dv.q || !dv.t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !seeds || !usac || n_pairs < 1 || nq < 1 || nt < 2 || dv.cols < 1 ||
-        (dv.type == 5 && dv.cols > 1024)) {
+    if (!pair_batch_args_ok(ctx, dv, d_kp1, d_kp2, K0, K1, out, n_pairs, nq, nt) || !seeds || !usac) {
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
@@ -4769,87 +4655,72 @@ static int pair_pose_batch_usac_entry(mlpl_ctx *ctx, int n_pairs, const DescView
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
     const int per = ctx->opt_pair_batch_seq > 0 ? ctx->opt_pair_batch_seq : kSeqBatchPairsPerCall;
-    try {
-        for (int at = 0; at < n_pairs; at += per) {
-            const int B = std::min(per, n_pairs - at);
-            rc = pair_pose_batch_usac_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt, d_kp1 + (size_t)at * nq * 2,
-                                          d_kp2 + (size_t)at * nt * 2, K0, K1, &chk, prosac, seeds + at, dist, out + at,
-                                          d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s);
-            if (rc) return rc;
-        }
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
+    for (int at = 0; at < n_pairs; at += per) {
+        const int B = std::min(per, n_pairs - at);
+        rc = pair_pose_batch_usac_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt, d_kp1 + (size_t)at * nq * 2,
+                                      d_kp2 + (size_t)at * nt * 2, K0, K1, &chk, prosac, seeds + at, dist, out + at,
+                                      d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s);
+        if (rc) return rc;
     }
     return MLPL_OK;
 }
 
 int mlpl_pair_pose_batch_usac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                                   const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
-                                  const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+                                  const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) try {
     return pair_pose_batch_usac_entry(ctx, n_pairs, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, usac, prosac, seeds, dist, out, d_matches_out,
                                       stream, "mlpl_pair_pose_batch_usac_dev");
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_usac_dev")
 
 int mlpl_pair_pose_batch_usac_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
                                       const float *d_kp2, const double K0[4], const double K1[4], const mlpl_usac_params *usac, int prosac,
-                                      const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+                                      const uint32_t *seeds, double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) try {
     return pair_pose_batch_usac_entry(ctx, n_pairs, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, usac, prosac, seeds, dist, out, d_matches_out,
                                       stream, "mlpl_pair_pose_batch_usac_f32_dev");
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_usac_f32_dev")
 
 static int pair_pose_batch_arrsac_entry(mlpl_ctx *ctx, int n_pairs, const DescView &dv, int nq, int nt, const float *d_kp1, const float *d_kp2,
                                         const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states, double dist,
                                         mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream, const char *who) {
-    if (!ctx || !dv.q || !dv.t || !d_kp1 || !d_kp2 || !K0 || !K1 || !out || !rng_states || n_pairs < 1 || nq < 1 || nt < 2 || dv.cols < 1 || !(thresh > 0) ||
-        (dv.type == 5 && dv.cols > 1024)) {
+    if (!pair_batch_args_ok(ctx, dv, d_kp1, d_kp2, K0, K1, out, n_pairs, nq, nt) || !rng_states || !(thresh > 0)) {
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
     const int per = ctx->opt_pair_batch_seq > 0 ? ctx->opt_pair_batch_seq : kSeqBatchPairsPerCall;
-    try {
-        for (int at = 0; at < n_pairs; at += per) {
-            const int B = std::min(per, n_pairs - at);
-            const int rc = pair_pose_batch_usac_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt,
-                                                    d_kp1 + (size_t)at * nq * 2, d_kp2 + (size_t)at * nt * 2, K0, K1, nullptr, 0, nullptr, dist, out + at,
-                                                    d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s, thresh, refine, rng_states + 2 * (size_t)at);
-            if (rc) return rc;
-        }
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", who);
-        return MLPL_E_NOMEM;
+    for (int at = 0; at < n_pairs; at += per) {
+        const int B = std::min(per, n_pairs - at);
+        const int rc = pair_pose_batch_usac_dev(ctx, B, dv.pair((size_t)at, nq, nt), nq, nt, d_kp1 + (size_t)at * nq * 2, d_kp2 + (size_t)at * nt * 2, K0, K1,
+                                                nullptr, 0, nullptr, dist, out + at, d_matches_out ? d_matches_out + (size_t)at * nq : nullptr, s, thresh,
+                                                refine, rng_states + 2 * (size_t)at);
+        if (rc) return rc;
     }
     return MLPL_OK;
 }
 
 int mlpl_pair_pose_batch_arrsac_dev(mlpl_ctx *ctx, int n_pairs, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, int nbytes, const float *d_kp1,
                                     const float *d_kp2, const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states, double dist,
-                                    mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+                                    mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) try {
     return pair_pose_batch_arrsac_entry(ctx, n_pairs, DescView{d_q, d_t, nbytes, 0}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, refine, rng_states, dist, out,
                                         d_matches_out, stream, "mlpl_pair_pose_batch_arrsac_dev");
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_arrsac_dev")
 
 int mlpl_pair_pose_batch_arrsac_f32_dev(mlpl_ctx *ctx, int n_pairs, const float *d_q, int nq, const float *d_t, int nt, int dim, const float *d_kp1,
                                         const float *d_kp2, const double K0[4], const double K1[4], double thresh, int refine, uint64_t *rng_states,
-                                        double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) {
+                                        double dist, mlpl_pair_result *out, mlpl_dmatch *d_matches_out, void *stream) try {
     return pair_pose_batch_arrsac_entry(ctx, n_pairs, DescView{d_q, d_t, dim, 5}, nq, nt, d_kp1, d_kp2, K0, K1, thresh, refine, rng_states, dist, out,
                                         d_matches_out, stream, "mlpl_pair_pose_batch_arrsac_f32_dev");
-}
+} MLPL_ENTRY_END("mlpl_pair_pose_batch_arrsac_f32_dev")
 
 int mlpl_ransac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts, double thresh,
                                     int max_iters, double confidence, const uint32_t *seeds, int recover_pose, double dist, mlpl_pair_result *out,
-                                    uint8_t *d_masks, void *stream) {
+                                    uint8_t *d_masks, void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !counts || !seeds || !out || n_problems < 1 || stride < 1 || max_iters < 1 || !(thresh > 0)) {
         set_error("mlpl_ransac_essential_batch_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
-    for (int b = 0; b < n_problems; ++b)
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("mlpl_ransac_essential_batch_dev: counts[%d] = %d outside [0, stride = %d]", b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
+    if (!counts_in_range("mlpl_ransac_essential_batch_dev", n_problems, counts, 0, stride)) return MLPL_E_BAD_INPUT;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
     const int per = ctx->opt_pair_batch > 0 ? ctx->opt_pair_batch : kBatchPairsPerCall;
@@ -4866,7 +4737,7 @@ int mlpl_ransac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double 
     }
     std::memcpy(ctx->last_batch_stats, acc, sizeof(acc));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_ransac_essential_batch_dev")
 
 int mlpl_pair_batch_last_stats(mlpl_ctx *ctx, long long stats[8]) {
     if (!ctx || !stats) return MLPL_E_BAD_INPUT;
@@ -4910,7 +4781,7 @@ static int usac_check_params(const mlpl_usac_params *P, int n, const char *who) 
 }
 
 int mlpl_usac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p2, int n, const mlpl_usac_params *params, double E[9],
-                            uint8_t *d_mask, double results[12], void *stream) {
+                            uint8_t *d_mask, double results[12], void *stream) try {
     if (!ctx || !d_p1 || !d_p2 || !E) {
         set_error("mlpl_usac_essential_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -4918,13 +4789,8 @@ int mlpl_usac_essential_dev(mlpl_ctx *ctx, const double *d_p1, const double *d_p
     int rc;
     if ((rc = usac_check_params(params, n, "mlpl_usac_essential_dev"))) return rc;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    try {  // the host side of a run allocates (sample cache, bit rows): nothing may unwind through the C boundary
-        return usac_essential_dev(ctx, d_p1, d_p2, n, params, E, d_mask, results, pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_usac_essential_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return usac_essential_dev(ctx, d_p1, d_p2, n, params, E, d_mask, results, pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_usac_essential_dev")
 
 int mlpl_usac_last_degeneracy(mlpl_ctx *ctx, double info[16], uint8_t *flags_rot, uint8_t *flags_nomot, int n) {
     if (!ctx || !info) {
@@ -4944,7 +4810,7 @@ int mlpl_usac_last_degeneracy(mlpl_ctx *ctx, double info[16], uint8_t *flags_rot
 }
 
 int mlpl_usac_essential(mlpl_ctx *ctx, const double *p1, const double *p2, int n, const mlpl_usac_params *params, double E[9],
-                        uint8_t *mask, double results[12]) {
+                        uint8_t *mask, double results[12]) try {
     if (!ctx || !p1 || !p2 || !E) {
         set_error("mlpl_usac_essential: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -4952,47 +4818,29 @@ int mlpl_usac_essential(mlpl_ctx *ctx, const double *p1, const double *p2, int n
     int rc;
     if ((rc = usac_check_params(params, n, "mlpl_usac_essential"))) return rc;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
-    void *dp1, *dp2;
-    const size_t pb = (size_t)std::max(n, 1) * 16;
-    if ((rc = ws_get(ctx, WS_AUX0, pb, &dp1)) || (rc = ws_get(ctx, WS_AUX1, pb, &dp2))) return rc;
-    MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    const double *dp1, *dp2;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     // the sequential part runs on the host and reads the correspondences there: it takes the caller's copies and returns the mask directly
-    try {
-        return usac_essential_dev(ctx, (const double *)dp1, (const double *)dp2, n, params, E, nullptr, results, ctx->stream, p1, p2, mask);
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_usac_essential: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return usac_essential_dev(ctx, dp1, dp2, n, params, E, nullptr, results, ctx->stream, p1, p2, mask);
+} MLPL_ENTRY_END("mlpl_usac_essential")
 
 int mlpl_usac_essential_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride, const int32_t *counts,
                                   const mlpl_usac_params *params, double *E, uint8_t *d_masks, double *results, int32_t *status, double *degen,
-                                  double *trace, int trace_cap, int32_t *trace_lens, void *stream) {
+                                  double *trace, int trace_cap, int32_t *trace_lens, void *stream) try {
     if (!ctx || n_problems < 0 || !d_p1 || !d_p2 || stride < 1 || !counts || !params || !E || !results || !status) {
         set_error("mlpl_usac_essential_batch_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
     }
-    int rc;
-    for (int b = 0; b < n_problems; ++b) {
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("mlpl_usac_essential_batch_dev: problem %d has %d correspondences (stride %d)", b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
-        if ((rc = usac_check_params(&params[b], counts[b], "mlpl_usac_essential_batch_dev"))) return rc;
-    }
+    if (!counts_in_range("mlpl_usac_essential_batch_dev", n_problems, counts, 0, stride)) return MLPL_E_BAD_INPUT;
+    for (int b = 0; b < n_problems; ++b)
+        if (const int rc = usac_check_params(&params[b], counts[b], "mlpl_usac_essential_batch_dev")) return rc;
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     UsacBatchTrace tr{trace, trace_cap, trace_lens};
     if (trace && trace_lens)
         for (int b = 0; b < n_problems; ++b) trace_lens[b] = 0;
-    try {
-        return usac_essential_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, params, E, d_masks, results, status, degen, trace ? &tr : nullptr,
-                                        pick_stream(ctx, stream));
-    } catch (const std::bad_alloc &) {
-        set_error("mlpl_usac_essential_batch_dev: out of host memory");
-        return MLPL_E_NOMEM;
-    }
-}
+    return usac_essential_batch_dev(ctx, n_problems, d_p1, d_p2, stride, counts, params, E, d_masks, results, status, degen, trace ? &tr : nullptr,
+                                    pick_stream(ctx, stream));
+} MLPL_ENTRY_END("mlpl_usac_essential_batch_dev")
 
 int mlpl_usac_last_stats(mlpl_ctx *ctx, long long stats[8]) {
     if (!ctx || !stats) return MLPL_E_BAD_INPUT;

@@ -507,31 +507,31 @@ static int recover_pose_impl(mlpl_ctx *ctx, const double *E, const double *t_onl
 // Device-resident correspondences (d_p1, d_p2: n x 2 doubles; d_Q: n x 3 doubles or NULL; d_mask_inout: n bytes or NULL, all on
 // the device); E, R, t are host.  One host hop (the four candidate counts decide which candidate's outputs are kept).
 extern "C" int mlpl_recover_pose_dev(mlpl_ctx *ctx, const double E[9], const double *d_p1, const double *d_p2, int n, double dist,
-                                     double R[9], double t[3], double *d_Q, uint8_t *d_mask_inout, void *stream) {
+                                     double R[9], double t[3], double *d_Q, uint8_t *d_mask_inout, void *stream) try {
     if (!E || !ctx) {
         set_error("mlpl_recover_pose_dev: ctx and E are mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return recover_pose_impl(ctx, E, nullptr, d_p1, d_p2, n, dist, R, t, d_Q, d_mask_inout, true, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_recover_pose_dev")
 
 extern "C" int mlpl_recover_pose(mlpl_ctx *ctx, const double E[9], const double *p1, const double *p2, int n, double dist,
-                                 double R[9], double t[3], double *Q, uint8_t *mask_inout) {
+                                 double R[9], double t[3], double *Q, uint8_t *mask_inout) try {
     if (!E) {
         set_error("mlpl_recover_pose: E is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return recover_pose_impl(ctx, E, nullptr, p1, p2, n, dist, R, t, Q, mask_inout);
-}
+} MLPL_ENTRY_END("mlpl_recover_pose")
 
 extern "C" int mlpl_recover_pose_translation(mlpl_ctx *ctx, const double t_only[3], const double *p1, const double *p2, int n,
-                                             double dist, double R[9], double t[3], double *Q, uint8_t *mask_inout) {
+                                             double dist, double R[9], double t[3], double *Q, uint8_t *mask_inout) try {
     if (!t_only) {
         set_error("mlpl_recover_pose_translation: t_only is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return recover_pose_impl(ctx, nullptr, t_only, p1, p2, n, dist, R, t, Q, mask_inout);
-}
+} MLPL_ENTRY_END("mlpl_recover_pose_translation")
 
 static int recover_pose_impl(mlpl_ctx *ctx, const double *E, const double *t_only, const double *p1, const double *p2, int n,
                              double dist, double *R, double *t, double *Q, uint8_t *mask_inout, bool dev, hipStream_t stream) {
@@ -542,13 +542,11 @@ static int recover_pose_impl(mlpl_ctx *ctx, const double *E, const double *t_onl
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = dev ? stream : ctx->stream;
-    void *dp1 = const_cast<double *>(p1), *dp2 = const_cast<double *>(p2), *dQ, *dmask, *dsmall;
+    const double *dp1 = p1, *dp2 = p2;
+    void *dQ, *dmask, *dsmall;
     int rc;
     const size_t nn = (size_t)std::max(n, 1);
-    if (!dev) {
-        if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
-        if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
-    }
+    if (!dev && (rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     if ((rc = ws_get(ctx, WS_AUX5, nn * 4 * 3 * 8, &dQ))) return rc;
     if ((rc = ws_get(ctx, WS_AUX6, nn * 5, &dmask))) return rc;
     if ((rc = ws_get(ctx, WS_AUX2, 4096, &dsmall))) return rc;
@@ -573,18 +571,13 @@ static int recover_pose_impl(mlpl_ctx *ctx, const double *E, const double *t_onl
         MLPL_HIP_TRY(hipMemcpyAsync(dP, hPt, sizeof(hPt), hipMemcpyHostToDevice, s));
     }
     MLPL_HIP_TRY(hipMemsetAsync(dcnt, 0, 16, s));
-    if (n > 0 && !dev) {
-        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        if (mask_inout) MLPL_HIP_TRY(hipMemcpyAsync(dmask_in, mask_inout, (size_t)n, hipMemcpyHostToDevice, s));
-    }
+    if (n > 0 && !dev && mask_inout) MLPL_HIP_TRY(hipMemcpyAsync(dmask_in, mask_inout, (size_t)n, hipMemcpyHostToDevice, s));
     if (n > 0 && dev && mask_inout) dmask_in = mask_inout;  // read in place; the chosen candidate's mask is copied back below
     if (E) hipLaunchKernelGGL(decompose_kernel, dim3(1), dim3(64), 0, s, (const double *)dE, dP);
     if (n > 0) {
         prof_mark(ctx, MLPL_PROF_RECOVER_POSE, 0, s);
-        hipLaunchKernelGGL(triangulate_kernel, dim3((n + 255) / 256, 4), dim3(256), 0, s, (const double *)dP, (const double *)dp1,
-                           (const double *)dp2, n, dist, mask_inout ? (const uint8_t *)dmask_in : (const uint8_t *)nullptr,
-                           (double *)dQ, (uint8_t *)dmask, dcnt);
+        hipLaunchKernelGGL(triangulate_kernel, dim3((n + 255) / 256, 4), dim3(256), 0, s, (const double *)dP, dp1, dp2, n, dist,
+                           mask_inout ? (const uint8_t *)dmask_in : (const uint8_t *)nullptr, (double *)dQ, (uint8_t *)dmask, dcnt);
         prof_mark(ctx, MLPL_PROF_RECOVER_POSE, 1, s);
     }
     MLPL_HIP_TRY(hipGetLastError());
@@ -641,14 +634,8 @@ static int triang_pts3d_run(mlpl_ctx *ctx, const char *who, int B, const double 
         set_error("%s: bad arguments", who);
         return MLPL_E_BAD_INPUT;
     }
-    int max_n = 0;
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] < 0 || counts[b] > stride) {
-            set_error("%s: counts[%d] = %d outside [0, stride = %d]", who, b, counts[b], stride);
-            return MLPL_E_BAD_INPUT;
-        }
-        max_n = std::max(max_n, counts[b]);
-    }
+    if (!counts_in_range(who, B, counts, 0, stride)) return MLPL_E_BAD_INPUT;
+    const int max_n = *std::max_element(counts, counts + B);
     if (B > 65535) {
         set_error("%s: at most 65535 problems per call", who);
         return MLPL_E_BAD_INPUT;
@@ -681,17 +668,17 @@ static int triang_pts3d_run(mlpl_ctx *ctx, const char *who, int B, const double 
 
 extern "C" int mlpl_triang_pts3d_batch_dev(mlpl_ctx *ctx, int n_problems, const double *d_p1, const double *d_p2, int stride,
                                            const int32_t *counts, const double *R, const double *t, double dist, uint8_t *d_masks,
-                                           double *d_Q, int32_t *n_good, void *stream) {
+                                           double *d_Q, int32_t *n_good, void *stream) try {
     if (!ctx) {
         set_error("mlpl_triang_pts3d_batch_dev: ctx is mandatory");
         return MLPL_E_BAD_INPUT;
     }
     return triang_pts3d_run(ctx, "mlpl_triang_pts3d_batch_dev", n_problems, d_p1, d_p2, stride, counts, R, t, dist, d_masks, d_Q, n_good,
                             pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_triang_pts3d_batch_dev")
 
 extern "C" int mlpl_triang_pts3d_dev(mlpl_ctx *ctx, const double R[9], const double t[3], const double *d_p1, const double *d_p2, int n,
-                                     double dist, double *d_Q, uint8_t *d_mask_inout, void *stream) {
+                                     double dist, double *d_Q, uint8_t *d_mask_inout, void *stream) try {
     if (!ctx || n < 0) {
         set_error("mlpl_triang_pts3d_dev: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -701,10 +688,10 @@ extern "C" int mlpl_triang_pts3d_dev(mlpl_ctx *ctx, const double R[9], const dou
     const int rc = triang_pts3d_run(ctx, "mlpl_triang_pts3d_dev", 1, d_p1, d_p2, std::max(n, 1), &count, R, t, dist, d_mask_inout, d_Q, &good,
                                     pick_stream(ctx, stream));
     return rc ? rc : good;
-}
+} MLPL_ENTRY_END("mlpl_triang_pts3d_dev")
 
 extern "C" int mlpl_triang_pts3d(mlpl_ctx *ctx, const double R[9], const double t[3], const double *p1, const double *p2, int n, double dist,
-                                 double *Q, uint8_t *mask_inout) {
+                                 double *Q, uint8_t *mask_inout) try {
     if (!ctx || !p1 || !p2 || n < 0) {
         set_error("mlpl_triang_pts3d: bad arguments");
         return MLPL_E_BAD_INPUT;
@@ -712,25 +699,17 @@ extern "C" int mlpl_triang_pts3d(mlpl_ctx *ctx, const double R[9], const double 
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t nn = (size_t)std::max(n, 1);
-    void *dp1, *dp2, *dQ = nullptr, *dmask = nullptr;
+    const double *dp1, *dp2;
+    void *dQ = nullptr, *dmask = nullptr;
     int rc;
-    if ((rc = ws_get(ctx, WS_AUX0, nn * 16, &dp1))) return rc;
-    if ((rc = ws_get(ctx, WS_AUX1, nn * 16, &dp2))) return rc;
+    if ((rc = upload_points(ctx, p1, p2, n, &dp1, &dp2))) return rc;
     if (Q && (rc = ws_get(ctx, WS_AUX5, nn * 24, &dQ))) return rc;
     if (mask_inout && (rc = ws_get(ctx, WS_AUX6, nn, &dmask))) return rc;
-    if (n > 0) {
-        MLPL_HIP_TRY(hipMemcpyAsync(dp1, p1, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        MLPL_HIP_TRY(hipMemcpyAsync(dp2, p2, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        if (mask_inout) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask_inout, (size_t)n, hipMemcpyHostToDevice, s));
-    }
+    if (n > 0 && mask_inout) MLPL_HIP_TRY(hipMemcpyAsync(dmask, mask_inout, (size_t)n, hipMemcpyHostToDevice, s));
     const int32_t count = n;
     int32_t good = 0;
-    if ((rc = triang_pts3d_run(ctx, "mlpl_triang_pts3d", 1, (const double *)dp1, (const double *)dp2, (int)nn, &count, R, t, dist, (uint8_t *)dmask,
-                               (double *)dQ, &good, s)))
-        return rc;
-    if (n > 0) {
-        if (Q) MLPL_HIP_TRY(hipMemcpy(Q, dQ, (size_t)n * 24, hipMemcpyDeviceToHost));
-        if (mask_inout) MLPL_HIP_TRY(hipMemcpy(mask_inout, dmask, (size_t)n, hipMemcpyDeviceToHost));
-    }
+    if ((rc = triang_pts3d_run(ctx, "mlpl_triang_pts3d", 1, dp1, dp2, (int)nn, &count, R, t, dist, (uint8_t *)dmask, (double *)dQ, &good, s))) return rc;
+    if (n > 0 && Q) MLPL_HIP_TRY(hipMemcpy(Q, dQ, (size_t)n * 24, hipMemcpyDeviceToHost));
+    if (mask_inout && (rc = download_mask(mask_inout, dmask, n))) return rc;
     return good;
-}
+} MLPL_ENTRY_END("mlpl_triang_pts3d")

@@ -428,7 +428,7 @@ extern "C" {
 
 int mlpl_rectify_parameters(const double R[9], const double t_in[3], const double K1[9], const double K2[9], const double *dist1, int n_dist1,
                             const double *dist2, int n_dist2, int width, int height, double alpha, int new_width, int new_height,
-                            double Rect1[9], double Rect2[9], double Knew_out[9], int roi[4], double P1[12], double P2[12], double info[8]) {
+                            double Rect1[9], double Rect2[9], double Knew_out[9], int roi[4], double P1[12], double P2[12], double info[8]) try {
     auto n_ok = [](int n) { return n == 0 || n == 4 || n == 5 || n == 8; };
     if (!R || !t_in || !K1 || !K2 || !Rect1 || !Rect2 || !Knew_out || !n_ok(n_dist1) || !n_ok(n_dist2) || (n_dist1 && !dist1) ||
         (n_dist2 && !dist2) || width < 1 || height < 1 || new_width < 0 || new_height < 0 || !finite_all(R, 9) || !finite_all(t_in, 3) ||
@@ -587,10 +587,10 @@ int mlpl_rectify_parameters(const double R[9], const double t_in[3], const doubl
             }
     }
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_rectify_parameters")
 
 int mlpl_rectify_maps_dev(mlpl_ctx *ctx, const double K[9], const double *dist, int n_dist, const double Rect[9], const double Knew[9],
-                          int width, int height, float *d_mapx, float *d_mapy, size_t map_stride, void *stream) {
+                          int width, int height, float *d_mapx, float *d_mapy, size_t map_stride, void *stream) try {
     MapParams p;
     if (!ctx || !K || !Rect || !Knew || !(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8) || (n_dist && !dist) || !size_ok(width, height) ||
         !d_mapx || !d_mapy || map_stride < (size_t)width || !make_map_params(K, dist, n_dist, Rect, Knew, &p)) {
@@ -599,10 +599,10 @@ int mlpl_rectify_maps_dev(mlpl_ctx *ctx, const double K[9], const double *dist, 
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_maps(p, width, height, d_mapx, d_mapy, map_stride, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_rectify_maps_dev")
 
 int mlpl_rectify_maps(mlpl_ctx *ctx, const double K[9], const double *dist, int n_dist, const double Rect[9], const double Knew[9], int width,
-                      int height, float *mapx, float *mapy) {
+                      int height, float *mapx, float *mapy) try {
     if (!ctx || !mapx || !mapy || !size_ok(width, height)) {
         set_error("mlpl_rectify_maps: bad arguments (sides in [1, 16384], two output maps)");
         return MLPL_E_BAD_INPUT;
@@ -618,10 +618,10 @@ int mlpl_rectify_maps(mlpl_ctx *ctx, const double K[9], const double *dist, int 
     MLPL_HIP_TRY(hipMemcpy2DAsync(mapy, (size_t)width * 4, dy, stride * 4, (size_t)width * 4, (size_t)height, hipMemcpyDeviceToHost, ctx->stream));
     MLPL_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_rectify_maps")
 
 int mlpl_remap_bilinear_dev(mlpl_ctx *ctx, const uint8_t *d_img, int width, int height, size_t step, const float *d_mapx, const float *d_mapy,
-                            size_t map_stride, int out_width, int out_height, uint8_t *d_out, size_t out_step, void *stream) {
+                            size_t map_stride, int out_width, int out_height, uint8_t *d_out, size_t out_step, void *stream) try {
     if (!ctx || !d_img || !size_ok(width, height) || step < (size_t)width || !d_mapx || !d_mapy || !size_ok(out_width, out_height) ||
         map_stride < (size_t)out_width || !d_out || out_step < (size_t)out_width) {
         set_error("mlpl_remap_bilinear: bad arguments (8-bit image and output with sides in [1, 16384], row step >= width, map stride >= output width)");
@@ -629,10 +629,10 @@ int mlpl_remap_bilinear_dev(mlpl_ctx *ctx, const uint8_t *d_img, int width, int 
     }
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_remap(d_img, width, height, step, d_mapx, d_mapy, map_stride, out_width, out_height, d_out, out_step, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_remap_bilinear_dev")
 
 int mlpl_remap_bilinear(mlpl_ctx *ctx, const uint8_t *img, int width, int height, size_t step, const float *mapx, const float *mapy, int out_width,
-                        int out_height, uint8_t *out, size_t out_step) {
+                        int out_height, uint8_t *out, size_t out_step) try {
     if (!ctx || !img || !size_ok(width, height) || step < (size_t)width || !mapx || !mapy || !size_ok(out_width, out_height) || !out ||
         out_step < (size_t)out_width) {
         set_error("mlpl_remap_bilinear: bad arguments (8-bit image and output with sides in [1, 16384], row step >= width)");
@@ -656,11 +656,11 @@ int mlpl_remap_bilinear(mlpl_ctx *ctx, const uint8_t *img, int width, int height
     MLPL_HIP_TRY(hipMemcpy2DAsync(out, out_step, dout, ostep, (size_t)out_width, (size_t)out_height, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_remap_bilinear")
 
 int mlpl_rectify_images_dev(mlpl_ctx *ctx, int batch, const uint8_t *d_img1, const uint8_t *d_img2, int width, int height, size_t step,
                             size_t batch_stride, const double *params, int out_width, int out_height, uint8_t *d_out1, uint8_t *d_out2,
-                            size_t out_step, size_t out_batch_stride, void *stream) {
+                            size_t out_step, size_t out_batch_stride, void *stream) try {
     if (!ctx || batch < 1 || batch > 32767 || !d_img1 || !d_img2 || !size_ok(width, height) || step < (size_t)width ||
         (batch > 1 && batch_stride < step * (size_t)height) || !params || !size_ok(out_width, out_height) || !d_out1 || !d_out2 ||
         out_step < (size_t)out_width || (batch > 1 && out_batch_stride < out_step * (size_t)out_height)) {
@@ -671,10 +671,10 @@ int mlpl_rectify_images_dev(mlpl_ctx *ctx, int batch, const uint8_t *d_img1, con
     MLPL_HIP_TRY(hipSetDevice(ctx->device));
     return launch_fused(ctx, batch, d_img1, d_img2, width, height, step, batch_stride, params, out_width, out_height, d_out1, d_out2, out_step,
                         out_batch_stride, pick_stream(ctx, stream));
-}
+} MLPL_ENTRY_END("mlpl_rectify_images_dev")
 
 int mlpl_rectify_images(mlpl_ctx *ctx, const uint8_t *img1, const uint8_t *img2, int width, int height, size_t step, const double *params,
-                        int out_width, int out_height, uint8_t *out1, uint8_t *out2, size_t out_step) {
+                        int out_width, int out_height, uint8_t *out1, uint8_t *out2, size_t out_step) try {
     if (!ctx || !img1 || !img2 || !size_ok(width, height) || step < (size_t)width || !params || !size_ok(out_width, out_height) || !out1 || !out2 ||
         out_step < (size_t)out_width) {
         set_error("mlpl_rectify_images: bad arguments (8-bit images and outputs with sides in [1, 16384], row step >= width)");
@@ -698,6 +698,6 @@ int mlpl_rectify_images(mlpl_ctx *ctx, const uint8_t *img1, const uint8_t *img2,
     MLPL_HIP_TRY(hipMemcpy2DAsync(out2, out_step, o2, ostep, (size_t)out_width, (size_t)out_height, hipMemcpyDeviceToHost, s));
     MLPL_HIP_TRY(hipStreamSynchronize(s));
     return MLPL_OK;
-}
+} MLPL_ENTRY_END("mlpl_rectify_images")
 
 }  // extern "C"
